@@ -8,12 +8,17 @@ resident in HBM: pack the queries -> fused pairwise/logsumexp sweep -> finish/re
 
     python bench.py --gpus N --steps K --warmup W        # N > 1 without WORLD_SIZE: starts its own N ranks (see launch_ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+    python bench.py --gpus 1 --steps K --warmup W --full # + roofline, secondary legs, parity, CPU baselines, bench_full.json
+    python bench.py ... --dump-outputs DIR               # + DIR/slogl.npy: the slogl of the last timed step (float64)
+
+A plain run sets up, warms up, times the K steps and prints the headline line (the contract fields and the configuration);
+everything else this file measures runs only with --full.
 
 Multi-GPU (weak scaling): the fitted training set is replicated on every GPU, each rank owns its own
 N_test test rows (independent units = test rows); there is no data-path collective — the
 only exchange is one all-reduce of the K per-step partial sums at the end of the timed region.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel = kde_sweep,
+Prints ONE JSON line (rank 0) with the contract fields; with --full also `roofline` (dominant kernel = kde_sweep,
 timed with HIP events on the library's own stream) and `cpu_baseline` (the oracle's restatement of the
 reference algorithm on the host cores, bounded sample; rank 0, N=1 only).
 """
@@ -821,10 +826,38 @@ def _pick(src, *keys, **renamed):
     return out
 
 
-def compact_line(out, full_name):
-    """The ONE stdout line, numbers only and under 5 KB (the driver's record keeps the parsed headline keys and the last ~6 KB of the line:
-    round 5's 25 KB line lost its C3 / C4 / cv_weak legs there).  Everything else - prose, methods, samples, per-flip lists - goes to the
-    verbose object `full_name` beside it."""
+def headline(args, world, elapsed, slogl, ranks_seen, devs):
+    """The contract fields of the result line and the run's configuration: everything a plain run (no --full) reports."""
+    return {
+        "metric": "KDE slogl M-samples/s",
+        "value": args.n_test * world * args.steps / elapsed / 1e6,
+        "unit": "M-samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic",
+        "config": {
+            "workload": f"C2: {'ProductKDE' if args.kde == 'product' else 'KDE'}.slogl {args.dtype}, N_train={args.n_train}, "
+                        f"N_test={args.n_test} per GPU, d={D}, normal-reference {'diagonal' if args.kde == 'product' else 'full'} bandwidth",
+            "parallelism": f"test rows sharded over {world} GPU(s), training set replicated",
+            "ranks": world,
+            "backend": (args.backend + (" (RCCL)" if args.backend == "nccl" else "")) if world > 1 else None,
+            "rccl_ranks_seen": ranks_seen if args.backend == "nccl" else None,
+            "ranks_seen": ranks_seen,
+            "rank_devices": devs,
+            "pairs_per_step_per_gpu": float(args.n_train) * float(args.n_test),
+            "slogl_step0_rank_sum": slogl,
+        },
+    }
+
+
+def _head(out):
+    """The headline keys and the configuration of the line (all of a plain run's line)."""
     head = {k: _num(out[k]) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                      "vs_baseline", "dtype", "data") if k in out}
     cfg = out.get("config", {})
@@ -832,6 +865,14 @@ def compact_line(out, full_name):
                                                     "pairs_per_step_per_gpu", "slogl_step0_rank_sum") if k in cfg}
     if cfg.get("rank_devices"):
         head["config"]["rank_devices"] = [list(d[:2]) for d in cfg["rank_devices"] if d]
+    return head
+
+
+def compact_line(out, full_name):
+    """The ONE stdout line of a --full run, numbers only and under 5 KB (the driver's record keeps the parsed headline keys and the last
+    ~6 KB of the line: round 5's 25 KB line lost its C3 / C4 / cv_weak legs there).  Everything else - prose, methods, samples, per-flip
+    lists - goes to the verbose object `full_name` beside it."""
+    head = _head(out)
     r = out.get("roofline", {})
     head["roofline"] = _pick(r, "kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "avg_launch_ms", "exp_unit")
     if isinstance(r.get("dp_issue_util"), dict):
@@ -1036,7 +1077,16 @@ def main():
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the secondary_* legs of the default run (C3, C5, C1, f32, weak-scaling CV)")
     ap.add_argument("--hc-rows", type=int, default=0)
     ap.add_argument("--hc-max-iters", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel roofline, the secondary hill-climb / f32 / C1 legs, RCCL world-1 child, "
+                         "host end-to-end leg, oracle parity and CPU baselines, bench_full.json (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (its slogl, float64) as DIR/slogl.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and args.hc not in ("auto", "none"):
+        ap.error(f"--hc {args.hc} selects a secondary leg: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))   # before any torch / HIP call in this process
@@ -1112,7 +1162,8 @@ def main():
     for i in range(args.warmup):
         step(i)
     sync_all()
-    ctx.set_profiling(True)
+    if args.full:   # per-kernel HIP events for the roofline object
+        ctx.set_profiling(True)
     t0 = time.perf_counter()
     for i in range(args.steps):
         step(args.warmup + i)
@@ -1121,14 +1172,28 @@ def main():
         dist.all_reduce(partial)  # the only exchange: K scalars
     sync_all()
     elapsed = time.perf_counter() - t0
-    sweep_ms, sweep_n = ctx.kernel_time(_lib.PBN_K_SWEEP)
-    pack_ms, _ = ctx.kernel_time(_lib.PBN_K_PACK)
-    fin_ms, _ = ctx.kernel_time(_lib.PBN_K_FINISH)
-    ctx.set_profiling(False)
+    if args.full:
+        sweep_ms, sweep_n = ctx.kernel_time(_lib.PBN_K_SWEEP)
+        pack_ms, _ = ctx.kernel_time(_lib.PBN_K_PACK)
+        fin_ms, _ = ctx.kernel_time(_lib.PBN_K_FINISH)
+        ctx.set_profiling(False)
     if dist is not None:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: one slogl (after the all-reduce: the sum over the ranks)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = partial[args.warmup + args.steps - 1:].cpu().numpy().astype(np.float64)
+        np.save(os.path.join(args.dump_outputs, "slogl.npy"), last)
+
+    out = headline(args, world, elapsed, float(partial[args.warmup].item()), ranks_seen, devs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(_head(out), separators=(",", ":")), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        sys.exit(0)
 
     hc_out = None
     legs = {}
@@ -1230,8 +1295,6 @@ def main():
         slogl = float(partial[args.warmup].item())
         leg("secondary_f32", f32_leg)
 
-    total_samples = args.n_test * world * args.steps
-    value = total_samples / elapsed / 1e6
     slogl = float(partial[args.warmup].item())
 
     if rank == 0:
@@ -1255,50 +1318,24 @@ def main():
                          f"pair value -> {peak_pairs / 1e12:.2f}e12 pairs/s x (3d+2) flop; the distances run as f16x2 on the 16-bit matrix "
                          f"cores under the VALU work (the FP32 vector peak, {FP32_PEAK_TFLOPS} TFLOP/s, is not the binding unit)")
         traffic, traffic_source = pmc_traffic(args)
-        out = {
-            "metric": "KDE slogl M-samples/s",
-            "value": value,
-            "unit": "M-samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {
-                "workload": f"C2: {'ProductKDE' if args.kde == 'product' else 'KDE'}.slogl {args.dtype}, N_train={args.n_train}, "
-                            f"N_test={args.n_test} per GPU, d={D}, normal-reference {'diagonal' if args.kde == 'product' else 'full'} bandwidth",
-                "parallelism": f"test rows sharded over {world} GPU(s), training set replicated",
-                "ranks": world,
-                "backend": (args.backend + (" (RCCL)" if args.backend == "nccl" else "")) if world > 1 else None,
-                "rccl_ranks_seen": ranks_seen if args.backend == "nccl" else None,
-                "ranks_seen": ranks_seen,
-                "rank_devices": devs,
-                "pairs_per_step_per_gpu": pairs,
-                "slogl_step0_rank_sum": slogl,
-            },
-            "roofline": {
-                "kernel": "kde_sweep_kernel" if args.dtype == "f64" else "kde_sweep_f16_w32_kernel",
-                "bound": "mfma",
-                "achieved": achieved_tf,
-                "peak": peak_tf,
-                "unit": "TFLOP/s",
-                "frac": achieved_tf / peak_tf,
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-                "note": "compute-bound sweep (SURVEY.md §8d): algorithmic flops = (3d+2) per train/test pair (exp counted as 1) "
-                        + peak_note + "; sweep launch duration from HIP events on the library stream",
-                "avg_launch_ms": sweep_s * 1e3,
-                "gpairs_per_s": pairs / sweep_s / 1e9,
-                "hbm_algorithmic_bytes": alg_bytes,
-                "hbm_achieved_GBs": alg_bytes / sweep_s / 1e9,
-                "hbm_frac_of_8TBs": alg_bytes / sweep_s / 1e9 / HBM_PEAK_GBS,
-                "pack_ms": pack_ms / max(sweep_n, 1),
-                "finish_ms": fin_ms / max(sweep_n, 1),
-            },
+        out["roofline"] = {
+            "kernel": "kde_sweep_kernel" if args.dtype == "f64" else "kde_sweep_f16_w32_kernel",
+            "bound": "mfma",
+            "achieved": achieved_tf,
+            "peak": peak_tf,
+            "unit": "TFLOP/s",
+            "frac": achieved_tf / peak_tf,
+            "traffic": traffic,
+            "traffic_source": traffic_source,
+            "note": "compute-bound sweep (SURVEY.md §8d): algorithmic flops = (3d+2) per train/test pair (exp counted as 1) "
+                    + peak_note + "; sweep launch duration from HIP events on the library stream",
+            "avg_launch_ms": sweep_s * 1e3,
+            "gpairs_per_s": pairs / sweep_s / 1e9,
+            "hbm_algorithmic_bytes": alg_bytes,
+            "hbm_achieved_GBs": alg_bytes / sweep_s / 1e9,
+            "hbm_frac_of_8TBs": alg_bytes / sweep_s / 1e9 / HBM_PEAK_GBS,
+            "pack_ms": pack_ms / max(sweep_n, 1),
+            "finish_ms": fin_ms / max(sweep_n, 1),
         }
         if args.dtype == "f64":
             out["roofline"]["dp_issue_util"] = dp_issue_util()

@@ -159,3 +159,11 @@ def test_compact_line_carries_every_leg_in_under_6000_bytes():
                 assert len(v) <= 140, (path + k, len(v))
     no_prose(out)
     assert out["full"] == "bench_full.json"
+
+
+def test_leg_options_need_full():
+    """A plain run times the headline only: asking it for a secondary leg (that runs with --full), or for no timed step at all, is an
+    argument error raised before torch or HIP is touched."""
+    for argv, msg in ((["--hc", "c3"], "add --full"), (["--steps", "0"], "--steps must be >= 1")):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=120)
+        assert out.returncode == 2 and msg in out.stderr and out.stdout == "", (argv, out.stderr[-500:])

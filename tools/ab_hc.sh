@@ -6,7 +6,7 @@ for spec in "$@"; do
   n=${spec%%=*}; lib=${spec#*=}
   if [ "$lib" = main ]; then unset PBN_LIB; else export PBN_LIB=$PWD/$lib; fi
   for leg in cv64 c3; do
-    python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --hc $leg --hc-max-iters 1 2>> $OUT/$n.err | tail -1 > $OUT/$n.$leg.json; cp bench_full.json $OUT/$n.$leg.full.json
+    python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --hc $leg --hc-max-iters 1 2>> $OUT/$n.err | tail -1 > $OUT/$n.$leg.json; cp bench_full.json $OUT/$n.$leg.full.json
   done
   python - $OUT $n <<'P'
 import json, sys

@@ -6,8 +6,8 @@ mkdir -p $OUT
 for spec in "$@"; do
   n=${spec%%=*}; lib=${spec#*=}
   if [ "$lib" = main ]; then unset PBN_LIB; else export PBN_LIB=$PWD/$lib; fi
-  python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-e2e > $OUT/$n.line.json 2> $OUT/$n.err; cp bench_full.json $OUT/$n.full.json
-  python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --hc cv64 --hc-max-iters 1 > $OUT/$n.cv64.json 2>> $OUT/$n.err
+  python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-e2e > $OUT/$n.line.json 2> $OUT/$n.err; cp bench_full.json $OUT/$n.full.json
+  python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --hc cv64 --hc-max-iters 1 > $OUT/$n.cv64.json 2>> $OUT/$n.err
   python - $OUT $n <<'P'
 import json, sys
 out, n = sys.argv[1:3]

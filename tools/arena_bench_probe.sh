@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 run() {
 echo "== $*"
-env "$@" python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "
+env "$@" python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read())
 print(' '.join('%s %.3f' % (k[10:], d[k]['estimate_s']) for k in d if k.startswith('secondary_') and 'estimate_s' in d[k]), 'c5 8-rank', d['secondary_c5']['eight_rank_estimate'].get('per_rank_s'), d['secondary_c5']['eight_rank_estimate'].get('slowest_over_mean_share'))"
 }

@@ -1,16 +1,18 @@
 # rocprofv3 kernel trace of a hill-climb config (default C5) with the default issue lanes: device busy time (union of the kernel
 # intervals) against the span, per-kernel totals, and the sweep launches bucketed by grid size.
-#   bash tools/c5_trace.sh [max_iters] [output dir under gpurun_out] [hc config: c5mmhc, cv64, c3]
+#   bash tools/c5_trace.sh [max_iters] [trace name] [hc config: c5mmhc, cv64, c3]
+# The trace folder <trace name> and its log go under $TRACE_DIR (an absolute path; default: a new temporary directory).
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 ITERS=${1:-1000000}
 OUT=${2:-c5_trace}
 HC=${3:-c5mmhc}
-rm -rf $R/gpurun_out/$OUT
-mkdir -p $R/gpurun_out/$OUT
-rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/$OUT -- python3 $R/bench.py --no-c3 --no-e2e --no-cpu-baseline --hc $HC --hc-max-iters $ITERS --steps 1 --warmup 1 > $R/gpurun_out/$OUT.log 2>&1
+T=${TRACE_DIR:-$(mktemp -d)}/$OUT
+rm -rf $T
+mkdir -p $T
+rocprofv3 --kernel-trace --output-format csv -d $T -- python3 $R/bench.py --full --no-c3 --no-e2e --no-cpu-baseline --hc $HC --hc-max-iters $ITERS --steps 1 --warmup 1 > $T.log 2>&1
 cd $R
-t=$(find gpurun_out/$OUT -name "*kernel_trace.csv" | head -1)
+t=$(find $T -name "*kernel_trace.csv" | head -1)
 python3 - $t <<'PY'
 import csv, sys, collections, re
 rows = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].replace("(anonymous namespace)::", ""), int(r["Grid_Size_X"]) // max(1, int(r["Workgroup_Size_X"])))
@@ -46,5 +48,5 @@ print("sweep launches by grid size (workgroups, rounded up to a power of two):")
 for k in sorted(b):
     print(f"  <= {k:7d}: {b[k][1]:6d} launches {b[k][0] / 1e9:6.2f} s  {b[k][0] / b[k][1] / 1e3:8.1f} us each")
 PY
-tail -1 gpurun_out/$OUT.log | cut -c1-300
-find gpurun_out/$OUT -name "*kernel_trace.csv" -delete
+tail -1 $T.log | cut -c1-300
+find $T -name "*kernel_trace.csv" -delete

@@ -1,7 +1,7 @@
 # SQ counters of ONE kernel family inside a bench.py command (separate --pmc passes, never with a trace domain; the program directly after `--`).
 #   bash tools/pmc_kernel.sh <kernel substring> <output name> <bench.py arguments...>
 # e.g. the tile-moment pass of C3's first iteration:
-#   bash tools/pmc_kernel.sh kde_moment_group_kernel moment_pmc --no-e2e --no-cpu-baseline --no-extra-legs --hc c3 --hc-max-iters 1 --steps 1 --warmup 1
+#   bash tools/pmc_kernel.sh kde_moment_group_kernel moment_pmc --full --no-e2e --no-cpu-baseline --no-extra-legs --hc c3 --hc-max-iters 1 --steps 1 --warmup 1
 # Writes gpurun_out/<output name>.txt: per-dispatch means, the counters as shares of the SIMD cycles, and the git blob hash of kde_kernels.hip they were taken on.
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
