@@ -83,7 +83,7 @@ __global__ __launch_bounds__(GB) void group_keys_kernel(GDev g) {
     // (tools/farfield_feasibility.py: median tile radius 0.34 bandwidths against 0.15 with fine cells)
     const double scale = (bits >= 12 && g.fine_keys) ? (double)(1 << (bits - 4)) : (bits >= 8 ? 16.0 : (bits >= 6 ? 8.0 : 4.0));   // (3 / 4 key dimensions: finer cells change nothing, the cells are smaller than the tiles already)
     uint32_t key = 0;
-    uint32_t cells[PBN_PRUNE_PD];
+    uint32_t cells[PBN_PRUNE_PD_NARROW];
     for (int i = 0; i < kd; ++i) {
         double u = 0.0;
         for (int j = 0; j <= i; ++j) u = __builtin_fma(P.Wg[i * d + j], xc[j], u);
@@ -332,18 +332,18 @@ __global__ __launch_bounds__(256) void group_tile_box_kernel(GDev g) {
     const GPool& P = g.pools[U.pool];
     const int d = P.d, pd = P.kd;
     const bool valid = r < U.N;
-    double lo[PBN_PRUNE_PD], hi[PBN_PRUNE_PD];
+    double lo[PBN_PRUNE_PD_NARROW], hi[PBN_PRUNE_PD_NARROW];
 #pragma unroll
-    for (int k = 0; k < PBN_PRUNE_PD; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+    for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
     if (valid) {
         const double* z = (const double*)(g.arena + U.zs) + (int64_t)r * d;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k)
+        for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k)
             if (k < pd) { const double v = z[k]; if (v == v) { lo[k] = v; hi[k] = v; } }
     }
     for (int off = 1; off < 16; off <<= 1) {
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k) {
+        for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k) {
             const double l = __shfl_xor(lo[k], off), h = __shfl_xor(hi[k], off);
             lo[k] = l < lo[k] ? l : lo[k];
             hi[k] = h > hi[k] ? h : hi[k];
@@ -365,18 +365,18 @@ __global__ __launch_bounds__(64) void group_batch_box_kernel(GDev g) {
     const int split = blockIdx.x / nbps, k = blockIdx.x - split * nbps;
     const int t0 = split * U.tps, t1 = t0 + U.tps < U.ntiles ? t0 + U.tps : U.ntiles;
     const int t = t0 + 64 * k + (int)threadIdx.x;
-    double lo[PBN_PRUNE_PD], hi[PBN_PRUNE_PD];
+    double lo[PBN_PRUNE_PD_NARROW], hi[PBN_PRUNE_PD_NARROW];
 #pragma unroll
-    for (int i = 0; i < PBN_PRUNE_PD; ++i) { lo[i] = INFINITY; hi[i] = -INFINITY; }
+    for (int i = 0; i < PBN_PRUNE_PD_NARROW; ++i) { lo[i] = INFINITY; hi[i] = -INFINITY; }
     if (t < t1) {
         const double* bx = (const double*)(g.arena + U.box) + (int64_t)t * 2 * pd;
 #pragma unroll
-        for (int i = 0; i < PBN_PRUNE_PD; ++i)
+        for (int i = 0; i < PBN_PRUNE_PD_NARROW; ++i)
             if (i < pd) { lo[i] = bx[i]; hi[i] = bx[pd + i]; }
     }
     for (int off = 1; off < 64; off <<= 1) {
 #pragma unroll
-        for (int i = 0; i < PBN_PRUNE_PD; ++i) {
+        for (int i = 0; i < PBN_PRUNE_PD_NARROW; ++i) {
             const double l = __shfl_xor(lo[i], off), h = __shfl_xor(hi[i], off);
             lo[i] = l < lo[i] ? l : lo[i];
             hi[i] = h > hi[i] ? h : hi[i];
@@ -497,14 +497,14 @@ __global__ __launch_bounds__(256) void group_prepass_kernel(GDev g) {
     // the pruning threshold may stand on the bound of the query's SUM (>= the sum over the scanned rows): what a skipped tile
     // could add is then below 2^-margin of the sum itself, not merely of its largest term
     double thr = valid ? (g.use_sum_bound && acc > 0.0 ? best + log2(acc) : best) : INFINITY;
-    double lob[PBN_PRUNE_PD], hib[PBN_PRUNE_PD];
+    double lob[PBN_PRUNE_PD_NARROW], hib[PBN_PRUNE_PD_NARROW];
 #pragma unroll
-    for (int k = 0; k < PBN_PRUNE_PD; ++k) { lob[k] = (valid && k < pd) ? z[k] : INFINITY; hib[k] = (valid && k < pd) ? z[k] : -INFINITY; }
+    for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k) { lob[k] = (valid && k < pd) ? z[k] : INFINITY; hib[k] = (valid && k < pd) ? z[k] : -INFINITY; }
     for (int off = 1; off < 16; off <<= 1) {
         const double o = __shfl_xor(thr, off);
         thr = o < thr ? o : thr;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k) {
+        for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k) {
             const double l = __shfl_xor(lob[k], off), h = __shfl_xor(hib[k], off);
             lob[k] = l < lob[k] ? l : lob[k];
             hib[k] = h > hib[k] ? h : hib[k];
@@ -897,7 +897,7 @@ void kde_group_run(pbn_ctx* ctx, const pbn_table* t, GroupBatch& b, double* dev_
     if (!force_f64 && t->dtype != PBN_F64 && !use_f16x2(t->dtype)) throw invalid_error("grouped KDE evaluation: fp64 tables, or fp32 tables on the f16 matrix cores");
     HIP_CHECK(hipSetDevice(ctx->device));
     for (const GPool& P : b.pools) {
-        if (P.d < 1 || P.d > PBN_GROUP_MAX_D || P.kd < 1 || P.kd > PBN_PRUNE_PD || P.kd > P.d || P.R < 1 || P.R > PBN_GROUP_MAX_R || P.n < 1)
+        if (P.d < 1 || P.d > PBN_GROUP_MAX_D || P.kd < 1 || P.kd > PBN_PRUNE_PD_NARROW || P.kd > P.d || P.R < 1 || P.R > PBN_GROUP_MAX_R || P.n < 1)
             throw invalid_error("grouped KDE evaluation: bad pool");
         for (int u = 0; u < P.nunits; ++u) {
             const GUnit& U = b.units[P.unit0 + u];

@@ -324,7 +324,8 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(PackArgs a) {
         double z = 0.0;
         if (valid && i < dm) {
             const double* w = (a.Wdev ? a.Wdev : a.W) + (size_t)i * d;
-            for (int j = 0; j <= i; ++j) z = __builtin_fma(w[j], xc[j], z);
+            const int jn = a.wfull ? d : i + 1;   // a rotated whitening matrix (KdeModel::wfull) is full
+            for (int j = 0; j < jn; ++j) z = __builtin_fma(w[j], xc[j], z);
         }
         const T zt = (T)z;
         // the norm is taken from the ROUNDED coordinate so that s2(t,t) == 0 up to one rounding
@@ -420,7 +421,8 @@ __global__ __launch_bounds__(256) void max_norm2_kernel(PackArgs a, unsigned lon
         for (int i = 0; i < d; ++i) {
             double z = 0.0;
             const double* w = (a.Wdev ? a.Wdev : a.W) + (size_t)i * d;
-            for (int j = 0; j <= i; ++j) z = __builtin_fma(w[j], xc[j], z);
+            const int jn = a.wfull ? d : i + 1;
+            for (int j = 0; j < jn; ++j) z = __builtin_fma(w[j], xc[j], z);
             nrm = __builtin_fma(z, z, nrm);
         }
         if (!(nrm == nrm)) nrm = INFINITY;   // a NaN row: as far out as it gets
@@ -458,7 +460,8 @@ __global__ __launch_bounds__(256) void prune_keys_kernel(PackArgs a, int zd, int
     for (int i = 0; i < zd; ++i) {
         double z = 0.0;
         const double* w = (a.Wdev ? a.Wdev : a.W) + (size_t)i * d;
-        for (int j = 0; j <= i; ++j) z = __builtin_fma(w[j], xc[j], z);
+        const int jn = a.wfull ? d : i + 1;
+        for (int j = 0; j < jn; ++j) z = __builtin_fma(w[j], xc[j], z);
         z = (double)(T)z;   // the rounding the pack applies
         zrow[r * zd + i] = z;
         if (i < kd) {
@@ -656,16 +659,16 @@ __device__ __forceinline__ void xcd_block(int& qx, int& split) {
 // tiles.  The sweeps then walk the set bits only: a skipped tile costs 1/64 of a test and no fragment load (the first
 // version tested tile by tile on wave-uniform values - 15 DP instructions and three loads per tile, skipped or not:
 // a fifth of a kept tile's cost in the fp32 sweep and ALL of a skipped tile's).
-template <typename BP>
+template <int PD, typename BP>
 __device__ __forceinline__ unsigned long long prune_visit_mask(BP tile_box, int pd, int64_t tb, int64_t t1,
-                                                               const double (&wlo)[PBN_PRUNE_PD], const double (&whi)[PBN_PRUNE_PD], double wthr, int lane) {
+                                                               const double (&wlo)[PD], const double (&whi)[PD], double wthr, int lane) {
     const int64_t t = tb + lane;
     bool keep = false;
     if (t < t1) {
         const BP bx = tile_box + t * 2 * pd;
         double d2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k)
+        for (int k = 0; k < PD; ++k)
             if (k < pd) {
                 const double g1 = bx[k] - whi[k], g2 = wlo[k] - bx[pd + k];
                 double g = g1 > g2 ? g1 : g2;
@@ -681,7 +684,7 @@ __device__ __forceinline__ unsigned long long prune_visit_mask(BP tile_box, int 
 // order, and the box of all of them is up to twice as wide per axis as a group's own - at 3-4 dimensions, where a wave's box is
 // as wide as the kernel's support, a third of the (tile, group) pairs of a visited tile lie beyond the group's own support.  The
 // boxes are re-read per group (uniform addresses: scalar loads; the tile's box from L1) so that no box stays in registers.
-template <typename BP>
+template <int PD, typename BP>
 __device__ __forceinline__ unsigned long long prune_group_mask(BP tile_box, BP qbox, int pd, int64_t tb, int64_t t1, double thr, int lane) {
     const int64_t t = tb + lane;
     bool keep = false;
@@ -689,7 +692,7 @@ __device__ __forceinline__ unsigned long long prune_group_mask(BP tile_box, BP q
         const BP bx = tile_box + t * 2 * pd;
         double d2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k)
+        for (int k = 0; k < PD; ++k)
             if (k < pd) {
                 const double g1 = bx[k] - qbox[pd + k], g2 = qbox[k] - bx[pd + k];
                 double g = g1 > g2 ? g1 : g2;
@@ -703,7 +706,7 @@ __device__ __forceinline__ unsigned long long prune_group_mask(BP tile_box, BP q
 
 // ... with a second, nearer threshold: `near` = the tiles that hold a term above thr_near (the others of the returned mask are the
 // far tiles of the fp32 tail path)
-template <typename BP>
+template <int PD, typename BP>
 __device__ __forceinline__ unsigned long long prune_group_mask2(BP tile_box, BP qbox, int pd, int64_t tb, int64_t t1, double thr, double thr_near, int lane,
                                                                 unsigned long long& near) {
     const int64_t t = tb + lane;
@@ -712,7 +715,7 @@ __device__ __forceinline__ unsigned long long prune_group_mask2(BP tile_box, BP 
         const BP bx = tile_box + t * 2 * pd;
         double d2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k)
+        for (int k = 0; k < PD; ++k)
             if (k < pd) {
                 const double g1 = bx[k] - qbox[pd + k], g2 = qbox[k] - bx[pd + k];
                 double g = g1 > g2 ? g1 : g2;
@@ -727,11 +730,11 @@ __device__ __forceinline__ unsigned long long prune_group_mask2(BP tile_box, BP 
 }
 
 // One uniform test per (64-tile batch, query group): does the batch's box come within the drop threshold of the group's box at all?
-template <typename BP>
+template <int PD, typename BP>
 __device__ __forceinline__ bool batch_in_reach(BP bb, BP qbox, int pd, double thr) {
     double d2 = 0.0;
 #pragma unroll
-    for (int k = 0; k < PBN_PRUNE_PD; ++k)
+    for (int k = 0; k < PD; ++k)
         if (k < pd) {
             const double g1 = bb[k] - qbox[pd + k], g2 = qbox[k] - bb[pd + k];
             double g = g1 > g2 ? g1 : g2;
@@ -745,11 +748,11 @@ __device__ __forceinline__ bool batch_in_reach(BP bb, BP qbox, int pd, double th
 // PBN_OPEN_FAR2?  With boxes over all whitened dimensions every exponent of the batch's rows against the group's queries then lies at most
 // PBN_OPEN_FAR2 / 2 below the offset, and exp2_magic needs no clamp for the batch (false for a box with a NaN or infinite side).
 #define PBN_OPEN_FAR2 2200.0
-template <typename BP>
+template <int PD, typename BP>
 __device__ __forceinline__ bool batch_all_near(BP bb, BP qbox, int pd) {
     double f2 = 0.0;
 #pragma unroll
-    for (int k = 0; k < PBN_PRUNE_PD; ++k)
+    for (int k = 0; k < PD; ++k)
         if (k < pd) {
             const double h1 = bb[pd + k] - qbox[k], h2 = qbox[pd + k] - bb[k];
             const double h = h1 > h2 ? h1 : h2;
@@ -772,7 +775,7 @@ __device__ __forceinline__ bool batch_all_near(BP bb, BP qbox, int pd) {
 #ifndef PBN_MOM_EXTRA
 #define PBN_MOM_EXTRA 2.0
 #endif
-template <typename BP, typename RP>
+template <int PD, typename BP, typename RP>
 __device__ __forceinline__ unsigned long long prune_group_mask3(BP tile_box, BP qbox, RP rad2, int pd, int64_t tb, int64_t t1, double thr, double thr_near,
                                                                 double thr_mom, int lane, unsigned long long& near, unsigned long long& mom) {
 #pragma clang fp contract(off)   // both kernels must take bit-identical decisions: no fused multiply-adds the inliner could place differently
@@ -782,7 +785,7 @@ __device__ __forceinline__ unsigned long long prune_group_mask3(BP tile_box, BP 
         const BP bx = tile_box + t * 2 * pd;
         double d2 = 0.0, f2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k)
+        for (int k = 0; k < PD; ++k)
             if (k < pd) {
                 const double g1 = bx[k] - qbox[pd + k], g2 = qbox[k] - bx[pd + k];
                 double g = g1 > g2 ? g1 : g2;
@@ -834,7 +837,7 @@ __device__ __forceinline__ void pruned_block(const SweepArgs& a, int groups_per_
 // MOM (round 5): the moment pass runs beside this sweep (grouped fp64 sum-only launches of one- and two-variable units) - the sweep skips the
 // pairs the pass takes (prune_group_mask3).  A template parameter, not a run-time branch:
 // the kernel sits at its register limit and the extra paths cost the plain sweep 25 % when compiled in.
-template <typename T, int KS, bool COND, int QG, bool FOLD, bool PRUNE, bool WMUL, bool EF32 = false, bool MOM = false>
+template <typename T, int KS, bool COND, int QG, bool FOLD, bool PRUNE, bool WMUL, bool EF32 = false, bool MOM = false, int PDMAX = PBN_PRUNE_PD>
 __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigned bid) {
     static_assert(!WMUL || (!FOLD && !COND), "WMUL: plain sweeps without a free K slot only");
     using V = typename Tr<T>::vec4;
@@ -891,19 +894,21 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
     const T ctop = Tr<T>::top();   // leading exp2 coefficient pinned in a VGPR for the whole kernel
 
     // ---- tile pruning: box of this wave's queries and the exponent below which a training tile cannot matter -------
-    double wlo[PBN_PRUNE_PD] = {}, whi[PBN_PRUNE_PD] = {}, wthr = 0;
+    // boxes of up to 8 dimensions in the plain fp64 shapes (d = 7, 8: kde_prune_rotates), of up to 5 in the conditional and grouped ones (their spills)
+    constexpr int PDW = COND ? PBN_PRUNE_PD_NARROW : PDMAX;
+    double wlo[PDW] = {}, whi[PDW] = {}, wthr = 0;
     const int pd = PRUNE ? a.pdims : 0;
     if (PRUNE) {
         wthr = INFINITY;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k) { wlo[k] = INFINITY; whi[k] = -INFINITY; }
+        for (int k = 0; k < PDW; ++k) { wlo[k] = INFINITY; whi[k] = -INFINITY; }
 #pragma unroll
         for (int g = 0; g < QG; ++g) {
             const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
             const double th = QTp[qt];
             wthr = th < wthr ? th : wthr;
 #pragma unroll
-            for (int k = 0; k < PBN_PRUNE_PD; ++k)
+            for (int k = 0; k < PDW; ++k)
                 if (k < pd) {
                     const double l = QBp[qt * 2 * pd + k], h = QBp[qt * 2 * pd + pd + k];
                     wlo[k] = l < wlo[k] ? l : wlo[k];
@@ -1150,18 +1155,18 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                         if constexpr (FARP) {
                             if constexpr (MOM) {   // the moment pass takes the pairs it can expand: this sweep skips them
                                 unsigned long long mx;
-                                gm[g] = prune_group_mask3(TBp, QBp + qt * 2 * pd, (const PBN_GLOBAL float*)a.tile_rad2, pd, tb, t1, QTp[qt] - a.prune_margin,
+                                gm[g] = prune_group_mask3<PDW>(TBp, QBp + qt * 2 * pd, (const PBN_GLOBAL float*)a.tile_rad2, pd, tb, t1, QTp[qt] - a.prune_margin,
                                                                   a.far_span > 0.0 ? QTp[qt] - (a.prune_margin - a.far_span) : -INFINITY,
                                                                   QTp[qt] - (a.prune_margin + PBN_MOM_EXTRA), lane, gn[g], mx);
                                 gm[g] &= ~mx;
                             } else if (a.far_span > 0.0) {
-                                gm[g] = prune_group_mask2(TBp, QBp + qt * 2 * pd, pd, tb, t1, QTp[qt] - a.prune_margin, QTp[qt] - (a.prune_margin - a.far_span), lane, gn[g]);
+                                gm[g] = prune_group_mask2<PDW>(TBp, QBp + qt * 2 * pd, pd, tb, t1, QTp[qt] - a.prune_margin, QTp[qt] - (a.prune_margin - a.far_span), lane, gn[g]);
                             } else {
-                                gm[g] = prune_group_mask(TBp, QBp + qt * 2 * pd, pd, tb, t1, QTp[qt] - a.prune_margin, lane);
+                                gm[g] = prune_group_mask<PDW>(TBp, QBp + qt * 2 * pd, pd, tb, t1, QTp[qt] - a.prune_margin, lane);
                                 gn[g] = ~0ull;
                             }
                         } else {
-                            gm[g] = prune_group_mask(TBp, QBp + qt * 2 * pd, pd, tb, t1, QTp[qt] - a.prune_margin, lane);
+                            gm[g] = prune_group_mask<PDW>(TBp, QBp + qt * 2 * pd, pd, tb, t1, QTp[qt] - a.prune_margin, lane);
                         }
                         mask |= gm[g];
                     }
@@ -1225,11 +1230,11 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
 #pragma unroll
                     for (int g = 0; g < QG; ++g) {
                         const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
-                        bmg[g] = __ballot(bt < t1 && batch_in_reach(bb, QBp + qt * 2 * pd, pd, QTp[qt] - a.prune_margin));
+                        bmg[g] = __ballot(bt < t1 && batch_in_reach<PDW>(bb, QBp + qt * 2 * pd, pd, QTp[qt] - a.prune_margin));
                         bm |= bmg[g];
                         // open for the wave = proven for every group that reaches the batch (the batch with the table's last tile - padding
                         // rows, whose norm slot is not a distance - never)
-                        if constexpr (GUARDP) bopen &= ~bmg[g] | (gate_of(g) ? __ballot(bt + 64 < a.ntiles && batch_all_near(bb, QBp + qt * 2 * pd, pd)) : 0ull);
+                        if constexpr (GUARDP) bopen &= ~bmg[g] | (gate_of(g) ? __ballot(bt + 64 < a.ntiles && batch_all_near<PDW>(bb, QBp + qt * 2 * pd, pd)) : 0ull);
                     }
                 }
             }
@@ -1414,7 +1419,7 @@ __global__ __launch_bounds__(sweep_block_threads(true), PBN_F64_GROUP_WAVES) voi
     a.nsplit_grid = su.nsplit; a.part = su.part; a.group_masks = g.group_masks;
     a.far_span = g.far_span;
     a.tile_rad2 = su.tile_rad2; a.tile_mom = su.tile_mom; a.batch_box = su.batch_box; a.batches_per_split = su.nbps;
-    kde_sweep_body<T, KS, false, QG, FOLD, true, WMUL, /*EF32: the engine's terms are sums*/ true, MOM>(a, bid);
+    kde_sweep_body<T, KS, false, QG, FOLD, true, WMUL, /*EF32: the engine's terms are sums*/ true, MOM, PBN_PRUNE_PD_NARROW>(a, bid);
 }
 
 // The moment pass of a grouped fp64 sum-only sweep of D = 1 or 2 dimensions (round 5).  Same flat grid and the same (unit, query block,
@@ -1513,7 +1518,7 @@ __global__ __launch_bounds__(64, D == 2 ? PBN_MOM_WAVES2 : 3) void kde_moment_gr
         for (int gi = 0; gi < QG; ++gi) {
             if (su.batch_box) {
                 const PBN_GLOBAL double* bb = (const PBN_GLOBAL double*)su.batch_box + ((int64_t)split * su.nbps + ((bt - t0) >> 6)) * 2 * pd;
-                bm[gi] = __ballot(gok[gi] && bt < t1 && batch_in_reach(bb, QBp + (qt0 + (gok[gi] ? gi : 0)) * 2 * pd, pd, thr[gi] - margin));
+                bm[gi] = __ballot(gok[gi] && bt < t1 && batch_in_reach<PBN_PRUNE_PD_NARROW>(bb, QBp + (qt0 + (gok[gi] ? gi : 0)) * 2 * pd, pd, thr[gi] - margin));
             } else {
                 bm[gi] = __ballot(gok[gi] && bt < t1);
             }
@@ -1530,7 +1535,7 @@ __global__ __launch_bounds__(64, D == 2 ? PBN_MOM_WAVES2 : 3) void kde_moment_gr
                 if ((bm[gi] >> bj) & 1ull) {
                     unsigned long long nr;
                     if (g.count_redo && lane == 0) atomicAdd(&g_mom_visits, 1ull);
-                    const unsigned long long kept = prune_group_mask3(TBp, QBp + (qt0 + gi) * 2 * pd, R2p, pd, tb, t1, thr[gi] - margin,
+                    const unsigned long long kept = prune_group_mask3<PBN_PRUNE_PD_NARROW>(TBp, QBp + (qt0 + gi) * 2 * pd, R2p, pd, tb, t1, thr[gi] - margin,
                                                                       g.far_span > 0.0 ? thr[gi] - (margin - g.far_span) : -INFINITY,
                                                                       thr[gi] - (margin + PBN_MOM_EXTRA), lane, nr, m[gi]);
                     if (g.count_redo && lane == 0 && (kept & ~m[gi])) atomicAdd(&g_mom_left, 1ull);
@@ -1882,19 +1887,19 @@ __device__ __forceinline__ void kde_sweep_f16_body(const SweepArgs& a, const uns
         if (COND) { bx[g] = BXp[qt * 64 + lane]; xn[g] = XNp[qt * 16 + (lane & 15)]; sumj[g] = 0.0; }
     }
     // tile pruning, as in kde_sweep_kernel
-    double wlo[PBN_PRUNE_PD] = {}, whi[PBN_PRUNE_PD] = {}, wthr = 0;
+    double wlo[PBN_PRUNE_PD_NARROW] = {}, whi[PBN_PRUNE_PD_NARROW] = {}, wthr = 0;
     const int pd = PRUNE ? a.pdims : 0;
     if (PRUNE) {
         wthr = INFINITY;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k) { wlo[k] = INFINITY; whi[k] = -INFINITY; }
+        for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k) { wlo[k] = INFINITY; whi[k] = -INFINITY; }
 #pragma unroll
         for (int g = 0; g < QG; ++g) {
             const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
             const double th = QTp[qt];
             wthr = th < wthr ? th : wthr;
 #pragma unroll
-            for (int k = 0; k < PBN_PRUNE_PD; ++k)
+            for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k)
                 if (k < pd) {
                     const double l = QBp[qt * 2 * pd + k], h = QBp[qt * 2 * pd + pd + k];
                     wlo[k] = l < wlo[k] ? l : wlo[k];
@@ -2560,17 +2565,17 @@ __device__ __forceinline__ void kde_sweep_f16_w32p_body(const SweepArgs& a, cons
         lbm[s] = false;
     }
     // the wave's query box and threshold (as kde_sweep_f16_body)
-    double wlo[PBN_PRUNE_PD], whi[PBN_PRUNE_PD], wthr = INFINITY;
+    double wlo[PBN_PRUNE_PD_NARROW], whi[PBN_PRUNE_PD_NARROW], wthr = INFINITY;
     const int pd = a.pdims;
 #pragma unroll
-    for (int k = 0; k < PBN_PRUNE_PD; ++k) { wlo[k] = INFINITY; whi[k] = -INFINITY; }
+    for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k) { wlo[k] = INFINITY; whi[k] = -INFINITY; }
 #pragma unroll
     for (int g = 0; g < QG; ++g) {
         const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
         const double th = QTp[qt];
         wthr = th < wthr ? th : wthr;
 #pragma unroll
-        for (int k = 0; k < PBN_PRUNE_PD; ++k)
+        for (int k = 0; k < PBN_PRUNE_PD_NARROW; ++k)
             if (k < pd) {
                 const double l = QBp[qt * 2 * pd + k], h = QBp[qt * 2 * pd + pd + k];
                 wlo[k] = l < wlo[k] ? l : wlo[k];

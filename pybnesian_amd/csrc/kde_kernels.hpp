@@ -9,7 +9,8 @@
 #define PBN_MAX_D 33       // up to 32 whitened "main" dimensions (fp64: KS <= 8; fp32: 16) + 1 CKDE extra coordinate
 #define PBN_W_INLINE_D 17  // whitening matrices up to this order travel inside the kernel arguments, larger ones through device memory
 
-#define PBN_PRUNE_PD 5     // most whitened dimensions the Morton keys and the boxes of the pruned sweeps cover (KdeModel::pdims <= this)
+#define PBN_PRUNE_PD 8     // most whitened dimensions the boxes of the pruned sweeps cover (KdeModel::pdims <= this; the keys: at most 4)
+#define PBN_PRUNE_PD_NARROW 5   // ... in the kernels that never see more than 5 (fp32, conditional and grouped sweeps): their box registers
 
 namespace pbn {
 
@@ -51,6 +52,7 @@ struct PackArgs {
     int64_t ntiles;       // ceil(n / 16)
     double W[PBN_W_INLINE_D * PBN_W_INLINE_D];  // d x d row-major lower-triangular whitening matrix (kernel argument), d <= PBN_W_INLINE_D
     const double* Wdev;               // the same matrix in device memory when d > PBN_W_INLINE_D (else null)
+    int wfull;                        // W is full, not lower-triangular (rotated to the principal axes: KdeModel::wfull)
     double mu[PBN_MAX_D];             // d centring offsets
     void* pack;           // [ntiles][KS][64]
     void* npack;          // [ntiles][16]

@@ -157,11 +157,13 @@ static void fill_pack_common(pbn_ctx* ctx, PackArgs& pa, const pbn_table* t, con
     for (int i = 0; i < m.d; ++i) pa.cols[i] = cols[m.perm[i]];
     pa.rows = nullptr;
     pa.Wdev = nullptr;
+    const std::vector<double>& W = m.wfull ? m.Wrot : m.W;
+    pa.wfull = m.wfull ? 1 : 0;
     if (m.d <= PBN_W_INLINE_D) {
-        for (int i = 0; i < m.d * m.d; ++i) pa.W[i] = m.W[i];
+        for (int i = 0; i < m.d * m.d; ++i) pa.W[i] = W[i];
     } else {   // too large for the kernel arguments: through the context's (lane's) scratch, in stream order behind its last reader
         ctx->scratch_w.reserve((size_t)PBN_MAX_D * PBN_MAX_D);
-        HIP_CHECK(hipMemcpyAsync(ctx->scratch_w.p, m.W.data(), (size_t)m.d * m.d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(ctx->scratch_w.p, W.data(), (size_t)m.d * m.d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         pa.Wdev = ctx->scratch_w.p;
     }
     for (int i = 0; i < m.d; ++i) pa.mu[i] = m.mu[i];
@@ -234,6 +236,100 @@ bool kde_prune_applies(int dtype, int dm, int64_t n) {
     return knob_int("PBN_SWEEP_PRUNE", 1) && (dtype == PBN_F64 || use_f16x2(dtype)) && dm <= max_dims && n >= knob_int("PBN_PRUNE_MIN_ROWS", 32768);
 }
 
+// d = 7 and 8 (fp64 tables, plain models): the boxes cover ALL whitened dimensions, rotated to the principal axes of the training rows first,
+// and the rows are sorted on the widest four of them (principal_rotation).  Boxes over 4 raw axes lost 10 % at d = 8 (tools/prune_dims67.py);
+// with the rotation C2's sum-only sweep visits 0.525 of its (tile, group) blocks, 40.7 -> 27.2 ms (tools/prune_d8_estimate.py, profiles/r7/).  Per-row logl
+// sweeps of these models stay unpruned (kde_eval_enqueue).  PBN_SWEEP_PRUNE=0 turns it off with the rest.
+bool kde_prune_rotates(const KdeModel& m) {
+    return PBN_TUNE(PRUNE_ROTATE, 1) && knob_int("PBN_SWEEP_PRUNE", 1) && m.dtype == PBN_F64 && !m.widen && !m.cond && !m.wide &&
+           (m.dm == 7 || m.dm == 8) && m.N >= knob_int("PBN_PRUNE_MIN_ROWS", 32768);
+}
+
+// Eigenvectors of a symmetric n x n matrix (column-major) by cyclic Jacobi rotations: a becomes diagonal, V (column-major) holds the vectors
+static void sym_eigen(std::vector<double>& a, int n, std::vector<double>& V) {
+    V.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i) V[i + (size_t)i * n] = 1.0;
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) (i == j ? diag : off) += a[i + (size_t)j * n] * a[i + (size_t)j * n];
+        if (off <= 1e-30 * (diag > 0 ? diag : 1.0)) break;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = a[p + (size_t)q * n];
+                if (apq == 0.0) continue;
+                const double theta = (a[q + (size_t)q * n] - a[p + (size_t)p * n]) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; ++k) {
+                    const double akp = a[k + (size_t)p * n], akq = a[k + (size_t)q * n];
+                    a[k + (size_t)p * n] = c * akp - s * akq;
+                    a[k + (size_t)q * n] = s * akp + c * akq;
+                }
+                for (int k = 0; k < n; ++k) {
+                    const double apk = a[p + (size_t)k * n], aqk = a[q + (size_t)k * n];
+                    a[p + (size_t)k * n] = c * apk - s * aqk;
+                    a[q + (size_t)k * n] = s * apk + c * aqk;
+                }
+                for (int k = 0; k < n; ++k) {
+                    const double vkp = V[k + (size_t)p * n], vkq = V[k + (size_t)q * n];
+                    V[k + (size_t)p * n] = c * vkp - s * vkq;
+                    V[k + (size_t)q * n] = s * vkp + c * vkq;
+                }
+            }
+    }
+}
+
+// Rotation of the whitened training rows to their principal axes, widest first: Wrot = R W with R's rows the eigenvectors of the rows'
+// covariance (O(d^3) on the host, from one copy of the whitened rows).  Orthonormal: every distance, norm and term is the same in exact
+// arithmetic - only the fp64 rounding of the packed coordinates moves.  Rows with a NaN or an infinity are left out of the covariance.
+static void principal_rotation(pbn_ctx* ctx, KdeModel& m, const PackArgs& pa) {
+    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const int d = m.d;
+    const size_t n = (size_t)pa.n, zb = al(n * d * sizeof(double)), kb = al(n * sizeof(uint32_t));
+    ctx->scratch_prune.reserve(zb + 2 * kb);
+    double* z = (double*)ctx->scratch_prune.p;
+    launch_prune_keys(pa, m.fdtype(), d, 1, z, (uint32_t*)(ctx->scratch_prune.p + zb), (int32_t*)(ctx->scratch_prune.p + zb + kb), ctx->stream);
+    std::vector<double> h(n * d);
+    HIP_CHECK(hipMemcpyAsync(h.data(), z, n * d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<double> mean(d, 0.0), cov((size_t)d * d, 0.0);
+    size_t cnt = 0;
+    for (size_t r = 0; r < n; ++r) {
+        const double* zr = h.data() + r * d;
+        bool ok = true;
+        for (int i = 0; i < d; ++i) ok = ok && std::isfinite(zr[i]);
+        if (!ok) continue;
+        ++cnt;
+        for (int i = 0; i < d; ++i) mean[i] += zr[i];
+    }
+    m.Wrot = m.W;
+    m.wfull = true;
+    if (cnt < 2) return;
+    for (int i = 0; i < d; ++i) mean[i] /= (double)cnt;
+    for (size_t r = 0; r < n; ++r) {
+        const double* zr = h.data() + r * d;
+        bool ok = true;
+        for (int i = 0; i < d; ++i) ok = ok && std::isfinite(zr[i]);
+        if (!ok) continue;
+        for (int j = 0; j < d; ++j)
+            for (int i = j; i < d; ++i) cov[i + (size_t)j * d] += (zr[i] - mean[i]) * (zr[j] - mean[j]);
+    }
+    for (int j = 0; j < d; ++j)
+        for (int i = j; i < d; ++i) cov[j + (size_t)i * d] = cov[i + (size_t)j * d];
+    std::vector<double> V;
+    sym_eigen(cov, d, V);
+    std::vector<int> ord(d);
+    for (int i = 0; i < d; ++i) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return cov[x + (size_t)x * d] > cov[y + (size_t)y * d]; });
+    for (int i = 0; i < d; ++i)        // row i of R = eigenvector ord[i]
+        for (int j = 0; j < d; ++j) {
+            double w = 0.0;
+            for (int k = 0; k < d; ++k) w += V[k + (size_t)ord[i] * d] * m.W[(size_t)k * d + j];
+            m.Wrot[(size_t)i * d + j] = w;
+        }
+}
+
 // bytes of the subsample packs (kde_pack_bytes of nsub rows, each part 256-aligned)
 struct SubBytes { size_t a, n, x, total; };
 static SubBytes sub_bytes(const KdeModel& m, int64_t nsub) {
@@ -282,23 +378,33 @@ void kde_pack_train(pbn_ctx* ctx, KdeModel& m, const pbn_table* t, const int* co
         return;
     }
     PackArgs pa{};
+    m.wfull = false;   // (set again below for a rotated model: the rotation is the training rows')
     fill_pack_common(ctx, pa, t, cols, m);
     pa.rows = dev_rows;
     pa.row0 = row0; pa.n0 = n0; pa.row1 = row1; pa.n = m.N; pa.ntiles = m.ntiles;
     pa.is_query = 0;
     if (dev_max_norm2 && m.dtype == PBN_F32 && !m.widen) launch_max_norm2(pa, t->dtype, dev_max_norm2, ctx->stream);
     m.prune = false;
-    if (prune && kde_prune_applies(m.fdtype(), m.dm, m.N)) {
+    const bool rot = prune && kde_prune_rotates(m);
+    if (rot || (prune && kde_prune_applies(m.fdtype(), m.dm, m.N))) {
         auto al = [](size_t x) { return (x + 255) / 256 * 256; };
         m.zdims = m.d;
         m.pdims = std::min(m.dm, std::min(PBN_TUNE(PRUNE_BOX_DIMS, 4), PBN_PRUNE_PD));   // dimensions of the Morton keys and the boxes (<= PBN_PRUNE_PD)
+        m.kdims = m.pdims;
+        if (rot) {   // boxes over all (rotated) dimensions, keys on the widest four
+            principal_rotation(ctx, m, pa);
+            for (int i = 0; i < m.d * m.d; ++i) pa.W[i] = m.Wrot[i];
+            pa.wfull = 1;
+            m.pdims = m.dm;
+            m.kdims = 4;
+        }
         const size_t box_b = al((size_t)m.ntiles * 2 * m.pdims * sizeof(double)), zs_b = al((size_t)m.N * m.zdims * sizeof(double));
         // more dimensions than the keys cover: a stratified subsample (every N / nsub-th row of the sorted order, <= 4096
         // rows, <= 1/64 of the set) is packed as well; the queries are swept against it first (kde_eval_enqueue)
         m.nsub = 0;
         if (m.d > m.pdims && PBN_TUNE(PRUNE_SUBSAMPLE, 1)) m.nsub = std::min<int64_t>(4096, m.N / 64) / 16 * 16;
         const SubBytes sb = sub_bytes(m, m.nsub);
-        const PruneSide s = prune_sort_side(ctx, ctx->scratch_prune, pa, m.fdtype(), m.zdims, m.pdims, box_b + zs_b + (m.nsub ? sb.total : 0));
+        const PruneSide s = prune_sort_side(ctx, ctx->scratch_prune, pa, m.fdtype(), m.zdims, m.kdims, box_b + zs_b + (m.nsub ? sb.total : 0));
         double* box = (double*)s.rest;
         double* zsorted = (double*)(s.rest + box_b);
         launch_tile_boxes(s.zrow, s.perm, m.N, m.zdims, m.pdims, box, zsorted, ctx->stream);
@@ -419,11 +525,13 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     const double* qlb = nullptr;
     const int32_t* qperm = nullptr;
     PruneSide qs{};
-    if (m.prune) {
+    // a rotated (d = 7, 8) model prunes its sum-only sweeps only; per-row logl outputs take the plain sweep over the same (sorted) pack
+    const bool prune = m.prune && (sum_only || !m.wfull);
+    if (prune) {
         auto al = [](size_t x) { return (x + 255) / 256 * 256; };
         const size_t qbox_b = al((size_t)nqtiles * 2 * m.pdims * sizeof(double)), qthr_b = al((size_t)nqtiles * sizeof(double));
         const size_t qlb_b = al((size_t)nqtiles * 16 * sizeof(double));
-        qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.pdims, qbox_b + qthr_b + qlb_b);
+        qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.kdims, qbox_b + qthr_b + qlb_b);
         pa.perm = qs.perm;
         qperm = qs.perm;
         qbox = (double*)qs.rest; qthr = (double*)(qs.rest + qbox_b);
@@ -436,7 +544,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     { KernelTimer kt(ctx, PBN_K_PACK); launch_pack(pa, fdt, ctx->stream); }
     const int P = m.cond ? 4 : 2;
     const bool wmul = !fold && sweep_weights_norm(fdt, m.cond, m.KS, m.dm);
-    if (m.prune) {
+    if (prune) {
         // bounds of the queries' largest exponents: neighbours in Morton order, and (more dimensions than keys) one sweep over
         // the subsample of the training rows; then per query tile the smallest bound and the box
         const double* subpart = nullptr;
@@ -456,7 +564,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     }
 
     // split the training tiles so that the grid is a few waves deep on every CU
-    const int64_t qblocks = ceil_div(nqtiles, 4 * sweep_qg(fdt, m.cond, m.KS, m.prune));
+    const int64_t qblocks = ceil_div(nqtiles, 4 * sweep_qg(fdt, m.cond, m.KS, prune));
     const int64_t target = (int64_t)ctx->num_cus * PBN_TUNE(SWEEP_BLOCKS_PER_CU, 24);
     int64_t nsplit = std::max<int64_t>(1, ceil_div(target, qblocks));
     // with the XCD-aware block order (xcd_block) the blocks resident on one XCD share a split: keep a split's training
@@ -467,7 +575,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     // pruned sweeps: a workgroup of the queries' own neighbourhood visits most tiles of its split, and those long workgroups are
     // the sweep's tail - at most PBN_PRUNE_MAX_TILES tiles per split (1e6 x 1e5 handles: fp64 -5...9 %, fp32 -7 %; the score
     // engine's slices are below that anyway - splitting THEM four times finer costs C5 12 %)
-    if (m.prune) nsplit = std::max<int64_t>(nsplit, ceil_div(m.ntiles, (int64_t)PBN_TUNE(PRUNE_MAX_TILES, 1024)));
+    if (prune) nsplit = std::max<int64_t>(nsplit, ceil_div(m.ntiles, (int64_t)PBN_TUNE(PRUNE_MAX_TILES, 1024)));
     if (nsplit > 1) nsplit = ceil_div(nsplit, 8) * 8;
     nsplit = std::min<int64_t>(nsplit, std::max<int64_t>(1, m.ntiles / PBN_TUNE(SWEEP_MIN_TILES, 64)));
     nsplit = std::min<int64_t>(nsplit, 4096);
@@ -476,7 +584,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     // pruned fp64 plain sweeps with per-group masks walk their tiles in two levels (kde_sweep_body): the boxes of the 64-tile batches of every split,
     // behind the partials (they depend on the split size, which depends on the number of queries)
     static const int gmasks = PBN_TUNE(PRUNE_GROUP_MASKS, 1);
-    const bool bboxes = m.prune && gmasks && !m.cond && fdt == PBN_F64 && PBN_TUNE(GROUP_BATCH_BOXES, 1) != 0;
+    const bool bboxes = prune && gmasks && !m.cond && fdt == PBN_F64 && PBN_TUNE(GROUP_BATCH_BOXES, 1) != 0;
     const size_t part_b = ((size_t)nsplit * nqtiles * 16 * P * sizeof(double) + 255) / 256 * 256;
     const size_t bbox_b = bboxes ? (size_t)nsplit * ceil_div(tps, 64) * 2 * m.pdims * sizeof(double) : 0;
     ctx->scratch_part.reserve(part_b + bbox_b);
@@ -486,14 +594,14 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     sa.ntiles = m.ntiles; sa.nqtiles = nqtiles; sa.tiles_per_split = tps;
     sa.fold = fold ? 1 : 0;
     sa.wmul = wmul ? 1 : 0;
-    sa.w32 = (b3 && !m.cond && (m.prune ? f16x2_w32p(m.dm, m.KS) : f16x2_w32(m.dm, m.KS))) ? 1 : 0;
-    sa.far_span = (sum_only && m.prune) ? (double)knob_int("PBN_FAR_SPAN", 17) : 0.0;   // sum-only pruned sweeps: fp32 tail for tiles 26+ bits below the sum bound
+    sa.w32 = (b3 && !m.cond && (prune ? f16x2_w32p(m.dm, m.KS) : f16x2_w32(m.dm, m.KS))) ? 1 : 0;
+    sa.far_span = (sum_only && prune) ? (double)knob_int("PBN_FAR_SPAN", 17) : 0.0;   // sum-only pruned sweeps: fp32 tail for tiles 26+ bits below the sum bound
     const bool guard = knob_int("PBN_MAGIC_GUARD", 1) != 0;   // 0: exp2_magic keeps its clamp everywhere (the same bits, slower: tests/test_magic_exp2_gpu.py)
-    sa.tile_r = (guard && m.tile_r && !m.prune && sum_only) ? (const double*)((const char*)m.nxpack + (size_t)m.ntiles * 16 * es * 2) : nullptr;
+    sa.tile_r = (guard && m.tile_r && !prune && sum_only) ? (const double*)((const char*)m.nxpack + (size_t)m.ntiles * 16 * es * 2) : nullptr;
     sa.fast = sum_only ? 1 : 0;   // only sums leave this call: 2^f on the fp32 transcendental unit; per-row logl keeps the polynomial
     sa.count_redo = knob_int("PBN_SWEEP_COUNT_REDO", 0);
-    sa.box_full = (guard && m.prune && m.pdims == m.dm) ? 1 : 0;
-    sa.prune = m.prune ? 1 : 0; sa.pdims = m.pdims; sa.prune_margin = prune_margin(fdt, m.N, sum_only); sa.tile_box = m.tile_box; sa.qtile_box = qbox; sa.qtile_thr = qthr; sa.qlb = qlb;
+    sa.box_full = (guard && prune && m.pdims == m.dm) ? 1 : 0;
+    sa.prune = prune ? 1 : 0; sa.pdims = m.pdims; sa.prune_margin = prune_margin(fdt, m.N, sum_only); sa.tile_box = m.tile_box; sa.qtile_box = qbox; sa.qtile_thr = qthr; sa.qlb = qlb;
     sa.part = (double*)ctx->scratch_part.p;
     sa.group_masks = gmasks;
     if (bboxes) {
@@ -502,7 +610,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         sa.batch_box = bb; sa.batches_per_split = (int)ceil_div(tps, 64);
     }
     static const bool log_sweeps = PBN_TUNE(SWEEP_LOG, 0) != 0;   // one line per sweep on stderr (tools/c5_sweeps.py)
-    if (log_sweeps) std::fprintf(stderr, "pbn-sweep N=%lld n=%lld d=%d cond=%d prune=%d nsub=%lld nsplit=%lld\n", (long long)m.N, (long long)n, m.d, (int)m.cond, (int)m.prune, (long long)(m.prune ? m.nsub : 0), (long long)nsplit);
+    if (log_sweeps) std::fprintf(stderr, "pbn-sweep N=%lld n=%lld d=%d cond=%d prune=%d nsub=%lld nsplit=%lld\n", (long long)m.N, (long long)n, m.d, (int)m.cond, (int)prune, (long long)(prune ? m.nsub : 0), (long long)nsplit);
     { KernelTimer kt(ctx, PBN_K_SWEEP); launch_sweep(sa, fdt, m.KS, m.cond, (int)nsplit, ctx->stream); }
     // f16x2 fragments: queries beyond the f16 range were clamped by the pack - their partials are recomputed in fp64 (a flag test otherwise)
     if (b3) launch_far_fix(pa, m.Apack, m.Axpack, m.KS, m.N, m.ntiles, sa.part, (int)nsplit, nqtiles, m.cond, ctx->stream);

@@ -38,6 +38,11 @@ struct KdeModel {
     // hold the training rows in Morton order of their whitened coordinates
     bool prune = false;
     int pdims = 0, zdims = 0;
+    int kdims = 0;             // dimensions of the sort keys (<= 4, <= pdims)
+    // d = 7, 8 (kde_prune_rotates): the packs hold the rows rotated to the principal axes of the whitened training rows - Wrot = R W
+    // (full, d x d row-major), the same distances; W itself stays the lower-triangular whitening of the other consumers
+    bool wfull = false;
+    std::vector<double> Wrot;
     const double* tile_box = nullptr;      // [ntiles][2 * pdims]
     const double* zsorted = nullptr;       // [N][zdims] whitened rows in packed order
     const uint32_t* keys_sorted = nullptr; // [N]
@@ -84,6 +89,7 @@ void kde_pack_train(pbn_ctx* ctx, KdeModel& m, const pbn_table* t, const int* co
                     int64_t row1, const int32_t* dev_rows = nullptr, bool prune = false, double* dev_max_norm2 = nullptr);
 // Whether kde_pack_train(prune = true) would build the Morton-ordered pack for a model of `dm` main dimensions and n rows.
 bool kde_prune_applies(int dtype, int dm, int64_t n);
+bool kde_prune_rotates(const KdeModel& m);
 // Copies the pruning tables of a pruned pack out of the context arena into `store` (handles that outlive the call).
 void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store);
 
