@@ -63,7 +63,7 @@ void* pbn_ctx_stream(pbn_ctx* ctx); /* hipStream_t the kernels are launched on (
  * on = 2: events around the sweep and Gram classes only, nothing else changes (launches on the engine's issue lanes are timed on their
  * lane - the classes' totals are device time and may overlap); 0: off.  Switching resets the totals. */
 #define PBN_NUM_KERNEL_CLASSES 8
-typedef enum { PBN_K_PACK = 0, PBN_K_SWEEP = 1, PBN_K_FINISH = 2, PBN_K_GRAM = 3, PBN_K_MOMENT = 4 } pbn_kernel_class;   /* MOMENT: the tile-moment pass beside the grouped fp64 sweeps */
+typedef enum { PBN_K_PACK = 0, PBN_K_SWEEP = 1, PBN_K_FINISH = 2, PBN_K_GRAM = 3, PBN_K_MOMENT = 4, PBN_K_RCOT_PROD = 5 } pbn_kernel_class;   /* MOMENT: the tile-moment pass beside the grouped fp64 sweeps; RCOT_PROD: RCoT's residual-product pass (its feature Gram is GRAM) */
 int pbn_ctx_set_profiling(pbn_ctx* ctx, int on);
 int pbn_ctx_kernel_time(pbn_ctx* ctx, int kernel_class, double* total_ms, int64_t* launches);
 
@@ -469,6 +469,30 @@ int pbn_kmi_create(pbn_ctx* ctx, const double* const* cols, int n_vars, int64_t 
 void pbn_kmi_destroy(pbn_kmi* h);
 int pbn_kmi_value(pbn_kmi* h, int v1, int v2, int n_cond, const int* cond, double* mi);
 double pbn_kmi_pvalue(void* user, int v1, int v2, int n_cond, const int* cond);   /* pbn_ci_pvalue_fn */
+/* ---- RCoT, the randomized conditional correlation test (learning/independences/continuous/RCoT.{hpp,cpp}; util/
+ * chisquaresum.hpp).  cols: n_vars host columns of N values as double, NaN marking a null (a float32 table is promoted
+ * exactly); every column is normalised over its valid values (DataFrame::normalize) and kept on the device.  nxy / nz: random
+ * Fourier features per x / y and for Z; caps 2 nxy + nz <= 255 and nxy^2 <= 64.  A test runs over the rows valid in all its
+ * variables: K1 = Gram of the generated features on the f64 MFMA, a host step, K2 = Gram of the residual products.  W and b
+ * are drawn per test from std::mt19937 seeded by (seed, the unordered pair, the sorted Z set used, the role): a p-value is a
+ * pure function of (seed, test).  pbn_rcot_pvalue / _batch have the pbn_ci_pvalue_fn / pbn_ci_pvalue_batch_fn signatures
+ * (user = the handle; indices mapped through pbn_rcot_set_order when set). */
+typedef struct pbn_rcot pbn_rcot;
+int pbn_rcot_create(pbn_ctx* ctx, const double* const* cols, int n_vars, int64_t N, int nxy, int nz, uint32_t seed, pbn_rcot** out);
+void pbn_rcot_destroy(pbn_rcot* h);
+int pbn_rcot_set_order(pbn_rcot* h, int n, const int* ids);
+double pbn_rcot_pvalue(void* user, int v1, int v2, int n_cond, const int* cond);
+void pbn_rcot_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond,
+                           double* out);
+/* One test in full (a test aid).  The x role is the smaller of v1, v2.  sigma[3]: x, y, Z; W: x (nxy), y (nxy), Z (k x nz,
+ * column by column); b: x, y, Z; z_used: the k Z columns used (sorted, constant ones dropped), n_z_used = k or -1 when the test
+ * needed no device work (x or y constant: p = 1); eig: the positive eigenvalues (ascending), at most nxy^2; method: 0 none,
+ * 1 HBE, 2 LPB4.  Any output pointer may be NULL. */
+int pbn_rcot_detail(pbn_rcot* h, int v1, int v2, int n_cond, const int* cond, int64_t* n_valid, double* sigma, double* W, double* b,
+                    int* z_used, int* n_z_used, double* sta, double* eig, int* n_eig, int* method, double* pvalue);
+/* Survival function at q of sum_i w_i chi2_1 over the positive weights (host only).  method 0: the reference's rule (HBE
+ * below 4 weights, else LPB4 falling back to HBE when it fails), 1: HBE, 2: LPB4 alone (PBN_ERR_INVALID when it fails). */
+int pbn_rcot_chisq_sum_sf(const double* weights, int n, double q, int method, double* out);
 
 /* mmpc_all_variables (learning/algorithms/mmpc.cpp:910-966; forward / backward phases :356-644): candidate
  * parents-and-children of every variable.  Lists are pairs of node indices.  symmetric != 0 applies

@@ -15,7 +15,7 @@ PBN_OK, PBN_ERR_INVALID, PBN_ERR_SINGULAR, PBN_ERR_DEVICE = 0, 1, 2, 3
 PBN_F64, PBN_F32 = 0, 1
 PBN_BW_FULL, PBN_BW_DIAG = 0, 1
 PBN_SEL_NORMAL_REFERENCE, PBN_SEL_SCOTT = 0, 1
-PBN_K_PACK, PBN_K_SWEEP, PBN_K_FINISH, PBN_K_GRAM, PBN_K_MOMENT = 0, 1, 2, 3, 4
+PBN_K_PACK, PBN_K_SWEEP, PBN_K_FINISH, PBN_K_GRAM, PBN_K_MOMENT, PBN_K_RCOT_PROD = 0, 1, 2, 3, 4, 5
 PBN_SPLIT_NONE, PBN_SPLIT_CV, PBN_SPLIT_HOLDOUT, PBN_SPLIT_VALIDATED = 0, 1, 2, 3
 PBN_SCORE_BIC, PBN_SCORE_BGE, PBN_SCORE_CVLIK, PBN_SCORE_HOLDOUT = 0, 1, 2, 3
 PBN_NODE_LG, PBN_NODE_CKDE, PBN_NODE_DISCRETE = 0, 1, 2
@@ -106,6 +106,13 @@ SIGNATURES = {
     "pbn_kmi_destroy": (None, [_vp]),
     "pbn_kmi_value": (_int, [_vp, _int, _int, _int, _ip, _dp]),
     "pbn_kmi_pvalue": (C.c_double, [_vp, _int, _int, _int, _ip]),
+    "pbn_rcot_create": (_int, [_vp, C.POINTER(_vp), _int, _i64, _int, _int, C.c_uint32, C.POINTER(_vp)]),
+    "pbn_rcot_destroy": (None, [_vp]),
+    "pbn_rcot_set_order": (_int, [_vp, _int, _ip]),
+    "pbn_rcot_pvalue": (C.c_double, [_vp, _int, _int, _int, _ip]),
+    "pbn_rcot_pvalue_batch": (None, [_vp, _int, _ip, _ip, _ip, _ip, _dp]),
+    "pbn_rcot_detail": (_int, [_vp, _int, _int, _int, _ip, C.POINTER(_i64), _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _dp]),
+    "pbn_rcot_chisq_sum_sf": (_int, [_dp, _int, C.c_double, _int, _dp]),
     "pbn_mmpc_cpcs": (_int, [_int, _vp, _vp, C.c_double, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _ip, C.POINTER(_i64)]),
     "pbn_mmpc_cpcs_conditional": (_int, [_int, _int, _vp, _vp, C.c_double, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _ip, C.POINTER(_i64)]),
     "pbn_mmpc_cpcs_batched": (_int, [_int, _int, _vp, _vp, _vp, C.c_double, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _ip, C.POINTER(_i64)]),

@@ -184,6 +184,7 @@ DynamicLinearCorrelation = _adaptator(DynamicIndependenceTestAdaptator, "LinearC
 DynamicMutualInformation = _adaptator(DynamicIndependenceTestAdaptator, "MutualInformation")
 DynamicChiSquare = _adaptator(DynamicIndependenceTestAdaptator, "ChiSquare")
 DynamicKMutualInformation = _adaptator(DynamicIndependenceTestAdaptator, "KMutualInformation")
+DynamicRCoT = _adaptator(DynamicIndependenceTestAdaptator, "RCoT")
 
 
 class DynamicBayesianNetworkBase:

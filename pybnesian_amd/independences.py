@@ -308,6 +308,109 @@ class KMutualInformation(IndependenceTest):
             pass
 
 
+class RCoT(IndependenceTest):
+    """pbn.RCoT(df, random_fourier_xy=5, random_fourier_z=100, seed=None): randomized conditional correlation test on random
+    Fourier features (learning/independences/continuous/RCoT.{hpp,cpp}).  Both passes of a test are device kernels over the rows
+    valid in its variables (csrc/rcot.hip).  W and b are drawn per test from the object's seed (seed=None draws one), so a
+    p-value is reproducible and symmetric in x, y and in the order of z - the reference draws afresh from std::random_device."""
+
+    def __init__(self, df, random_fourier_xy=5, random_fourier_z=100, seed=None, ctx=None):
+        import pyarrow as pa
+
+        from .factors import _random_seed
+
+        rb = as_record_batch(df)
+        self._all_names = [f.name for f in rb.schema]
+        cont = [f.name for f in rb.schema if pa.types.is_floating(f.type)]
+        if len(cont) < 2:
+            raise ValueError("DataFrame does not contain enough continuous columns.")
+        types = [rb.schema.field(c).type for c in cont]
+        for i, t in enumerate(types):
+            if t != types[0]:
+                raise ValueError(f"Column 0 [{types[0]}] and column {i} [{t}] have different types.")
+        self._names = cont
+        self._index = {n: i for i, n in enumerate(cont)}
+        self._seed = _random_seed() if seed is None else int(seed)
+        ctx = ctx or default_context()
+        self._ctx = ctx
+        cols = []
+        for c in cont:
+            col = rb.column(rb.schema.get_field_index(c))
+            if isinstance(col, pa.ChunkedArray):
+                col = col.combine_chunks()
+            cols.append(np.ascontiguousarray(col.to_numpy(zero_copy_only=False), dtype=np.float64))   # nulls -> NaN
+        ptrs = (C.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
+        h = C.c_void_p()
+        _lib.check(_lib.load().pbn_rcot_create(ctx.handle, ptrs, len(cols), rb.num_rows, int(random_fourier_xy), int(random_fourier_z),
+                                               C.c_uint32(self._seed & 0xFFFFFFFF), C.byref(h)))
+        self._handle = h
+
+    def _idx(self, name):
+        if name in self._index:
+            return self._index[name]
+        if name in self._all_names:
+            raise ValueError("Column are not continuous.")
+        raise ValueError(f"Variable {name} not present in RCoT.")
+
+    def _args(self, x, y, z):
+        cond = [] if z is None else ([z] if isinstance(z, str) else list(z))
+        return self._idx(x), self._idx(y), len(cond), _lib.int_array([self._idx(c) for c in cond] or [0])
+
+    def pvalue(self, x, y, z=None):
+        lib = _lib.load()
+        _lib.check(lib.pbn_rcot_set_order(self._handle, 0, None))
+        a = self._args(x, y, z)
+        p = lib.pbn_rcot_pvalue(self._handle, a[0], a[1], a[2], a[3])
+        if np.isnan(p):
+            raise ValueError("RCoT: " + lib.pbn_last_error().decode())
+        return p
+
+    def detail(self, x, y, z=None):
+        """One test in full (a test aid): n_valid, sigma (x, y, Z), W and b per role, the Z columns used, sta, the positive
+        eigenvalues, the approximation that answered ("none", "HBE", "LPB4") and the p-value.  The x role is the variable
+        with the smaller column index."""
+        lib = _lib.load()
+        _lib.check(lib.pbn_rcot_set_order(self._handle, 0, None))
+        a = self._args(x, y, z)
+        k = a[2]
+        nv = C.c_int64(0)
+        sigma = np.zeros(3)
+        nxy_cap = 8
+        W = np.zeros(2 * nxy_cap + max(k, 1) * 256)
+        b = np.zeros(2 * nxy_cap + 256)
+        zu = (C.c_int * max(1, k))()
+        nzu, neig, method = C.c_int(0), C.c_int(0), C.c_int(0)
+        sta, p = C.c_double(0), C.c_double(0)
+        eig = np.zeros(64)
+        _lib.check(lib.pbn_rcot_detail(self._handle, a[0], a[1], a[2], a[3], C.byref(nv), _lib.dptr(sigma), _lib.dptr(W), _lib.dptr(b), zu,
+                                       C.byref(nzu), C.byref(sta), _lib.dptr(eig), C.byref(neig), C.byref(method), C.byref(p)))
+        xi, yi = sorted((a[0], a[1]))
+        kz = max(nzu.value, 0)
+        return {"n_valid": nv.value, "sigma": sigma, "x": self._names[xi], "y": self._names[yi],
+                "z": [self._names[zu[i]] for i in range(kz)], "trivial": nzu.value < 0, "W": W, "b": b, "sta": sta.value,
+                "eigenvalues": eig[:neig.value].copy(), "method": ("none", "HBE", "LPB4")[method.value], "pvalue": p.value}
+
+    def variable_names(self):
+        return list(self._all_names)
+
+    def _ci_callback(self, nodes):
+        lib = _lib.load()
+        _lib.check(lib.pbn_rcot_set_order(self._handle, len(nodes), _lib.int_array([self._idx(n) for n in nodes])))
+        return C.cast(lib.pbn_rcot_pvalue, C.c_void_p), self._handle, self, []
+
+    def _ci_batch_callback(self):
+        """Batched native callback (same handle / index order as _ci_callback): one K1 and one K2 launch for many tests."""
+        return C.cast(_lib.load().pbn_rcot_pvalue_batch, C.c_void_p)
+
+    def __del__(self):
+        try:
+            if _lib.alive() and getattr(self, "_handle", None):
+                _lib.load().pbn_rcot_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+
 class ChiSquare(MutualInformation):
     """pbn.ChiSquare(df): Pearson's chi-square test on the categorical columns (learning/independences/discrete/
     chi_square.hpp); shares the device counting pass of MutualInformation."""

@@ -1,0 +1,206 @@
+"""numpy / scipy restatement of RCoT (learning/independences/continuous/RCoT.{hpp,cpp}, util/chisquaresum.hpp) for the tests.
+
+Given the W and b that pbn_rcot_detail reports, it recomputes the statistic, the eigenvalues of the residual-product covariance
+and the p-value from the table itself.  `perm` reorders the rows (the same test, another summation order): the spread between
+two such restatements is the scale the device result is held to.  Nothing under pybnesian_amd/ imports this file.
+"""
+import numpy as np
+from scipy import stats
+
+
+# ---- weighted chi-square sums ------------------------------------------------------------------------------------------------
+def hbe_sf(w, q):
+    w = np.asarray([v for v in w if v > 0], dtype=np.float64)
+    if len(w) == 0:
+        return 1.0
+    k1, k2, k3 = w.sum(), 2 * (w * w).sum(), 8 * (w ** 3).sum()
+    nu = 8 * k2 ** 3 / k3 ** 2
+    stat = np.sqrt(2 * nu / k2) * (q - k1) + nu
+    if stat <= 0:
+        return 1.0
+    return float(stats.gamma.sf(stat, nu / 2, scale=2))
+
+
+def brent_root(f, ax, bx, tol, maxit):
+    """Forsythe-Malcolm-Moler zeroin, step for step."""
+    eps = np.finfo(float).eps
+    a, b = ax, bx
+    c = a
+    fa, fb = f(a), f(b)
+    fc = fa
+    if fa == 0:
+        return a
+    if fb == 0:
+        return b
+    for _ in range(maxit + 1):
+        prev = b - a
+        if abs(fc) < abs(fb):
+            a, b, c = b, c, b
+            fa, fb, fc = fb, fc, fb
+        tol_act = 2 * eps * abs(b) + tol / 2
+        step = (c - b) / 2
+        if abs(step) <= tol_act or fb == 0:
+            return b
+        if abs(prev) >= tol_act and abs(fa) > abs(fb):
+            cb = c - b
+            if a == c:
+                t1 = fb / fa
+                p, q = cb * t1, 1 - t1
+            else:
+                qa, t1, t2 = fa / fc, fb / fc, fb / fa
+                p = t2 * (cb * qa * (qa - t1) - (b - a) * (t1 - 1))
+                q = (qa - 1) * (t1 - 1) * (t2 - 1)
+            if p > 0:
+                q = -q
+            else:
+                p = -p
+            if p < 0.75 * cb * q - abs(tol_act * q) / 2 and p < abs(prev * q / 2):
+                step = p / q
+        if abs(step) < tol_act:
+            step = tol_act if step > 0 else -tol_act
+        a, fa = b, fb
+        b += step
+        fb = f(b)
+        if (fb > 0 and fc > 0) or (fb < 0 and fc < 0):
+            c, fc = a, fa
+    raise ArithmeticError("no convergence")
+
+
+def lpb4_sf(w, q):
+    """Lindsay-Pilla-Basak, four support points; raises ArithmeticError where the method breaks down."""
+    w = np.asarray([v for v in w if v > 0], dtype=np.float64)
+    p = 4
+    if len(w) < p:
+        raise ArithmeticError("lpb4 needs 4 weights")
+    kap = np.zeros(2 * p + 1)
+    fact = 1.0
+    for r in range(1, 2 * p + 1):
+        if r > 1:
+            fact *= 2.0 * (r - 1)
+        kap[r] = fact * np.sum(w ** r)
+    mom = np.zeros(2 * p + 1)
+    mom[0] = 1
+    from math import comb
+
+    for n in range(1, 2 * p + 1):
+        mom[n] = sum(comb(n - 1, j - 1) * kap[j] * mom[n - j] for j in range(1, n + 1))
+
+    def delta(s, lam):
+        d = np.empty((s, s))
+        for i in range(s):
+            for j in range(s):
+                d[i, j] = mom[i + j] / np.prod([1 + l * lam for l in range(1, i + j)])
+        return d
+
+    lam = mom[2] / mom[1] ** 2 - 1
+    for i in range(2, p + 1):
+        lam = brent_root(lambda x: np.linalg.det(delta(i + 1, x)), 0.0, lam, 1e-9, 1000)
+    M = delta(p + 1, lam)
+    coef = np.zeros(p + 1)
+    for i in range(p + 1):
+        Mi = M.copy()
+        Mi[:, p] = 0
+        Mi[i, p] = 1
+        coef[p - i] = np.linalg.det(Mi)
+    mu = np.roots(coef).real
+    if len(mu) != p or not np.all(np.isfinite(mu)):
+        raise ArithmeticError("quartic")
+    V = np.vander(mu, p, increasing=True).T
+    rhs = np.array([mom[r] / np.prod([1 + l * lam for l in range(1, r)]) for r in range(p)])
+    pi = np.linalg.solve(V, rhs)
+    shape = 1 / lam
+    if not (shape > 0 and np.isfinite(shape)):
+        raise ArithmeticError("shape")
+    theta = mu * lam
+    if not np.all(theta > 0):
+        raise ArithmeticError("Wrong theta parameter.")
+    return float(np.sum(pi * stats.gamma.sf(q, shape, scale=theta)))
+
+
+def chisq_sum_sf(w, q, method=0):
+    """(p-value, 'HBE' | 'LPB4') under the reference's rule (method 0), HBE alone (1) or LPB4 alone (2)."""
+    pos = [v for v in w if v > 0]
+    if method == 2:
+        r, used = lpb4_sf(pos, q), "LPB4"
+    elif method == 1 or len(pos) < 4:
+        r, used = hbe_sf(pos, q), "HBE"
+    else:
+        try:
+            r, used = lpb4_sf(pos, q), "LPB4"
+        except (ArithmeticError, np.linalg.LinAlgError):
+            r, used = hbe_sf(pos, q), "HBE"
+    return max(r, 0.0), used
+
+
+# ---- the test ------------------------------------------------------------------------------------------------------------------
+def normalize(col):
+    """DataFrame::normalize over the valid values (NaN = null)."""
+    col = np.asarray(col, dtype=np.float64).copy()
+    ok = ~np.isnan(col)
+    v = col[ok]
+    sd = v.std(ddof=1) if len(v) > 1 else 0.0
+    col[ok] = (v - v.mean()) / sd if sd != 0 else 0.0
+    return col
+
+
+def _features(v, W, b):
+    f = np.sqrt(2.0) * np.cos(v @ W + b)
+    m = f.mean(axis=0)
+    s = f.std(axis=0, ddof=1)
+    out = np.zeros_like(f)
+    nz = s != 0
+    out[:, nz] = (f[:, nz] - m[nz]) / s[nz]
+    return out
+
+
+def _cov(a, b):
+    return (a - a.mean(0)).T @ (b - b.mean(0)) / (a.shape[0] - 1)
+
+
+def sigma_window(table, names, valid_in=()):
+    """rf_sigma_impl's bandwidth from the table itself: the median Euclidean distance between the first min(500, n) rows valid in
+    all of `names` and `valid_in` (each column normalised over its own valid values first), 0 -> 1."""
+    from scipy.spatial.distance import pdist
+
+    cols = np.column_stack([normalize(table[n]) for n in names])
+    ok = ~np.isnan(cols).any(axis=1)
+    for v in valid_in:
+        ok &= ~np.isnan(np.asarray(table[v], dtype=np.float64))
+    cols = cols[ok][:500]
+    if len(cols) < 2:
+        return 1.0
+    med = float(np.median(pdist(cols)))
+    return 1.0 if med == 0 else med
+
+
+def rcot_from_detail(table, det, nxy, nz, perm=None):
+    """table: dict name -> raw column (NaN = null).  Returns (sta, positive eigenvalues (ascending), p, method).  perm: rows
+    permuted with this seed (the same test, another summation order)."""
+    names = [det["x"], det["y"]] + list(det["z"])
+    cols = np.column_stack([normalize(table[n]) for n in names])
+    cols = cols[~np.isnan(cols).any(axis=1)]
+    if perm is not None:
+        cols = cols[np.random.default_rng(perm).permutation(len(cols))]
+    n = len(cols)
+    k = len(det["z"])
+    W, b = det["W"], det["b"]
+    fx = _features(cols[:, :1], W[:nxy].reshape(1, nxy), b[:nxy])
+    fy = _features(cols[:, 1:2], W[nxy:2 * nxy].reshape(1, nxy), b[nxy:2 * nxy])
+    if k == 0:
+        cxy = _cov(fx, fy)
+        rx, ry = fx, fy
+    else:
+        Wz = W[2 * nxy:2 * nxy + k * nz].reshape(nz, k).T
+        fz = _features(cols[:, 2:], Wz, b[2 * nxy:2 * nxy + nz])
+        czz = _cov(fz, fz) + 1e-10 * np.eye(nz)
+        iczz = np.linalg.inv(czz)
+        cxz, czy = _cov(fx, fz), _cov(fz, fy)
+        cxy = _cov(fx, fy) - cxz @ iczz @ czy
+        rx = fx - fz @ (iczz @ cxz.T)
+        ry = fy - fz @ (iczz @ czy)
+    sta = n * np.sum(cxy ** 2)
+    prod = (rx[:, :, None] * ry[:, None, :]).reshape(n, nxy * nxy)
+    ev = np.linalg.eigvalsh(prod.T @ prod / n)
+    ev = np.sort(ev[ev > 0])
+    p, used = chisq_sum_sf(ev, sta, 1 if (k and nz == 1) else 0)
+    return sta, ev, p, used
