@@ -530,7 +530,7 @@ __global__ __launch_bounds__(256) void query_prepass_kernel(const double* __rest
                                                             const uint32_t* __restrict__ tkeys, int64_t n, int zd, int pd,
                                                             double* __restrict__ qbox, double* __restrict__ qthr, double* __restrict__ qlb,
                                                             const double* __restrict__ subpart, int P, int which, double log2_nsub, int sum_bound,
-                                                            const double* __restrict__ tile_box, int tile_window) {
+                                                            const double* __restrict__ tile_box, int tile_window, int64_t* __restrict__ qtpos) {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = q < nq;
     double z[PBN_MAX_D];
@@ -619,9 +619,100 @@ __global__ __launch_bounds__(256) void query_prepass_kernel(const double* __rest
     if (qlb && q < (nq + 15) / 16 * 16) qlb[q] = valid ? best : -INFINITY;   // per query: the sweep's starting offset
     if (valid && (threadIdx.x & 15) == 0) {
         const int64_t tile = q >> 4;
+        if (qtpos) qtpos[tile] = tpos_;   // the tile's first query's training position: the centre of query_window_kernel's window
         qthr[tile] = thr;
         for (int k = 0; k < pd; ++k) { qbox[tile * 2 * pd + k] = lob[k]; qbox[tile * 2 * pd + pd + k] = hib[k]; }
     }
+}
+
+// Window-sum bound (sum-only pruned sweeps of the rotated d = 7, 8 models, kde_prune_rotates): one wave per 16-query tile adds up the EXACT
+// terms of its queries against the 2 W training tiles around the tile's position in the sorted order (qtpos, from query_prepass_kernel),
+// with the sweep's own fp64 MFMA exponents (fold: the norm rides in a K slot; otherwise the norms are added).  In 8 dimensions the prepass's
+// 64 neighbours and tile-box corners sit a median 13 log2 units below a query's true sum; the window recovers most of that
+// (tools/prune_window_estimate.py).  Any subset of a query's terms is a lower bound of its whole sum, so
+//   lb = log2(window sum) - PBN_WINDOW_SLACK <= log2(whole sum):
+// the exponents x are exact to ~1e-12 units; the per-lane offset mx is an integer >= every x seen, so 2^(x - mx) <= 1 goes through v_exp_f32
+// on (float)(x - mx): the cast errs by at most |x - mx| 2^-24 <= 150 2^-24 units where the term is not below fp32's range (smaller terms
+// may flush to 0 - a smaller sum, still a bound), v_exp_f32 by 1 ulp, and the four terms of a tile are added in fp32 (2 roundings) before
+// the fp64 running sum: each term at most 1.0001e-5 too large, the sum likewise, log2 of it at most 1.5e-5 units too large - far inside
+// the slack of 2^-8.  Rescaling by 2^(integer) is exact (or underflows: smaller).  Padding rows (row >= n_train) and NaN exponents are
+// left out, and queries that are NaN or beyond nq do not enter the tile's minimum.
+// Per query tile the smallest lb of its valid queries raises qthr where it is larger; per query the largest window exponent raises qlb
+// where it is larger (an exponent of a real term: a lower bound of the query's largest).  The window's terms are NOT added to any sum.
+// dbg (nullable, pbn_debug_sum_window): lb per query in the sorted order, -inf where there is none.
+#define PBN_WINDOW_SLACK 0x1p-8
+template <bool FOLD>
+__global__ __launch_bounds__(256) void query_window_kernel(const double* __restrict__ Ap, const double* __restrict__ Np, const double* __restrict__ Bp,
+                                                           const double* __restrict__ NYp, int64_t ntiles, int64_t n_train, int64_t nqtiles, int64_t nq,
+                                                           const int64_t* __restrict__ qtpos, int window, double* __restrict__ qthr,
+                                                           double* __restrict__ qlb, double* __restrict__ dbg) {
+    constexpr int KS = 2;
+    using V = Tr<double>::vec4;
+    const int lane = threadIdx.x & 63, lg = lane >> 4, col = lane & 15;
+    const int64_t qt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (qt >= nqtiles) return;   // (wave-uniform; no barriers)
+    const int64_t q = qt * 16 + col;
+    double b[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) b[ks] = Bp[(qt * KS + ks) * 64 + lane];
+    const double ny = NYp[qt * 16 + col];
+    const int64_t tt = qtpos[qt] >> 4;
+    const int64_t t_lo = tt - window > 0 ? tt - window : 0, t_hi = tt + window < ntiles ? tt + window : ntiles;
+    double mx = -INFINITY, s = 0.0, top = -INFINITY;   // integer offset, sum of 2^(x - mx), largest x
+    // the next tile's fragments are in flight while one is processed (after the last tile the last one is loaded again)
+    double a0 = 0.0, a1 = 0.0;
+    V nx = {};
+    auto load = [&](int64_t t) {
+        a0 = Ap[(t * KS) * 64 + lane];
+        a1 = Ap[(t * KS + 1) * 64 + lane];
+        if (!FOLD) nx = *(const V*)(Np + t * 16 + lg * 4);
+    };
+    if (t_lo < t_hi) load(t_lo);
+    for (int64_t t = t_lo; t < t_hi; ++t) {
+        V acc = FOLD ? V{ny, ny, ny, ny} : nx + ny;
+        const double c0 = a0, c1 = a1;
+        load(t + 1 < t_hi ? t + 1 : t);
+        acc = Tr<double>::mfma(c0, b[0], acc);
+        acc = Tr<double>::mfma(c1, b[1], acc);
+        double x[4], tm = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bool ok = t * 16 + Tr<double>::crow(lg, i) < n_train && acc[i] == acc[i];
+            x[i] = ok ? acc[i] : -INFINITY;
+            tm = x[i] > tm ? x[i] : tm;
+        }
+        if (tm > mx) {
+            const double nm = __builtin_ceil(tm), sh = mx - nm;
+            s = sh < -2000.0 ? 0.0 : __builtin_ldexp(s, (int)sh);
+            mx = nm;
+            top = tm;
+        }
+        if (tm > -INFINITY) {
+            const float f0 = __builtin_amdgcn_exp2f((float)(x[0] - mx)), f1 = __builtin_amdgcn_exp2f((float)(x[1] - mx));
+            const float f2 = __builtin_amdgcn_exp2f((float)(x[2] - mx)), f3 = __builtin_amdgcn_exp2f((float)(x[3] - mx));
+            s += (double)((f0 + f1) + (f2 + f3));
+        }
+    }
+    // the four lanes of a query column (lg = 0..3)
+    for (int off = 16; off < 64; off <<= 1) {
+        const double om = __shfl_xor(mx, off), os = __shfl_xor(s, off), ot = __shfl_xor(top, off);
+        top = ot > top ? ot : top;
+        if (om > mx) {
+            const double sh = mx - om;
+            s = (sh < -2000.0 ? 0.0 : __builtin_ldexp(s, (int)sh)) + os;
+            mx = om;
+        } else if (om > -INFINITY) {
+            const double sh = om - mx;
+            s += sh < -2000.0 ? 0.0 : __builtin_ldexp(os, (int)sh);
+        }
+    }
+    const bool valid = q < nq && ny == ny;
+    const double lb = (valid && s > 0.0) ? mx + log2(s) - PBN_WINDOW_SLACK : -INFINITY;
+    if (dbg && lg == 0 && q < nq) dbg[q] = lb;
+    if (qlb && lg == 0 && valid && top > qlb[q]) qlb[q] = top;
+    double g = valid ? lb : INFINITY;
+    for (int off = 1; off < 16; off <<= 1) { const double o = __shfl_xor(g, off); g = o < g ? o : g; }
+    if (lane == 0 && g < INFINITY && g > qthr[qt]) qthr[qt] = g;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3433,12 +3524,21 @@ void launch_batch_boxes(const double* tile_box, int pd, int64_t ntiles, int64_t 
 }
 void launch_query_prepass(const double* zq_row, const int32_t* qperm, int64_t nq, const uint32_t* qkeys_sorted, const double* ztrain_sorted,
                           const uint32_t* tkeys_sorted, int64_t n, int zd, int pd, double* qbox, double* qthr, double* qlb, hipStream_t st,
-                          const double* subpart, int P, int which, double log2_nsub, const double* tile_box) {
+                          const double* subpart, int P, int which, double log2_nsub, const double* tile_box, int64_t* qtpos) {
     if (nq == 0) return;
     static const int sum_bound = PBN_TUNE(GROUP_SUM_BOUND, 1);
     static const int tile_window = std::max(0, PBN_TUNE(GROUP_TILE_WINDOW, 256));
     hipLaunchKernelGGL(query_prepass_kernel, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0, st, zq_row, qperm, nq, qkeys_sorted, ztrain_sorted,
-                       tkeys_sorted, n, zd, pd, qbox, qthr, qlb, subpart, P, which, log2_nsub, sum_bound, tile_box, tile_window);
+                       tkeys_sorted, n, zd, pd, qbox, qthr, qlb, subpart, P, which, log2_nsub, sum_bound, tile_box, tile_window, qtpos);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_query_window(const double* Apack, const double* nxpack, const double* Bpack, const double* nypack, int64_t ntiles, int64_t n_train,
+                         int64_t nqtiles, int64_t nq, const int64_t* qtpos, int window, bool fold, double* qthr, double* qlb, double* dbg, hipStream_t st) {
+    if (nqtiles == 0 || window <= 0) return;
+    const dim3 grid((unsigned)ceil_div(nqtiles, 4));
+    if (fold) hipLaunchKernelGGL(query_window_kernel<true>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, nq, qtpos, window, qthr, qlb, dbg);
+    else hipLaunchKernelGGL(query_window_kernel<false>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, nq, qtpos, window, qthr, qlb, dbg);
     HIP_CHECK(hipGetLastError());
 }
 

@@ -275,7 +275,12 @@ void launch_batch_boxes(const double* tile_box, int pd, int64_t ntiles, int64_t 
 // largest exponent
 void launch_query_prepass(const double* zq_row, const int32_t* qperm, int64_t nq, const uint32_t* qkeys_sorted, const double* ztrain_sorted,
                           const uint32_t* tkeys_sorted, int64_t n, int zd, int pd, double* qbox, double* qthr, double* qlb, hipStream_t st,
-                          const double* subpart = nullptr, int P = 2, int which = 0, double log2_nsub = 0.0, const double* tile_box = nullptr);
+                          const double* subpart = nullptr, int P = 2, int which = 0, double log2_nsub = 0.0, const double* tile_box = nullptr,
+                          int64_t* qtpos = nullptr);
+// sum-only pruned sweeps of the rotated (d = 7, 8) models, KS = 2: per query tile the exact terms over the `window` training tiles on either
+// side of qtpos[tile] (query_prepass_kernel) raise qthr (lower bound of log2 of the tile's sums) and qlb (of each query's largest exponent)
+void launch_query_window(const double* Apack, const double* nxpack, const double* Bpack, const double* nypack, int64_t ntiles, int64_t n_train,
+                         int64_t nqtiles, int64_t nq, const int64_t* qtpos, int window, bool fold, double* qthr, double* qlb, double* dbg, hipStream_t st);
 void sort_keys(pbn::dev_buf<char>& tmp, const uint32_t* keys_in, uint32_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int64_t n,
                int bits, hipStream_t st);
 // 52 (fp64) / 40 (fp32 on the f16 cores) at 10^6 training rows, + log2(n_train / 10^6): a constant bound (2.2e-10 / 9.1e-7 of a sum) on what

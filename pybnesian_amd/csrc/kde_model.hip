@@ -2,9 +2,12 @@
 // engine.  See kde_kernels.hip for the device side.
 #include <cstdio>
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <mutex>
 #include <numeric>
+#include <vector>
 
 #include "hostmath.hpp"
 #include "kde_kernels.hpp"
@@ -454,6 +457,12 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store) {
     }
 }
 
+// pbn_debug_sum_window (test aid, not part of the C ABI header): capture the window bounds (query_window_kernel) of the sum-only evaluations
+// that follow; returns how many the last one produced and copies up to `cap` of them - log2 units, the table's row order, -inf = none
+static std::atomic<bool> g_window_capture{false};
+static std::mutex g_window_mu;
+static std::vector<double> g_window_lb;
+
 void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, const int* cols, int64_t row0, int64_t n,
                       double* dev_logl, double* dev_sum, const int32_t* dev_rows, double* dev_sum_marg, bool precise) {
     check_cols(test, cols, m.d, "pbn_kde_logl");
@@ -527,16 +536,26 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     PruneSide qs{};
     // a rotated (d = 7, 8) model prunes its sum-only sweeps only; per-row logl outputs take the plain sweep over the same (sorted) pack
     const bool prune = m.prune && (sum_only || !m.wfull);
+    // ... and those sweeps tighten the prepass bounds with the exact terms of a window of training tiles (query_window_kernel): W tiles on either
+    // side, PBN_SUM_WINDOW (0 = the prepass bounds alone).  W = 256: C2 visits 0.525 -> 0.441 of its blocks, 27.3 -> 24.3 ms;
+    // 64 is even within noise, 1024 costs 3.2 ms of window for 0.435 (profiles/r8/)
+    const int window = (prune && m.wfull && m.KS == 2) ? std::max(0, knob_int("PBN_SUM_WINDOW", 256)) : 0;
+    const bool wdbg = window > 0 && g_window_capture.load();
+    int64_t* qtpos = nullptr;
+    double* qdbg = nullptr;
     if (prune) {
         auto al = [](size_t x) { return (x + 255) / 256 * 256; };
         const size_t qbox_b = al((size_t)nqtiles * 2 * m.pdims * sizeof(double)), qthr_b = al((size_t)nqtiles * sizeof(double));
         const size_t qlb_b = al((size_t)nqtiles * 16 * sizeof(double));
-        qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.kdims, qbox_b + qthr_b + qlb_b);
+        const size_t qtpos_b = window ? al((size_t)nqtiles * sizeof(int64_t)) : 0, qdbg_b = wdbg ? al((size_t)nqtiles * 16 * sizeof(double)) : 0;
+        qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.kdims, qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b);
         pa.perm = qs.perm;
         qperm = qs.perm;
         qbox = (double*)qs.rest; qthr = (double*)(qs.rest + qbox_b);
         static const bool use_qlb = PBN_TUNE(SWEEP_QLB, 1) != 0;   // offsets of the pruned plain sweeps from the prepass bounds
         if (use_qlb) qlb = (double*)(qs.rest + qbox_b + qthr_b);
+        if (window) qtpos = (int64_t*)(qs.rest + qbox_b + qthr_b + qlb_b);
+        if (wdbg) qdbg = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b);
     }
     pa.pack = q; pa.npack = q + bpack_b; pa.xpack = m.cond ? q + bpack_b + ny_b : nullptr;
     pa.xnorm = xn_b ? q + bpack_b + ny_b + bx_b : nullptr;
@@ -560,7 +579,21 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
             subpart = ss.part;
         }
         launch_query_prepass(qs.zrow, qs.perm, n, qs.keys, m.zsorted, m.keys_sorted, m.N, m.zdims, m.pdims, (double*)qbox, (double*)qthr, (double*)qlb,
-                             ctx->stream, subpart, P, m.cond ? 2 : 0, subpart ? std::log2((double)m.nsub) : 0.0, m.cond ? nullptr : m.tile_box);
+                             ctx->stream, subpart, P, m.cond ? 2 : 0, subpart ? std::log2((double)m.nsub) : 0.0, m.cond ? nullptr : m.tile_box, qtpos);
+        if (window) {
+            { KernelTimer kt(ctx, PBN_K_PACK); launch_query_window((const double*)m.Apack, (const double*)m.nxpack, (const double*)pa.pack, (const double*)pa.npack,
+                                                               m.ntiles, m.N, nqtiles, n, qtpos, window, fold, (double*)qthr, (double*)qlb, qdbg, ctx->stream); }
+            if (wdbg) {   // pbn_debug_sum_window: the queries' bounds, in the table's row order
+                std::vector<double> lb((size_t)n);
+                std::vector<int32_t> perm((size_t)n);
+                HIP_CHECK(hipMemcpyAsync(lb.data(), qdbg, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_CHECK(hipMemcpyAsync(perm.data(), qperm, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                std::lock_guard<std::mutex> lk(g_window_mu);
+                g_window_lb.assign((size_t)n, -INFINITY);
+                for (int64_t i = 0; i < n; ++i) g_window_lb[(size_t)perm[(size_t)i]] = lb[(size_t)i];
+            }
+        }
     }
 
     // split the training tiles so that the grid is a few waves deep on every CU
@@ -626,3 +659,12 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
 }
 
 }  // namespace pbn
+
+extern "C" int64_t pbn_debug_sum_window(double* out, int64_t cap, int capture) {
+    pbn::g_window_capture.store(capture != 0);
+    std::lock_guard<std::mutex> lk(pbn::g_window_mu);
+    const int64_t n = (int64_t)pbn::g_window_lb.size();
+    for (int64_t i = 0; out && i < n && i < cap; ++i) out[i] = pbn::g_window_lb[(size_t)i];
+    if (!capture) pbn::g_window_lb.clear();
+    return n;
+}
