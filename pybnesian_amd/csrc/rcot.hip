@@ -29,11 +29,13 @@
 //  * HBE at a statistic below the support of its gamma law answers 1 (boost raises a domain error there); no positive weight
 //    at all answers 1.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <complex>
 #include <cstring>
 #include <limits>
 #include <memory>
+#include <mutex>
 #include <random>
 #include <vector>
 
@@ -55,8 +57,9 @@ namespace {
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 struct RcotTest {
-    int32_t col[RCOT_MAX_IN];   // input columns: x (the smaller index), y, then Z (sorted)
-    int32_t nin;                // 2 + k
+    int32_t col[RCOT_MAX_IN];   // input columns: x (the smaller index), y, the k Z columns used (sorted), then validity-only ones
+    int32_t nin;                // 2 + k + the validity-only columns
+    int32_t k;                  // Z columns made into features
     int32_t F;                  // features: 2 nxy + (k ? nz : 0); column F of [f, 1] is the ones column
     int32_t nxy;
     int32_t nt;                 // K1 column tiles: ceil((F + 1) / 16)
@@ -104,7 +107,7 @@ __device__ __forceinline__ void rcot_fill(const double* __restrict__ cols, int64
     }
     __syncthreads();
     const int fp = 16 * t.nt;
-    const int k = t.nin - 2;
+    const int k = t.k;
     for (int e = tid; e < RCOT_CHUNK * fp; e += 256) {
         const int r = e / fp, c = e % fp;
         feat[r * S + c] = valid[r] ? rcot_feature(vals + r * vs, c, t.F, t.nxy, k, t.kw, W, b, shift) : 0.0;
@@ -502,6 +505,7 @@ namespace {
 struct Plan {
     int a = 0, b = 0;
     std::vector<int> z;          // conditioning columns used (sorted, constant ones dropped)
+    std::vector<int> zv;         // every Z column dropped: those with nulls, read for validity only (the reference's rows for RIT)
     bool trivial = false;        // x or y constant: p = 1
     int F = 0, k = 0;
     double sigma[3] = {0, 0, 0};
@@ -581,6 +585,11 @@ Plan plan_test(pbn_rcot* h, int v1, int v2, int n_cond, const int* cond) {
     for (int c : z)
         if (!constant_on(c, vr)) pl.z.push_back(c);
     pl.k = (int)pl.z.size();
+    // every Z column constant: the reference runs RIT on the rows valid in x, y and all of Z, so the device passes still skip the
+    // rows where a dropped column is null (with only some of them dropped, the rows valid in x, y and the columns used: DESIGN §3.9)
+    if (!pl.k && vr)
+        for (int c : z)
+            if (h->has_null[(size_t)c]) pl.zv.push_back(c);
     pl.F = 2 * h->nxy + (pl.k ? h->nz : 0);
     // sigma window: the first 500 rows valid in x, y and the Z columns used (the dropped ones were only constant, not null-free
     // on the same rows: with nulls the window follows the reference and takes the rows valid in all the test's variables)
@@ -714,8 +723,16 @@ std::vector<double> unpack(const double* img, int nt, int n) {
     return G;
 }
 
+// what a K1 / K2 launch took (pbn_debug_rcot's launch log): K1's rcot_gram_kernel instantiation PPW or K2's product tiles, dynamic
+// LDS bytes, blocks
+struct Launched {
+    int variant = 0;
+    size_t lds = 0;
+    unsigned blocks = 0;
+};
+
 template <typename K>
-void launch_pass(pbn_rcot* h, int pass, const std::vector<Plan*>& ps, std::vector<std::vector<double>>& results) {
+Launched launch_pass(pbn_rcot* h, int pass, const std::vector<Plan*>& ps, std::vector<std::vector<double>>& results) {
     pbn_ctx* ctx = h->ctx;
     const int64_t rpb = rows_per_block(h->N), nb = ceil_div(h->N, rpb);
     std::vector<RcotTest> ts(ps.size());
@@ -729,7 +746,8 @@ void launch_pass(pbn_rcot* h, int pass, const std::vector<Plan*>& ps, std::vecto
         std::memset(&d, 0, sizeof d);
         d.col[0] = pl.a; d.col[1] = pl.b;
         for (int i = 0; i < pl.k; ++i) d.col[2 + i] = pl.z[(size_t)i];
-        d.nin = 2 + pl.k; d.F = pl.F; d.nxy = h->nxy; d.nt = pl.nt(); d.kw = std::max(1, pl.k);
+        for (size_t i = 0; i < pl.zv.size(); ++i) d.col[2 + pl.k + i] = pl.zv[i];
+        d.nin = 2 + pl.k + (int)pl.zv.size(); d.k = pl.k; d.F = pl.F; d.nxy = h->nxy; d.nt = pl.nt(); d.kw = std::max(1, pl.k);
         d.ntq = (h->nxy * h->nxy + 15) / 16;
         const int fp = 16 * d.nt;
         d.par = (int64_t)par.size();
@@ -772,10 +790,12 @@ void launch_pass(pbn_rcot* h, int pass, const std::vector<Plan*>& ps, std::vecto
     HIP_CHECK(hipMemcpyAsync(h->d_blk.p, blk.data(), blk.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(h->d_seg.p, seg.data(), seg.size() * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     const unsigned nblk = (unsigned)(blk.size() / 4);
+    Launched l;
     {
         KernelTimer kt(ctx, pass == 1 ? PBN_K_GRAM : PBN_K_RCOT_PROD);
-        K{}(h, max_np, nblk, s_max, vs, fp_max);
+        l = K{}(h, max_np, nblk, s_max, vs, fp_max);
     }
+    l.blocks = nblk;
     {
         KernelTimer kt(ctx, PBN_K_FINISH);
         hipLaunchKernelGGL(rcot_reduce_kernel, dim3((unsigned)ceil_div(max_ws, 256), (unsigned)ps.size()), dim3(256), 0, ctx->stream,
@@ -791,6 +811,7 @@ void launch_pass(pbn_rcot* h, int pass, const std::vector<Plan*>& ps, std::vecto
         const int nt = pass == 1 ? ts[t].nt : ts[t].ntq;
         results[t] = unpack(host.data() + seg[4 * t + 3], nt, n);
     }
+    return l;
 }
 
 // dynamic LDS of a launch (see rcot_gram_kernel); more than the default 64 KiB is asked for explicitly (gfx950 has 160 KiB per CU)
@@ -802,33 +823,71 @@ size_t lds_bytes(Kern kern, int s_max, int vs, int p_doubles) {
 }
 
 struct LaunchGram {
-    void operator()(pbn_rcot* h, int max_np, unsigned nblk, int s_max, int vs, int) const {
+    template <int P>
+    static Launched go(pbn_rcot* h, unsigned nblk, int s_max, int vs) {
+        Launched l;
+        l.variant = P;
+        l.lds = lds_bytes(rcot_gram_kernel<P>, s_max, vs, 0);
+        hipLaunchKernelGGL(rcot_gram_kernel<P>, dim3(nblk), dim3(256), l.lds, h->ctx->stream, h->d_cols.p, h->N, h->d_tests.p, h->d_par.p,
+                           h->d_blk.p, h->d_part.p, s_max, vs);
+        return l;
+    }
+    Launched operator()(pbn_rcot* h, int max_np, unsigned nblk, int s_max, int vs, int) const {
         const int ppw = (max_np + 3) / 4;
-        const double* c = h->d_cols.p;
-        auto st = h->ctx->stream;
-#define RCOT_K1(P) hipLaunchKernelGGL(rcot_gram_kernel<P>, dim3(nblk), dim3(256), lds_bytes(rcot_gram_kernel<P>, s_max, vs, 0), st, c, h->N, \
-                                      h->d_tests.p, h->d_par.p, h->d_blk.p, h->d_part.p, s_max, vs)
-        if (ppw <= 1) RCOT_K1(1);
-        else if (ppw <= 2) RCOT_K1(2);
-        else if (ppw <= 4) RCOT_K1(4);
-        else if (ppw <= 8) RCOT_K1(8);
-        else if (ppw <= 16) RCOT_K1(16);
-        else RCOT_K1(34);
-#undef RCOT_K1
+        if (ppw <= 1) return go<1>(h, nblk, s_max, vs);
+        if (ppw <= 2) return go<2>(h, nblk, s_max, vs);
+        if (ppw <= 4) return go<4>(h, nblk, s_max, vs);
+        if (ppw <= 8) return go<8>(h, nblk, s_max, vs);
+        if (ppw <= 16) return go<16>(h, nblk, s_max, vs);
+        return go<34>(h, nblk, s_max, vs);
     }
 };
 struct LaunchProd {
-    void operator()(pbn_rcot* h, int, unsigned nblk, int s_max, int vs, int fp_max) const {
-        hipLaunchKernelGGL(rcot_prod_kernel, dim3(nblk), dim3(256), lds_bytes(rcot_prod_kernel, s_max, vs, fp_max * 16), h->ctx->stream,
-                           h->d_cols.p, h->N, h->d_tests.p, h->d_par.p, h->d_blk.p, h->d_part.p, s_max, vs);
+    Launched operator()(pbn_rcot* h, int, unsigned nblk, int s_max, int vs, int fp_max) const {
+        Launched l;
+        l.variant = (h->nxy * h->nxy + 15) / 16;
+        l.lds = lds_bytes(rcot_prod_kernel, s_max, vs, fp_max * 16);
+        hipLaunchKernelGGL(rcot_prod_kernel, dim3(nblk), dim3(256), l.lds, h->ctx->stream, h->d_cols.p, h->N, h->d_tests.p, h->d_par.p,
+                           h->d_blk.p, h->d_part.p, s_max, vs);
+        return l;
     }
 };
+
+// pbn_debug_rcot (test aid, not part of the C ABI header; see its definition): what run_plans records while it is armed
+std::atomic<bool> g_rcot_capture{false};
+std::mutex g_rcot_mu;
+std::vector<double> g_rcot_rec;
+std::vector<int64_t> g_rcot_log;
+
+void debug_log_launch(int pass, const Launched& l, size_t tests) {
+    std::lock_guard<std::mutex> lk(g_rcot_mu);
+    g_rcot_log.insert(g_rcot_log.end(), {(int64_t)pass, (int64_t)l.variant, (int64_t)tests, (int64_t)l.lds, (int64_t)l.blocks});
+}
+
+void debug_record(const pbn_rcot* h, const Plan& pl, const std::vector<double>& G1, const std::vector<double>& G2) {
+    const int n = pl.F + 1, nxy = h->nxy;
+    std::vector<int> cols{pl.a, pl.b};
+    cols.insert(cols.end(), pl.z.begin(), pl.z.end());
+    cols.insert(cols.end(), pl.zv.begin(), pl.zv.end());
+    std::vector<double> r{(double)pl.F, (double)nxy, (double)pl.k, (double)h->nz, (double)pl.n_valid, (double)cols.size()};
+    r.insert(r.end(), cols.begin(), cols.end());
+    r.insert(r.end(), pl.W.begin(), pl.W.end());
+    r.insert(r.end(), pl.bias.begin(), pl.bias.end());
+    r.insert(r.end(), pl.shift.begin(), pl.shift.end());
+    r.insert(r.end(), G1.begin(), G1.end());
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < 2 * nxy; ++j) r.push_back(pl.P[(size_t)i * 16 + j]);
+    r.insert(r.end(), G2.begin(), G2.end());
+    std::lock_guard<std::mutex> lk(g_rcot_mu);
+    g_rcot_rec.insert(g_rcot_rec.end(), r.begin(), r.end());
+}
 
 // all non-trivial plans: K1 for a memory chunk of tests, the host step, K2, the p-values
 void run_plans(pbn_rcot* h, std::vector<Plan>& plans) {
     HIP_CHECK(hipSetDevice(h->ctx->device));
     const int64_t nb = ceil_div(h->N, rows_per_block(h->N));
     const int64_t budget = (int64_t)48 << 20;   // partial doubles per launch (384 MiB)
+    const bool dbg = g_rcot_capture.load(std::memory_order_relaxed);
     std::vector<Plan*> todo;
     for (auto& pl : plans)
         if (!pl.trivial) todo.push_back(&pl);
@@ -843,10 +902,15 @@ void run_plans(pbn_rcot* h, std::vector<Plan>& plans) {
             chunk.push_back(todo[i++]);
             used += need;
         }
-        std::vector<std::vector<double>> res;
-        launch_pass<LaunchGram>(h, 1, chunk, res);
+        std::vector<std::vector<double>> res, g1;
+        const Launched l1 = launch_pass<LaunchGram>(h, 1, chunk, res);
         for (size_t t = 0; t < chunk.size(); ++t) solve_between(h, *chunk[t], res[t]);
-        launch_pass<LaunchProd>(h, 2, chunk, res);
+        if (dbg) { debug_log_launch(1, l1, chunk.size()); g1 = res; }
+        const Launched l2 = launch_pass<LaunchProd>(h, 2, chunk, res);
+        if (dbg) {
+            debug_log_launch(2, l2, chunk.size());
+            for (size_t t = 0; t < chunk.size(); ++t) debug_record(h, *chunk[t], g1[t], res[t]);
+        }
         for (size_t t = 0; t < chunk.size(); ++t) finish_test(h, *chunk[t], res[t]);
     }
 }
@@ -968,6 +1032,34 @@ int pbn_rcot_detail(pbn_rcot* h, int v1, int v2, int n_cond, const int* cond, in
         if (method) *method = pl.used;
         if (pvalue) *pvalue = pl.p;
     });
+}
+
+// pbn_debug_rcot (test aid, not part of the C ABI header): op 1 arms the capture and clears it, op 0 disarms and clears.  While armed,
+// run_plans appends one record per test it runs, in plan order, and one launch-log entry per K1 / K2 launch.  op 2 copies up to `cap`
+// doubles of the records into out, op 3 up to `cap` int64 of the launch log; both return how many are held.
+//   record: F, nxy, k, nz, n_valid, nc, the nc columns read (x, y, the Z columns used, then those read for validity only), W (2 nxy + k nz,
+//           as pbn_rcot_detail), b (F), the pilot shift (F), the unpacked K1 Gram ((F + 1)^2), P (F + 1 rows of 2 nxy: row = feature of
+//           [f, 1], columns rx then ry), the unpacked K2 Gram (nxy^4)
+//   launch: pass (1 = K1, 2 = K2), the rcot_gram_kernel instantiation PPW (K1) or the product tiles ntq (K2), tests, dynamic LDS
+//           bytes, blocks
+// Unarmed, run_plans pays one flag test; no kernel and no result depends on it.
+int64_t pbn_debug_rcot(int op, void* out, int64_t cap) {
+    std::lock_guard<std::mutex> lk(g_rcot_mu);
+    if (op == 0 || op == 1) {
+        g_rcot_rec.clear();
+        g_rcot_log.clear();
+        g_rcot_capture.store(op == 1);
+        return 0;
+    }
+    if (op == 2) {
+        for (int64_t i = 0; out && i < (int64_t)g_rcot_rec.size() && i < cap; ++i) ((double*)out)[i] = g_rcot_rec[(size_t)i];
+        return (int64_t)g_rcot_rec.size();
+    }
+    if (op == 3) {
+        for (int64_t i = 0; out && i < (int64_t)g_rcot_log.size() && i < cap; ++i) ((int64_t*)out)[i] = g_rcot_log[(size_t)i];
+        return (int64_t)g_rcot_log.size();
+    }
+    return -1;
 }
 
 int pbn_rcot_chisq_sum_sf(const double* weights, int n, double q, int method, double* out) {

@@ -134,12 +134,15 @@ def chisq_sum_sf(w, q, method=0):
 
 # ---- the test ------------------------------------------------------------------------------------------------------------------
 def normalize(col):
-    """DataFrame::normalize over the valid values (NaN = null)."""
+    """DataFrame::normalize over the valid values (NaN = null), in pbn_rcot_create's arithmetic: sums left to right (np.cumsum),
+    sd over n - 1, (v - mean) * (1 / sd).  The result is the device's input column bit for bit."""
     col = np.asarray(col, dtype=np.float64).copy()
     ok = ~np.isnan(col)
     v = col[ok]
-    sd = v.std(ddof=1) if len(v) > 1 else 0.0
-    col[ok] = (v - v.mean()) / sd if sd != 0 else 0.0
+    n = len(v)
+    mean = np.cumsum(v)[-1] / n if n else 0.0
+    sd = np.sqrt(np.cumsum((v - mean) * (v - mean))[-1] / (n - 1)) if n > 1 else 0.0
+    col[ok] = (v - mean) * (1 / sd) if sd != 0 else 0.0
     return col
 
 
@@ -173,12 +176,13 @@ def sigma_window(table, names, valid_in=()):
     return 1.0 if med == 0 else med
 
 
-def rcot_from_detail(table, det, nxy, nz, perm=None):
+def rcot_from_detail(table, det, nxy, nz, perm=None, rows=None):
     """table: dict name -> raw column (NaN = null).  Returns (sta, positive eigenvalues (ascending), p, method).  perm: rows
-    permuted with this seed (the same test, another summation order)."""
+    permuted with this seed (the same test, another summation order).  rows: the test's rows (a boolean mask or indices), for a
+    row set other than the rows valid in x, y and the Z columns used."""
     names = [det["x"], det["y"]] + list(det["z"])
     cols = np.column_stack([normalize(table[n]) for n in names])
-    cols = cols[~np.isnan(cols).any(axis=1)]
+    cols = cols[~np.isnan(cols).any(axis=1)] if rows is None else cols[rows]
     if perm is not None:
         cols = cols[np.random.default_rng(perm).permutation(len(cols))]
     n = len(cols)
@@ -204,3 +208,40 @@ def rcot_from_detail(table, det, nxy, nz, perm=None):
     ev = np.sort(ev[ev > 0])
     p, used = chisq_sum_sf(ev, sta, 1 if (k and nz == 1) else 0)
     return sta, ev, p, used
+
+
+def check_parity(df, z, nxy=5, nz=100, seed=11, rows=None):
+    """pbn.RCoT(df, nxy, nz, seed).detail("x", "y", z) against the restatement: sigma, sta, the eigenvalues, the p-value, the
+    method and n_valid.  rows: the rows the test must run on, when they are not the rows valid in x, y and the Z columns used."""
+    import pybnesian_amd as pbn
+
+    t = pbn.RCoT(df, nxy, nz, seed=seed)
+    det = t.detail("x", "y", z)
+    table = {c: df[c].to_numpy(dtype=np.float64) for c in df.columns}
+    if det["trivial"]:
+        return det
+    # sigma from the table itself (the window: the first 500 rows valid in all the test's variables; even-count median; 0 -> 1)
+    zs = [] if z is None else ([z] if isinstance(z, str) else list(z))
+    valid_in = [det["x"], det["y"]] + zs
+    want_sigma = [sigma_window(table, [det["x"]], valid_in), sigma_window(table, [det["y"]], valid_in)]
+    if det["z"]:
+        want_sigma.append(sigma_window(table, det["z"], valid_in))
+    assert np.allclose(det["sigma"][:len(want_sigma)], want_sigma, rtol=1e-12, atol=0), (det["sigma"], want_sigma)
+    # the spread between restatements that differ only in summation order (rows permuted) is the scale of what the
+    # ridge-regularised projection amplifies: the device is held to a multiple of it
+    a = rcot_from_detail(table, det, nxy, nz, rows=rows)
+    alts = [rcot_from_detail(table, det, nxy, nz, perm=1, rows=rows), rcot_from_detail(table, det, nxy, nz, perm=2, rows=rows)]
+    spread_sta = max(abs(a[0] - o[0]) for o in alts)
+    assert abs(det["sta"] - a[0]) <= 20 * spread_sta + 1e-8 * abs(a[0]) + 1e-10, (det["sta"], a[0], spread_sta)
+    big = lambda ev: ev[ev > 1e-9 * np.max(a[1])]   # (eigenvalues at rounding level may change sign between orders)
+    assert len(big(det["eigenvalues"])) == len(big(a[1]))
+    spread_ev = max(np.max(np.abs(big(a[1]) - big(o[1]))) for o in alts)
+    assert np.max(np.abs(big(det["eigenvalues"]) - big(a[1]))) <= 20 * spread_ev + 1e-9 * np.max(a[1])
+    spread_p = max(abs(a[2] - o[2]) for o in alts)
+    assert abs(det["pvalue"] - a[2]) <= 20 * spread_p + 1e-7, (det["pvalue"], a[2], spread_p)
+    assert det["method"] == a[3]
+    if rows is None:
+        assert det["n_valid"] == int(np.sum(~np.isnan(np.column_stack([table[c] for c in [det["x"], det["y"]] + det["z"]])).any(axis=1)))
+    else:
+        assert det["n_valid"] == len(np.arange(len(df))[rows])
+    return det

@@ -6,7 +6,8 @@ import numpy as np
 import pandas as pd
 import pytest
 
-from rcot_restatement import rcot_from_detail, sigma_window
+from rcot_restatement import check_parity as _check_parity
+from rcot_restatement import sigma_window
 
 pytestmark = pytest.mark.gpu
 
@@ -21,38 +22,6 @@ def _table(n, k, seed, nonlinear=True):
     for i in range(k):
         d[f"z{i}"] = z[:, i]
     return pd.DataFrame(d)
-
-
-def _check_parity(df, z, nxy=5, nz=100, seed=11):
-    import pybnesian_amd as pbn
-
-    t = pbn.RCoT(df, nxy, nz, seed=seed)
-    det = t.detail("x", "y", z)
-    table = {c: df[c].to_numpy(dtype=np.float64) for c in df.columns}
-    if det["trivial"]:
-        return det
-    # sigma from the table itself (the window: the first 500 rows valid in all the test's variables; even-count median; 0 -> 1)
-    zs = [] if z is None else ([z] if isinstance(z, str) else list(z))
-    valid_in = [det["x"], det["y"]] + zs
-    want_sigma = [sigma_window(table, [det["x"]], valid_in), sigma_window(table, [det["y"]], valid_in)]
-    if det["z"]:
-        want_sigma.append(sigma_window(table, det["z"], valid_in))
-    assert np.allclose(det["sigma"][:len(want_sigma)], want_sigma, rtol=1e-12, atol=0), (det["sigma"], want_sigma)
-    # the spread between restatements that differ only in summation order (rows permuted) is the scale of what the
-    # ridge-regularised projection amplifies: the device is held to a multiple of it
-    a = rcot_from_detail(table, det, nxy, nz)
-    alts = [rcot_from_detail(table, det, nxy, nz, perm=1), rcot_from_detail(table, det, nxy, nz, perm=2)]
-    spread_sta = max(abs(a[0] - o[0]) for o in alts)
-    assert abs(det["sta"] - a[0]) <= 20 * spread_sta + 1e-8 * abs(a[0]) + 1e-10, (det["sta"], a[0], spread_sta)
-    big = lambda ev: ev[ev > 1e-9 * np.max(a[1])]   # (eigenvalues at rounding level may change sign between orders)
-    assert len(big(det["eigenvalues"])) == len(big(a[1]))
-    spread_ev = max(np.max(np.abs(big(a[1]) - big(o[1]))) for o in alts)
-    assert np.max(np.abs(big(det["eigenvalues"]) - big(a[1]))) <= 20 * spread_ev + 1e-9 * np.max(a[1])
-    spread_p = max(abs(a[2] - o[2]) for o in alts)
-    assert abs(det["pvalue"] - a[2]) <= 20 * spread_p + 1e-7, (det["pvalue"], a[2], spread_p)
-    assert det["method"] == a[3]
-    assert det["n_valid"] == int(np.sum(~np.isnan(np.column_stack([table[c] for c in [det["x"], det["y"]] + det["z"]])).any(axis=1)))
-    return det
 
 
 @pytest.mark.parametrize("n,k", [(50, 0), (50, 1), (2000, 0), (20000, 0), (20000, 1), (20000, 2), (20000, 4)])
