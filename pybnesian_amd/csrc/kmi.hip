@@ -330,6 +330,11 @@ __global__ __launch_bounds__(KMI_TILE) void kmi_neighbors_kernel(NbrArgs a) {
         for (int q = 0; q < a.m; ++q) a.out[i * a.m + q] = who[q];
 }
 
+// pbn_debug_kmi (test aid, not part of the C ABI header; see its definition): what Kmi::evaluate and Kmi::pvalue record while it is armed
+std::atomic<bool> g_kmi_capture{false};
+std::mutex g_kmi_mu;
+std::vector<int64_t> g_kmi_rec;
+
 struct IndexLess {   // kdtree::IndexComparator
     const float* v;
     bool operator()(size_t a, size_t b) const { return v[a] < v[b]; }
@@ -344,8 +349,11 @@ struct Kmi {
         return h->harmonic[(size_t)n - 1] - EULER;
     }
 
+    int form[3] = {0, 0, 0};   // the kernels of the last evaluation, for pbn_debug_kmi: all-pairs {0, D, TILE}, window {1, O, 256}
+
     template <bool EPS, int D, int TILE>
     void launch_dt(const KmiArgs& a) {
+        form[0] = 0; form[1] = D; form[2] = TILE;
         const dim3 grid((unsigned)ceil_div(a.n, TILE), (unsigned)a.slices), block(TILE);
         const size_t lds = (size_t)(a.k + 1) * TILE * sizeof(float);
         if (EPS) {
@@ -370,6 +378,29 @@ struct Kmi {
             case 6: launch_d<EPS, 6>(a); break;
             default: launch_d<EPS, 0>(a); break;
         }
+    }
+
+    template <int O>
+    void launch_window(const KmiWinArgs& w) {
+        form[0] = 1; form[1] = O; form[2] = 256;
+        const size_t lds = (size_t)(w.k + 1) * 256 * sizeof(float);
+        hipLaunchKernelGGL(kmi_window_kernel<O>, dim3((unsigned)ceil_div(w.n, 256)), dim3(256), lds, h->ctx->stream, w);
+    }
+
+    // pbn_debug_kmi, record of one evaluation (the layout is at its definition).  cnt is empty with two columns
+    void debug_record(const std::vector<int>& vars, const float* x_host, int slices, const std::vector<int32_t>& eps,
+                      const std::vector<int32_t>& cnt) const {
+        const int64_t N = h->N;
+        std::vector<int64_t> r{1, form[0], form[1], form[2], slices, (int64_t)vars.size(), N, h->k, x_host ? 1 : 0};
+        r.insert(r.end(), vars.begin(), vars.end());
+        for (size_t d = 0; d < vars.size(); ++d) {
+            const float* col = (d == 0 && x_host) ? x_host : h->ranks[vars[d]].data();
+            r.insert(r.end(), col, col + N);
+        }
+        r.insert(r.end(), eps.begin(), eps.end());
+        r.insert(r.end(), cnt.begin(), cnt.end());
+        std::lock_guard<std::mutex> lk(g_kmi_mu);
+        g_kmi_rec.insert(g_kmi_rec.end(), r.begin(), r.end());
     }
 
     // MI of columns vars = [x, y, z...]; a permuted sample passes its x ranks (device copy + the host original)
@@ -404,12 +435,11 @@ struct Kmi {
                 w.sc[o++] = dst;
             }
             w.others = o;
-            const size_t lds = (size_t)(h->k + 1) * 256 * sizeof(float);
             switch (o) {
-                case 1: hipLaunchKernelGGL(kmi_window_kernel<1>, grid, block, lds, ctx->stream, w); break;
-                case 2: hipLaunchKernelGGL(kmi_window_kernel<2>, grid, block, lds, ctx->stream, w); break;
-                case 3: hipLaunchKernelGGL(kmi_window_kernel<3>, grid, block, lds, ctx->stream, w); break;
-                default: hipLaunchKernelGGL(kmi_window_kernel<0>, grid, block, lds, ctx->stream, w); break;
+                case 1: launch_window<1>(w); break;
+                case 2: launch_window<2>(w); break;
+                case 3: launch_window<3>(w); break;
+                default: launch_window<0>(w); break;
             }
             HIP_CHECK(hipGetLastError());
         } else {
@@ -421,11 +451,13 @@ struct Kmi {
             launch<true>(a);
         }
         ++h->evaluations;
+        const bool dbg = g_kmi_capture.load(std::memory_order_relaxed);
         std::vector<int32_t> eps((size_t)N), cnt;
         double res = 0;
         if (a.dims == 2) {   // mi_pair (mutual_information.cpp:9-43): marginal counts have a closed form on ranks
             HIP_CHECK(hipMemcpyAsync(eps.data(), h->d_eps.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
             HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            if (dbg) debug_record(vars, x_override ? x_host : nullptr, a.slices, eps, cnt);
             const float* x = x_override ? x_host : h->ranks[vars[0]].data();
             const float* y = h->ranks[vars[1]].data();
             const int rows = (int)N;
@@ -444,6 +476,10 @@ struct Kmi {
         cnt.resize((size_t)3 * N);
         HIP_CHECK(hipMemcpyAsync(cnt.data(), h->d_cnt.p, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (dbg) {
+            HIP_CHECK(hipMemcpy(eps.data(), h->d_eps.p, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost));
+            debug_record(vars, x_override ? x_host : nullptr, a.slices, eps, cnt);
+        }
         for (int64_t i = 0; i < N; ++i)   // mi_triple / mi_general (mutual_information.cpp:107-114,136-143)
             res += digamma_int(cnt[2 * N + i]) - digamma_int(cnt[i]) - digamma_int(cnt[N + i]);
         res /= (double)N;
@@ -487,6 +523,13 @@ struct Kmi {
         std::vector<int32_t> neighbors((size_t)N * m);   // column i = the m neighbours of row i (MatrixXi(m, N), column-major)
         HIP_CHECK(hipMemcpyAsync(neighbors.data(), h->d_nbr.p, neighbors.size() * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (g_kmi_capture.load(std::memory_order_relaxed)) {
+            std::vector<int64_t> r{2, na.dims, N, m};
+            r.insert(r.end(), vars.begin() + 2, vars.end());
+            r.insert(r.end(), neighbors.begin(), neighbors.end());
+            std::lock_guard<std::mutex> lk(g_kmi_mu);
+            g_kmi_rec.insert(g_kmi_rec.end(), r.begin(), r.end());
+        }
         const float* original_x = h->ranks[vars[0]].data();
         std::vector<size_t> order((size_t)N), sorted_indices((size_t)N);
         std::iota(order.begin(), order.end(), 0);
@@ -508,7 +551,7 @@ struct Kmi {
                 if (evaluate(vars, h->d_x.p, v.data()) >= original) ++count_greater;
             } catch (...) { failed = std::current_exception(); }
         };
-        const bool pipelined = N >= 65536 && knob_int("PBN_KMI_PIPELINE", 1) != 0;
+        const bool pipelined = N >= knob_int("PBN_KMI_PIPELINE_MIN_ROWS", 65536) && knob_int("PBN_KMI_PIPELINE", 1) != 0;
         for (int s = 0; s < h->samples; ++s) {
             std::vector<float>& shuffled = stage[s & 1];   // (the worker reads the other one)
             std::shuffle(order.begin(), order.end(), rng);
@@ -621,6 +664,30 @@ double pbn_kmi_pvalue(void* user, int v1, int v2, int n_cond, const int* cond) {
         result = e.pvalue(vars);
     });
     return result;
+}
+
+// pbn_debug_kmi (test aid, not part of the C ABI header): op 1 arms the capture and clears it, op 0 disarms and clears, op 2 copies up to
+// `cap` int64 of the records into out and returns how many are held.  While armed, every Kmi::evaluate appends a record of kind 1 after
+// its kernels and every p-value with conditioning variables one of kind 2 after kmi_neighbors_kernel, in call order:
+//   1, window (0 = all-pairs kernels, 1 = sorted-window walk), D of kmi_eps_kernel / kmi_count_kernel (all-pairs) or O of
+//      kmi_window_kernel (window), TILE (rows per block), slices (all-pairs; 0 in the window form), dims, N, k, permuted (1: column 0 is
+//      a permuted sample's x), the dims variable indices [x, y, z...], the host ranks of these columns (dims x N; the permuted x ranks
+//      as uploaded), eps (N) and - with conditioning variables - n_xz, n_yz, n_z (3 x N) as copied back from the device
+//   2, the number of conditioning columns nz, N, m, the nz variable indices, the N x m neighbour table copied from the device (row i =
+//      the m neighbours of row i, nearest first, before the host shuffles them)
+// Unarmed, an evaluation pays one flag test (and three stores of the kernel form); no kernel and no result depends on it.
+int64_t pbn_debug_kmi(int op, int64_t* out, int64_t cap) {
+    std::lock_guard<std::mutex> lk(g_kmi_mu);
+    if (op == 0 || op == 1) {
+        g_kmi_rec.clear();
+        g_kmi_capture.store(op == 1);
+        return 0;
+    }
+    if (op == 2) {
+        for (int64_t i = 0; out && i < (int64_t)g_kmi_rec.size() && i < cap; ++i) out[i] = g_kmi_rec[(size_t)i];
+        return (int64_t)g_kmi_rec.size();
+    }
+    return -1;
 }
 
 }  // extern "C"
