@@ -774,9 +774,12 @@ __device__ __forceinline__ unsigned long long prune_visit_mask(BP tile_box, int 
 // The same test against ONE 16-query group's own box and bound (fp64 pruned sweeps): a wave owns QG groups, consecutive in Morton
 // order, and the box of all of them is up to twice as wide per axis as a group's own - at 3-4 dimensions, where a wave's box is
 // as wide as the kernel's support, a third of the (tile, group) pairs of a visited tile lie beyond the group's own support.  The
-// boxes are re-read per group (uniform addresses: scalar loads; the tile's box from L1) so that no box stays in registers.
-template <int PD, typename BP>
-__device__ __forceinline__ unsigned long long prune_group_mask(BP tile_box, BP qbox, int pd, int64_t tb, int64_t t1, double thr, int lane) {
+// boxes are re-read per group so that no box stays in registers across the walk: the tile's box from L1 / L2 and the group's own box - a uniform
+// address, but a VECTOR load per lane all the same (the kernel holds atomics and stores, so the compiler does not prove the memory unclobbered and
+// emits no scalar load) - or, in the d = 8 shape, from the copy the wave keeps in LDS (kde_sweep_body: QLDS).  `pd` is a compile-time constant
+// in that shape (PDFIX): the loop below is then flat, every load of the test issued before the first wait.
+template <int PD, typename BP, typename QP>
+__device__ __forceinline__ unsigned long long prune_group_mask(BP tile_box, QP qbox, int pd, int64_t tb, int64_t t1, double thr, int lane) {
     const int64_t t = tb + lane;
     bool keep = false;
     if (t < t1) {
@@ -793,6 +796,39 @@ __device__ __forceinline__ unsigned long long prune_group_mask(BP tile_box, BP q
         keep = !(-0.5 * d2 < thr);
     }
     return __ballot(keep);
+}
+
+// ... for ALL of a wave's groups at once (round 9, the d = 8 shape): the tile's box is loaded once and every group's distance is taken from it - one
+// round trip per batch instead of one per (batch, group).  Per group the same operations in the same order as prune_group_mask: the same masks.
+template <int PD, int QG, typename BP, typename QP>
+__device__ __forceinline__ void prune_group_masks_joint(BP tile_box, const QP (&qbox)[QG], int pd, int64_t tb, int64_t t1, const double (&thr)[QG], int lane,
+                                                        unsigned long long (&gm)[QG]) {
+    const int64_t t = tb + lane;
+    bool keep[QG];
+#pragma unroll
+    for (int g = 0; g < QG; ++g) keep[g] = false;
+    if (t < t1) {
+        const BP bx = tile_box + t * 2 * pd;
+        double d2[QG];
+#pragma unroll
+        for (int g = 0; g < QG; ++g) d2[g] = 0.0;
+#pragma unroll
+        for (int k = 0; k < PD; ++k)
+            if (k < pd) {
+                const double lo = bx[k], hi = bx[pd + k];
+#pragma unroll
+                for (int g = 0; g < QG; ++g) {
+                    const double g1 = lo - qbox[g][pd + k], g2 = qbox[g][k] - hi;
+                    double gg = g1 > g2 ? g1 : g2;
+                    gg = gg > 0.0 ? gg : 0.0;
+                    d2[g] = __builtin_fma(gg, gg, d2[g]);
+                }
+            }
+#pragma unroll
+        for (int g = 0; g < QG; ++g) keep[g] = !(-0.5 * d2[g] < thr[g]);
+    }
+#pragma unroll
+    for (int g = 0; g < QG; ++g) gm[g] = __ballot(keep[g]);
 }
 
 // ... with a second, nearer threshold: `near` = the tiles that hold a term above thr_near (the others of the returned mask are the
@@ -821,8 +857,8 @@ __device__ __forceinline__ unsigned long long prune_group_mask2(BP tile_box, BP 
 }
 
 // One uniform test per (64-tile batch, query group): does the batch's box come within the drop threshold of the group's box at all?
-template <int PD, typename BP>
-__device__ __forceinline__ bool batch_in_reach(BP bb, BP qbox, int pd, double thr) {
+template <int PD, typename BP, typename QP>
+__device__ __forceinline__ bool batch_in_reach(BP bb, QP qbox, int pd, double thr) {
     double d2 = 0.0;
 #pragma unroll
     for (int k = 0; k < PD; ++k)
@@ -850,6 +886,31 @@ __device__ __forceinline__ bool batch_all_near(BP bb, BP qbox, int pd) {
             f2 = __builtin_fma(h, h, f2);
         }
     return f2 <= PBN_OPEN_FAR2;
+}
+
+// GUARD of the pruned sum-only d = 8 sweep (round 9; norms as WEIGHTS, boxes over all eight rotated dimensions).  The accumulator of a (row, query)
+// pair holds x = z_t.z_q - 1/2|z_q|^2 - m_q + bias = 1/2|z_t|^2 - 1/2|z_t - z_q|^2 - m_q + bias (the norm rides in the weight), so with z_t inside
+// the batch's box, z_q inside the group's box and m_lo <= m_q <= m_hi over the group's 16 queries
+//   x <= 1/2 max|z_t|^2 - m_lo + bias,   max|z_t|^2 <= n2 = sum_k max(lo_k^2, hi_k^2) over the batch's box (the rotation keeps norms),
+//   x >= -1/2 f2 - m_hi + bias,           f2 = the LARGEST squared distance between the two boxes (batch_all_near's).
+// A batch is bare for the group when 1/2 n2 <= up = 1021 - bias + m_lo and 1/2 f2 <= dn = 1021 + bias - m_hi: every exponent inside +-1021, where
+// exp2_magic and its clamped form are the same function (the clamp acts beyond +-1023; one unit covers the rounding of these sums).  False for a
+// batch box with a NaN side; the caller keeps the group's side of the proof (finite queries and offsets, not the padded query tile) and the batch
+// with the table's padded last tile out.
+template <int PD, typename BP, typename QP>
+__device__ __forceinline__ bool batch_bare_wmul(BP bb, QP qbox, int pd, double up, double dn) {
+    double n2 = 0.0, f2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < PD; ++k)
+        if (k < pd) {
+            const double lo = bb[k], hi = bb[pd + k];
+            const double l2 = lo * lo, h2 = hi * hi;
+            n2 += (l2 > h2 || l2 != l2) ? l2 : h2;
+            const double d1 = hi - qbox[k], d2 = qbox[pd + k] - lo;
+            const double d = (d1 > d2 || d1 != d1) ? d1 : d2;
+            f2 = __builtin_fma(d, d, f2);
+        }
+    return 0.5 * n2 <= up && 0.5 * f2 <= dn;
 }
 
 // ... and with the MOMENT pass (round 5): `mom` = the (tile, group) pairs whose contribution is taken from the tile's moments instead
@@ -928,7 +989,10 @@ __device__ __forceinline__ void pruned_block(const SweepArgs& a, int groups_per_
 // MOM (round 5): the moment pass runs beside this sweep (grouped fp64 sum-only launches of one- and two-variable units) - the sweep skips the
 // pairs the pass takes (prune_group_mask3).  A template parameter, not a run-time branch:
 // the kernel sits at its register limit and the extra paths cost the plain sweep 25 % when compiled in.
-template <typename T, int KS, bool COND, int QG, bool FOLD, bool PRUNE, bool WMUL, bool EF32 = false, bool MOM = false, int PDMAX = PBN_PRUNE_PD>
+// PDFIX (round 9): the number of box dimensions as a compile-time fact (0: SweepArgs::pdims at run time).  With a run-time `pd` every box test
+// is a chain of `if (k < pd)` blocks, each with its own loads and its own wait: eight dependent round trips per mask at d = 8.  With pd = PDFIX
+// the loops unroll flat - all box loads of a test are issued before the first wait.  The launch picks the form (launch_sweep_tf: kde_sweep_pruned_d8_kernel where pdims == 8).
+template <typename T, int KS, bool COND, int QG, bool FOLD, bool PRUNE, bool WMUL, bool EF32 = false, bool MOM = false, int PDMAX = PBN_PRUNE_PD, int PDFIX = 0>
 __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigned bid) {
     static_assert(!WMUL || (!FOLD && !COND), "WMUL: plain sweeps without a free K slot only");
     using V = typename Tr<T>::vec4;
@@ -987,9 +1051,49 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
     // ---- tile pruning: box of this wave's queries and the exponent below which a training tile cannot matter -------
     // boxes of up to 8 dimensions in the plain fp64 shapes (d = 7, 8: kde_prune_rotates), of up to 5 in the conditional and grouped ones (their spills)
     constexpr int PDW = COND ? PBN_PRUNE_PD_NARROW : PDMAX;
+    static_assert(PDFIX == 0 || (PRUNE && PDFIX <= PDW), "PDFIX: a pruned shape's own number of box dimensions");
+    // pruned plain fp64 sweeps: visit masks per query group (GMASK), bit `bit` of gm[g] = group g needs this tile
+    constexpr bool GMASK = PRUNE && !COND && sizeof(T) == 8;
+    // The GMASK shapes test every 16-query group against its OWN box (prune_group_mask*) and every 64-tile batch against the batch boxes: the
+    // shipped library provides both with every launch (launch_sweep_tf and launch_sweep_grouped refuse a launch without them), so they are
+    // compile-time facts here and the box of the whole WAVE - 2 x PDW + 1 doubles, 34 VGPRs at eight dimensions, alive across the whole walk
+    // only to feed the fallback prune_visit_mask - is not part of these kernels.  Builds with -DPBN_EXPERIMENTS keep the run-time choice
+    // (PBN_PRUNE_GROUP_MASKS / PBN_GROUP_BATCH_BOXES = 0: tools/gmask_probe.sh).
+#ifdef PBN_EXPERIMENTS
+    constexpr bool WBOX = PRUNE;
+    const bool gmasks = GMASK && (MOM || a.group_masks), bboxes = gmasks && a.batch_box;
+#else
+    constexpr bool WBOX = PRUNE && !GMASK;
+    constexpr bool gmasks = GMASK, bboxes = GMASK;
+#endif
     double wlo[PDW] = {}, whi[PDW] = {}, wthr = 0;
-    const int pd = PRUNE ? a.pdims : 0;
-    if (PRUNE) {
+    const int pd = PRUNE ? (PDFIX ? PDFIX : a.pdims) : 0;
+    // QLDS (round 9, the PDFIX shape): the boxes of the wave's own groups and their drop thresholds - the same 2 x pd + 1 doubles for every test of
+    // the walk, at a uniform address - are copied to LDS once (one wave per workgroup: no barrier) and read from there: the box tests' vector-memory loads are the tile
+    // or batch boxes alone, and the groups' sides arrive on the LDS counter without holding 2 x pd x QG doubles in registers across a wait
+    constexpr bool QLDS = GMASK && PDFIX != 0;
+    __shared__ double qbs[QLDS ? QG * (2 * PDW + 1) : 1];
+    if constexpr (QLDS) {
+        static_assert(QG * 2 * PDW + QG <= 64, "one lane per box coordinate and threshold");
+        if (lane < QG * 2 * PDFIX) {
+            const int g = lane / (2 * PDFIX);
+            const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+            qbs[lane] = QBp[qt * 2 * PDFIX + (lane - g * 2 * PDFIX)];
+        } else if (lane < QG * 2 * PDFIX + QG) {
+            const int g = lane - QG * 2 * PDFIX;
+            const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+            qbs[lane] = QTp[qt] - a.prune_margin;
+        }
+    }
+    auto thr_of = [&](int g, int64_t qt) -> double {   // group g's drop threshold: its sum bound less the margin
+        if constexpr (QLDS) { (void)qt; return qbs[QG * 2 * PDFIX + g]; }
+        else { (void)g; return QTp[qt] - a.prune_margin; }
+    };
+    auto qbox_of = [&](int g, int64_t qt) {   // group g's box (query tile qt)
+        if constexpr (QLDS) { (void)qt; return (const double*)&qbs[g * 2 * PDFIX]; }
+        else { (void)g; return QBp + qt * 2 * pd; }
+    };
+    if constexpr (WBOX) {
         wthr = INFINITY;
 #pragma unroll
         for (int k = 0; k < PDW; ++k) { wlo[k] = INFINITY; whi[k] = -INFINITY; }
@@ -1081,8 +1185,6 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
         if (!FOLD) n = *(const PBN_GLOBAL V*)((WMUL ? Wp : Np) + t * 16 + lg * 4);
         if (COND) x = Xp[t * 64 + lane];
     };
-    // pruned plain fp64 sweeps: visit masks per query group (GMASK), bit `bit` of gm[g] = group g needs this tile
-    constexpr bool GMASK = PRUNE && !COND && sizeof(T) == 8;
     unsigned long long gm[QG];
 #pragma unroll
     for (int g = 0; g < QG; ++g) gm[g] = ~0ull;
@@ -1108,6 +1210,14 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
     // the visit masks out of the SGPRs into vector registers and lane-masked branches: 25 % of the kernel's time)
     auto gate_of = [&](int g) -> bool {
         return __builtin_amdgcn_readfirstlane(__all(a.box_full && qt0 + g < a.nqtiles - 1 && ny[g] == ny[g] && m[g] >= (T)-890 && m[g] <= (T)16)) != 0;
+    };
+    // GUARDW (round 9): the same for the d = 8 shape with the norms as weights and pd at compile time - batch_bare_wmul has the proof.  Taken per
+    // super-batch from the offsets as they stand, like GUARDP; a checked redo is the only thing that moves an offset, and it closes the rest of
+    // its super-batch (do_batch returns it), so no batch runs bare on a bound taken from older offsets.
+    constexpr bool GUARDW = MAGIC && GMASK && WMUL && KS == 2 && PDFIX != 0 && PBN_MAGIC_GUARD;
+    auto gate_w = [&](int g) -> bool {
+        const T am = m[g] < (T)0 ? -m[g] : m[g];
+        return __builtin_amdgcn_readfirstlane(__all(a.box_full && qt0 + g < a.nqtiles - 1 && ny[g] == ny[g] && am < (T)0x1p50)) != 0;
     };
     auto process_tile = [&](const int64_t t, const T (&af)[KS], const V& nx, const T ax, const int bit) {
 #pragma unroll
@@ -1225,16 +1335,35 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
         };
         // fp64 plain sweeps take a batch blind first (the offsets start from the prepass bounds: an overflow needs a term 896
         // exponent units above its query's bound) and redo it with the checked loop from the saved sums if a sum went bad
-        constexpr bool FASTP = PBN_SWEEP_UNCHECKED && !COND && sizeof(T) == 8 && (FOLD || KS == 1);   // the shapes that stay <= 168 VGPRs
+        // (WMUL: the weights ride in the FMA chain that runs into the running sum, as in the unpruned sweep; a NaN weight - rows beyond
+        // -1/2|z|^2 = -1000 - and 2^x' = inf or NaN from a huge z_t.z_q both leave the batch's sum NaN or infinite, and the redo takes the batch
+        // through process_tile, whose bad tiles add the norms back and take the classic exponents)
+        constexpr bool FASTP = PBN_SWEEP_UNCHECKED && !COND && sizeof(T) == 8 && (FOLD || WMUL || KS == 1);   // the shapes that stay <= 168 VGPRs
         if (a.count_redo && lane == 0) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
         // Two levels: a SUPER-BATCH of 64 batches (4096 tiles) is classified first, lane = batch, against the batches' own boxes (grouped
         // sweeps: GSweepUnit::batch_box) - one round trip to L2 for 64 batches instead of one per batch, which is what the walk over a
         // split's tiles costs where most batches hold nothing for the wave (the test below is latency, not arithmetic).
-        auto do_batch = [&](const int64_t tb, const unsigned gsel, const bool bare) {
-            unsigned long long mask;
+        constexpr bool JOINT = GMASK && !FARP && PDFIX != 0;   // prune_group_masks_joint
+        auto do_batch = [&](const int64_t tb, const unsigned gsel, const bool bare) -> bool {   // true: the batch was redone checked
+            unsigned long long mask = 0;
+            // (QLDS: the boxes are read from LDS where they are used - without this compiler barrier the reads are hoisted out of the walk and the
+            // boxes of both groups, 2 x pd x QG doubles, live in vector registers from the first batch to the last)
+            if constexpr (QLDS) asm volatile("" ::: "memory");
             if constexpr (GMASK) {
                 mask = 0;
-                if (MOM || a.group_masks) {
+                if (JOINT && gmasks && gsel == (1u << QG) - 1u) {   // in reach of every group of the wave: one pass over the tile boxes
+                    decltype(qbox_of(0, 0)) qb[QG];
+                    double thr[QG];
+#pragma unroll
+                    for (int g = 0; g < QG; ++g) {
+                        const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+                        qb[g] = qbox_of(g, qt);
+                        thr[g] = thr_of(g, qt);
+                    }
+                    prune_group_masks_joint<PDW, QG>(TBp, qb, pd, tb, t1, thr, lane, gm);
+#pragma unroll
+                    for (int g = 0; g < QG; ++g) mask |= gm[g];
+                } else if (gmasks) {
 #pragma unroll
                     for (int g = 0; g < QG; ++g) {
                         const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
@@ -1257,11 +1386,11 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                                 gn[g] = ~0ull;
                             }
                         } else {
-                            gm[g] = prune_group_mask<PDW>(TBp, QBp + qt * 2 * pd, pd, tb, t1, QTp[qt] - a.prune_margin, lane);
+                            gm[g] = prune_group_mask<PDW>(TBp, qbox_of(g, qt), pd, tb, t1, thr_of(g, qt), lane);
                         }
                         mask |= gm[g];
                     }
-                } else {
+                } else if constexpr (WBOX) {
                     mask = prune_visit_mask(TBp, pd, tb, t1, wlo, whi, wthr, lane);
 #pragma unroll
                     for (int g = 0; g < QG; ++g) gm[g] = mask;
@@ -1270,10 +1399,10 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                         for (int g = 0; g < QG; ++g) gn[g] = ~0ull;
                     }
                 }
-            } else {
+            } else if constexpr (WBOX) {
                 mask = prune_visit_mask(TBp, pd, tb, t1, wlo, whi, wthr, lane);
             }
-            if (!mask) return;
+            if (!mask) return false;
             if (a.count_redo && lane == 0) {
                 unsigned long long v = 0;
 #pragma unroll
@@ -1288,7 +1417,7 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                 // the last query tile of a unit, query groups whose offsets lie beyond -890) the SAME loop with it: the same instructions but one,
                 // the same order of additions, the far tiles' fp32 tail in both - a batch's sum does not depend on whether it was proven
                 // (PBN_MAGIC_GUARD=0 takes every batch through the second: bit-identical scores, tests/test_magic_exp2_gpu.py)
-                if (GUARDP && bare) run_batch(tb, mask, std::integral_constant<int, 2>{});
+                if ((GUARDP || GUARDW) && bare) run_batch(tb, mask, std::integral_constant<int, 2>{});
                 else run_batch(tb, mask, std::integral_constant<int, 1>{});
                 if constexpr (FARP) {
 #pragma unroll
@@ -1304,28 +1433,45 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                     for (int g = 0; g < QG; ++g) sum[g] = saved[g];
                     run_batch(tb, mask, std::integral_constant<int, 0>{});
                 }
+                return redo;
             } else {
                 run_batch(tb, mask, std::integral_constant<int, 0>{});
+                return false;
             }
         };
         for (int64_t sb = t0; sb < t1; sb += 4096) {
             const int64_t bt = sb + 64 * lane;   // my batch's first tile
+            if constexpr (QLDS) asm volatile("" ::: "memory");
             unsigned long long bm = __ballot(bt < t1), bmg[QG];
-            unsigned long long bopen = (GUARDP && (MOM || a.group_masks) && a.batch_box) ? ~0ull : 0ull;
+            unsigned long long bopen = ((GUARDP || GUARDW) && bboxes) ? ~0ull : 0ull;
 #pragma unroll
             for (int g = 0; g < QG; ++g) bmg[g] = bm;
             if constexpr (GMASK) {
-                if ((MOM || a.group_masks) && a.batch_box) {
+                if (bboxes) {
                     const PBN_GLOBAL double* bb = (const PBN_GLOBAL double*)a.batch_box + ((int64_t)split * a.batches_per_split + ((bt - t0) >> 6)) * 2 * pd;
                     bm = 0;
 #pragma unroll
                     for (int g = 0; g < QG; ++g) {
                         const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
-                        bmg[g] = __ballot(bt < t1 && batch_in_reach<PDW>(bb, QBp + qt * 2 * pd, pd, QTp[qt] - a.prune_margin));
+                        bmg[g] = __ballot(bt < t1 && batch_in_reach<PDW>(bb, qbox_of(g, qt), pd, thr_of(g, qt)));
                         bm |= bmg[g];
                         // open for the wave = proven for every group that reaches the batch (the batch with the table's last tile - padding
                         // rows, whose norm slot is not a distance - never)
                         if constexpr (GUARDP) bopen &= ~bmg[g] | (gate_of(g) ? __ballot(bt + 64 < a.ntiles && batch_all_near<PDW>(bb, QBp + qt * 2 * pd, pd)) : 0ull);
+                        if constexpr (GUARDW) {
+                            unsigned long long ob = 0;
+                            if (gate_w(g)) {
+                                double mlo = (double)m[g], mhi = mlo;   // over the group's 16 queries (the four row-lanes of a column hold the same offset)
+#pragma unroll
+                                for (int o = 1; o < 16; o <<= 1) {
+                                    const double l = __shfl_xor(mlo, o), h = __shfl_xor(mhi, o);
+                                    mlo = l < mlo ? l : mlo;
+                                    mhi = h > mhi ? h : mhi;
+                                }
+                                ob = __ballot(bt + 64 < a.ntiles && batch_bare_wmul<PDW>(bb, qbox_of(g, qt), pd, 1021.0 - (double)Tr<T>::bias() + mlo, 1021.0 + (double)Tr<T>::bias() - mhi));
+                            }
+                            bopen &= ~bmg[g] | ob;
+                        }
                     }
                 }
             }
@@ -1335,7 +1481,8 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                 unsigned gsel = 0;
 #pragma unroll
                 for (int g = 0; g < QG; ++g) gsel |= (unsigned)((bmg[g] >> j) & 1ull) << g;
-                do_batch(sb + 64 * (int64_t)j, gsel, GUARDP && ((bopen >> j) & 1ull));
+                const bool redone = do_batch(sb + 64 * (int64_t)j, gsel, (GUARDP || GUARDW) && ((bopen >> j) & 1ull));
+                if constexpr (GUARDW) { if (redone) bopen = 0; } else (void)redone;
             }
         }
     } else {
@@ -1485,6 +1632,11 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
 template <typename T, int KS, bool COND, int QG, bool FOLD, bool PRUNE, bool WMUL = false, bool EF32 = false>
 __global__ __launch_bounds__(sweep_block_threads(PRUNE), PRUNE ? PBN_F64_PRUNE_WAVES : 2) void kde_sweep_kernel(SweepArgs a) {
     kde_sweep_body<T, KS, COND, QG, FOLD, PRUNE, WMUL, EF32>(a, blockIdx.x);
+}
+// The pruned sum-only sweep of d = 8 models on boxes over all eight rotated dimensions (bench.py's headline):
+// kde_sweep_kernel<double, 2, false, PBN_QG_PRUNE, false, true, true, true> with the number of box dimensions at compile time (PDFIX)
+__global__ __launch_bounds__(sweep_block_threads(true), PBN_F64_PRUNE_WAVES) void kde_sweep_pruned_d8_kernel(SweepArgs a) {
+    kde_sweep_body<double, 2, false, PBN_QG_PRUNE, false, true, true, true, false, PBN_PRUNE_PD, PBN_PRUNE_PD>(a, blockIdx.x);
 }
 
 // Grouped launch (kde_group.hip): the flat grid covers the sweeps of MANY units back to back, unit-major, every unit's share
@@ -3423,9 +3575,15 @@ static void launch_sweep_tf(const SweepArgs& a, int KS, dim3 grid, hipStream_t s
             constexpr int QGP = COND ? PBN_QG_PRUNE_COND : PBN_QG_PRUNE;   // query groups per wave of the pruned kernels
             block = dim3(sweep_block_threads(true));
             grid = dim3((unsigned)(ceil_div(a.nqtiles, QGP) * a.nsplit_grid));   // one wave per workgroup, placed by pruned_block
+#ifndef PBN_EXPERIMENTS
+            // the plain pruned fp64 kernels are compiled for per-group masks and batch boxes (kde_sweep_body: gmasks / bboxes)
+            if (!COND && (!a.group_masks || !a.batch_box)) throw invalid_error("KDE: pruned fp64 sweeps need per-group masks and batch boxes");
+#endif
             if constexpr (!COND && !FOLD) {
                 if (a.wmul && KS <= 2) {   // 4 / 8 marginal dimensions: the pruned shapes without a free K slot
                     if (KS == 1) PBN_LAUNCH_SWEEP(1, false, QGP, false, true, true);
+                    // the sum-only d = 8 sweep on boxes over all eight (rotated) dimensions - the headline shape: pd at compile time (PDFIX)
+                    else if (a.fast && a.pdims == PBN_PRUNE_PD) hipLaunchKernelGGL(kde_sweep_pruned_d8_kernel, grid, block, 0, st, a);
                     else PBN_LAUNCH_SWEEP(2, false, QGP, false, true, true);
                     HIP_CHECK(hipGetLastError());
                     return;
@@ -3642,6 +3800,9 @@ void launch_sweep_grouped(const GSweepArgs& g, int dtype, int KS, hipStream_t st
         return;
     }
     if (dtype != PBN_F64 || KS < 1 || KS > 2 || (g.fold != 0) == (g.wmul != 0)) throw invalid_error("grouped sweeps: fp64 / fp32 on the f16 cores, at most 8 whitened dimensions");
+#ifndef PBN_EXPERIMENTS
+    if (!g.group_masks) throw invalid_error("grouped fp64 sweeps are compiled for per-group masks");   // (kde_sweep_body: gmasks)
+#endif
     constexpr int QGP = PBN_QG_PRUNE;
     if (g.fold) {
         if (g.moments && (KS != 1 || !g.group_masks)) throw invalid_error("grouped sweeps: the moment pass stands beside one- and two-variable units with per-group masks");

@@ -169,6 +169,7 @@ struct SweepArgs {
     const double* qlb;         // [nqtiles * 16] per (sorted) query: lower bound of its largest exponent, -inf = none; nullable
     int nsplit_grid;           // pruned sweeps: number of splits (their grid is one-dimensional; launch_sweep sets this)
     int group_masks;           // pruned plain fp64 sweeps: test every 16-query group against its own box and bound (prune_group_mask)
+                               // (required, like batch_box, by the shipped kernels: a run-time choice only in -DPBN_EXPERIMENTS builds)
     double far_span;           // pruned plain fp64 sum-only sweeps (FOLD shapes): > 0 = tiles whose every term lies more than prune_margin - far_span
                                // below the group's sum bound take the fp32 tail path (kde_sweep_body: FARP); 0 = off
     // Tile moments (round 5; grouped sum-only fp64 sweeps of one or two dimensions, kde_group.hip): tile_rad2[t] = squared radius of tile t
