@@ -427,6 +427,17 @@ int pbn_lincor_from_cov(int n, int64_t rows, const double* cov /* n*n col-major 
 void pbn_lincor_destroy(pbn_lincor* h);
 int pbn_lincor_cov(const pbn_lincor* h, double* cov /* n*n */);
 double pbn_lincor_pvalue(void* user, int v1, int v2, int n_cond, const int* cond);
+/* Many tests per call (pbn_ci_pvalue_batch_fn, user = the handle).  Handles from pbn_lincor_create evaluate conditioning sets of
+ * up to pbn_lincor_batch_max_cond() variables on the device, one test per lane (csrc/lincor_batch.hip), when a call holds at least
+ * the batch threshold of them (per set size); everything else - larger sets, fewer than 32 degrees of freedom, handles from
+ * pbn_lincor_from_cov - loops over pbn_lincor_pvalue's routine on the host.  Device and host p-values agree to rounding; a test whose
+ * block has an eigenvalue near the pseudo-inverse threshold is recomputed on the host before the call returns.  The counters are
+ * cumulative: tests answered by the device, tests looped on the host, device tests recomputed on the host. */
+void pbn_lincor_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond,
+                             double* out);
+int pbn_lincor_batch_stats(const pbn_lincor* h, int64_t* device_tests, int64_t* host_tests, int64_t* host_redone);
+int pbn_lincor_set_batch_threshold(pbn_lincor* h, int64_t min_tests);
+int pbn_lincor_batch_max_cond(void);
 /* Hybrid MutualInformation (learning/independences/hybrid/mutual_information.{hpp,cpp}): conditional-Gaussian MI of
  * mixed discrete / continuous variables and its chi-square p-value.  table = the continuous columns (device, may be
  * NULL), codes[j] = n_rows int32 category indices of discrete column j (HOST), cardinality[j] its categories.
@@ -514,6 +525,34 @@ int pbn_mmpc_cpcs_batched(int n, int n_interface, pbn_ci_pvalue_fn fn, pbn_ci_pv
                           double alpha, int n_arc_whitelist, const int* arc_whitelist, int n_edge_blacklist,
                           const int* edge_blacklist, int n_edge_whitelist, const int* edge_whitelist, int symmetric,
                           int* cpc_off, int* cpc, int64_t* n_tests);
+
+/* PC::estimate / estimate_conditional (learning/algorithms/pc.cpp:25-336, PC-stable; the v-structure search of
+ * learning/algorithms/constraint.hpp:16-353; the Meek rules) over node indices, the last n_interface of the n variables being
+ * interface nodes.  Restriction lists are index pairs as util::validate_restrictions leaves them; the arc whitelist is applied in
+ * the order given.  batch_fn may be NULL (the serial search); with it every skeleton level and the v-structure phase ask for their
+ * mutually independent tests together, and a batched p-value within band * alpha of alpha is evaluated again through fn - graph,
+ * separating sets, their p-values and tests[0] equal the serial search's.  band < 0 takes pbn_pc_band().  name_rank[i]: position of
+ * node i's name among the sorted names (NULL: i) - the reference enumerates subsets of two adjacency sets in name order.
+ * Outputs: arcs / edges as pairs (capacity n (n - 1) pairs each; a bidirected pair is two arcs); the removed edges in sep_pair
+ * (capacity n (n - 1) / 2 pairs) with sep_off (n_sep + 1 offsets) into sep_set (capacity n * n (n - 1) / 2) and sep_pvalue;
+ * tests[3]: [0] = tests the reference's serial search evaluates, [1] = tests evaluated, [2] = batched p-values inside the band that
+ * were evaluated again through fn (counted in [1] as well).  The sep_* outputs may be NULL. */
+double pbn_pc_band(void);
+int pbn_pc_estimate(int n, int n_interface, pbn_ci_pvalue_fn fn, pbn_ci_pvalue_batch_fn batch_fn, void* user, double alpha,
+                    double band, int n_arc_blacklist, const int* arc_blacklist, int n_arc_whitelist, const int* arc_whitelist,
+                    int n_edge_blacklist, const int* edge_blacklist, int n_edge_whitelist, const int* edge_whitelist,
+                    int use_sepsets, double ambiguous_threshold, int allow_bidirected, const int* name_rank, int* n_arcs,
+                    int* arcs, int* n_edges, int* edges, int* n_sep, int* sep_pair, int* sep_off, int* sep_set,
+                    double* sep_pvalue, int64_t* tests);
+/* The second half alone (MMPC::estimate, mmpc.cpp:1042-1068): a given graph -> direct_arc_blacklist -> direct_unshielded_triples
+ * with no separating sets and use_sepsets = true (the threshold-0 search, constraint.hpp:219-222) -> Meek rules. */
+int pbn_pdag_orient(int n, int n_interface, pbn_ci_pvalue_fn fn, pbn_ci_pvalue_batch_fn batch_fn, void* user, double alpha,
+                    double band, int n_in_arcs, const int* in_arcs, int n_in_edges, const int* in_edges, int n_arc_blacklist,
+                    const int* arc_blacklist, int n_arc_whitelist, const int* arc_whitelist, int allow_bidirected,
+                    const int* name_rank, int* n_arcs, int* arcs, int* n_edges, int* edges, int64_t* tests);
+/* MeekRules::rule1 / rule2 / rule3 (constraint.hpp:391-509) on a graph given as lists, edges in their stored orientation. */
+int pbn_meek_rule(int rule, int n, int n_in_arcs, const int* in_arcs, int n_in_edges, const int* in_edges, int* n_arcs, int* arcs,
+                  int* n_edges, int* edges, int* changed);
 
 #ifdef __cplusplus
 }

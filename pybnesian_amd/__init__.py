@@ -24,6 +24,8 @@ from .models import (BayesianNetwork, BayesianNetworkType, FactorType, Condition
 from .dynamic import (DynamicBDe, DynamicBayesianNetworkBase, DynamicKMutualInformation, DynamicRCoT, DynamicCLGNetwork, DynamicDiscreteBN, DynamicHeterogeneousBN, DynamicHomogeneousBN,  # noqa: F401
                       DynamicIndependenceTest, DynamicScore)
 from .models import BayesianNetworkBase, ConditionalBayesianNetworkBase  # noqa: F401
+from .graph import ConditionalPartiallyDirectedGraph, PartiallyDirectedGraph  # noqa: F401
+from .constraint import MMPC, PC, MeekRules  # noqa: F401
 from .scores import (Args, Arguments, BDe, BGe, BIC, CVLikelihood, HoldoutLikelihood, Kwargs, Score, ValidatedLikelihood,  # noqa: F401
                      ValidatedScore)
 
@@ -39,5 +41,6 @@ __all__ = [
     "DynamicHeterogeneousBN", "Dag", "ConditionalDag", "Operator", "ArcOperator", "OperatorSet", "SaveModel", "LinearGaussianParams",
     "DiscreteFactorParams", "MLELinearGaussianCPD", "MLEDiscreteFactor", "BayesianNetworkBase", "ConditionalBayesianNetworkBase",
     "DynamicBayesianNetworkBase", "DynamicScore", "DynamicIndependenceTest", "BDe", "DynamicBDe", "KMutualInformation",
-    "DynamicKMutualInformation", "Assignment", "RCoT", "DynamicRCoT",
+    "DynamicKMutualInformation", "Assignment", "RCoT", "DynamicRCoT", "PC", "MMPC", "MeekRules", "PartiallyDirectedGraph",
+    "ConditionalPartiallyDirectedGraph",
 ]

@@ -113,6 +113,16 @@ SIGNATURES = {
     "pbn_rcot_pvalue_batch": (None, [_vp, _int, _ip, _ip, _ip, _ip, _dp]),
     "pbn_rcot_detail": (_int, [_vp, _int, _int, _int, _ip, C.POINTER(_i64), _dp, _dp, _dp, _ip, _ip, _dp, _dp, _ip, _ip, _dp]),
     "pbn_rcot_chisq_sum_sf": (_int, [_dp, _int, C.c_double, _int, _dp]),
+    "pbn_lincor_pvalue_batch": (None, [_vp, _int, _ip, _ip, _ip, _ip, _dp]),
+    "pbn_lincor_batch_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "pbn_lincor_set_batch_threshold": (_int, [_vp, _i64]),
+    "pbn_lincor_batch_max_cond": (_int, []),
+    "pbn_pc_band": (C.c_double, []),
+    "pbn_pc_estimate": (_int, [_int, _int, _vp, _vp, _vp, C.c_double, C.c_double, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _int, C.c_double, _int, _ip,
+                               _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _dp, C.POINTER(_i64)]),
+    "pbn_pdag_orient": (_int, [_int, _int, _vp, _vp, _vp, C.c_double, C.c_double, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _ip, _ip, _ip, _ip,
+                               C.POINTER(_i64)]),
+    "pbn_meek_rule": (_int, [_int, _int, _int, _ip, _int, _ip, _ip, _ip, _ip, _ip, _ip]),
     "pbn_mmpc_cpcs": (_int, [_int, _vp, _vp, C.c_double, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _ip, C.POINTER(_i64)]),
     "pbn_mmpc_cpcs_conditional": (_int, [_int, _int, _vp, _vp, C.c_double, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _ip, C.POINTER(_i64)]),
     "pbn_mmpc_cpcs_batched": (_int, [_int, _int, _vp, _vp, _vp, C.c_double, _int, _ip, _int, _ip, _int, _ip, _int, _ip, _ip, C.POINTER(_i64)]),

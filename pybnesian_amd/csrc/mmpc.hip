@@ -14,83 +14,18 @@
 #include <unordered_set>
 
 #include "common.hpp"
+#include "lincor.hpp"
 #include "stats_kernels.hpp"
 
 using namespace pbn;
 
 // ---- LinearCorrelation -------------------------------------------------------------------------------------------
-struct pbn_lincor {
-    int n = 0;
-    int64_t rows = 0;
-    std::vector<double> cov;  // n x n
-};
+// (struct pbn_lincor and the Student-t tail shared with the device batch: lincor.hpp)
+using namespace pbn::lincor;
 
 namespace {
 
-constexpr double MACHINE_TOL = 1.4901161193847656e-08;  // util/math_constants.hpp:30
 constexpr int STOP = -1, RECOMPUTE = -2;                // mmpc.cpp:16
-
-// log(Gamma(a + 1/2) / Gamma(a)) without the cancellation of two lgamma() of ~a log a each
-double lgamma_ratio_half(double a) {
-    if (a < 16.0) return std::lgamma(a + 0.5) - std::lgamma(a);
-    const double r = 1.0 / a;
-    // Gamma(a+1/2)/Gamma(a) = sqrt(a) (1 - 1/(8a) + 1/(128a^2) + 5/(1024a^3) - 21/(32768a^4) - 399/(262144a^5) ...)
-    const double s = 1.0 + r * (-1.0 / 8 + r * (1.0 / 128 + r * (5.0 / 1024 + r * (-21.0 / 32768 + r * (-399.0 / 262144 + r * (869.0 / 4194304))))));
-    return 0.5 * std::log(a) + std::log(s);
-}
-
-// Regularised incomplete beta I_x(a, b) by the modified Lentz continued fraction; log_pref = log of x^a (1-x)^b / B(a,b).
-double ibeta_cf(double a, double b, double x) {
-    const double tiny = 1e-300, eps = 1e-16;
-    double c = 1.0, d = 1.0 - (a + b) * x / (a + 1.0);
-    if (std::fabs(d) < tiny) d = tiny;
-    d = 1.0 / d;
-    double h = d;
-    for (int m = 1; m < 100000; ++m) {
-        const double m2 = 2.0 * m;
-        double aa = m * (b - m) * x / ((a + m2 - 1.0) * (a + m2));
-        d = 1.0 + aa * d; if (std::fabs(d) < tiny) d = tiny;
-        c = 1.0 + aa / c; if (std::fabs(c) < tiny) c = tiny;
-        d = 1.0 / d;
-        h *= d * c;
-        aa = -(a + m) * (a + b + m) * x / ((a + m2) * (a + m2 + 1.0));
-        d = 1.0 + aa * d; if (std::fabs(d) < tiny) d = tiny;
-        c = 1.0 + aa / c; if (std::fabs(c) < tiny) c = tiny;
-        d = 1.0 / d;
-        const double del = d * c;
-        h *= del;
-        if (std::fabs(del - 1.0) < eps) break;
-    }
-    return h;
-}
-
-// 2 * P(T_df > |t|) = I_{df/(df+t^2)}(df/2, 1/2)   (linearcorrelation.cpp:9-13 with boost's students_t)
-double two_sided_t_pvalue(double t, double df) {
-    // Boost's students_t rejects df <= 0 (domain_error): fewer rows than variables + 2
-    if (std::isnan(t) || !(df > 0)) return std::numeric_limits<double>::quiet_NaN();
-    if (std::isinf(t)) return 0.0;
-    const double t2 = t * t;
-    if (t2 == 0.0) return 1.0;
-    const double a = 0.5 * df, b = 0.5;
-    const double x = df / (df + t2), y = t2 / (df + t2);  // y = 1 - x without cancellation
-    // log B(a, 1/2) = lgamma(1/2) - log(Gamma(a + 1/2) / Gamma(a))
-    const double lbeta = 0.5 * std::log(3.14159265358979323846264338327950288) - lgamma_ratio_half(a);
-    const double lx = (t2 < df) ? std::log1p(-y) : std::log(x);
-    const double ly = (t2 < df) ? std::log(y) : std::log1p(-x);
-    const double log_pref = a * lx + b * ly - lbeta;
-    if (x < (a + 1.0) / (a + b + 2.0)) {
-        // tails below the smallest normal double are reported as 0: the power terms of Boost's / cephes' incomplete
-        // beta underflow there, and exact zeros are what the tie-breaking of MMPC sees for such pairs
-        const double p = std::exp(log_pref) * ibeta_cf(a, b, x) / a;
-        return p < std::numeric_limits<double>::min() ? 0.0 : p;
-    }
-    return 1.0 - std::exp(log_pref) * ibeta_cf(b, a, y) / b;
-}
-
-double cor_pvalue(double cor, int64_t df) {
-    const double statistic = cor * std::sqrt((double)df) / std::sqrt(1 - cor * cor);
-    return two_sided_t_pvalue(std::fabs(statistic), (double)df);
-}
 
 // Symmetric eigen-decomposition by cyclic Jacobi rotations (k is the conditioning-set size + 2: a handful).
 // Eigenvalues ascending in d, eigenvectors in the columns of u.
@@ -156,14 +91,16 @@ double cor_from_eigen(const std::vector<double>& d, const std::vector<double>& u
     return std::min(1.0, std::max(-1.0, -p12 / std::sqrt(p11 * p22)));
 }
 
-double lincor_pvalue(const pbn_lincor* h, int v1, int v2, int k, const int* cond) {
+}  // namespace
+
+double pbn::lincor::lincor_pvalue(const pbn_lincor* h, int v1, int v2, int k, const int* cond) {
     const int n = h->n;
     auto C = [&](int i, int j) { return h->cov[i + (size_t)j * n]; };
     if (k == 0) {  // cor_0cond, df = N - 2
         double cor = 0;
         if (!(C(v1, v1) < MACHINE_TOL || C(v2, v2) < MACHINE_TOL))
             cor = std::min(1.0, std::max(-1.0, C(v1, v2) / std::sqrt(C(v1, v1) * C(v2, v2))));
-        return cor_pvalue(cor, h->rows - 2);
+        return cor_pvalue(cor, test_df(h->rows, 0));
     }
     const int m = k + 2;
     std::vector<int> idx(m);
@@ -174,10 +111,10 @@ double lincor_pvalue(const pbn_lincor* h, int v1, int v2, int k, const int* cond
         for (int i = 0; i < m; ++i) a[i + (size_t)j * m] = C(idx[i], idx[j]);
     jacobi_eigh(a, m, d, u);
     const double cor = cor_from_eigen(d, u, m);
-    // linearcorrelation.cpp:46,93: df = N - 3 for one conditioning variable; the general overload builds a (k+2)
-    // matrix and uses N - 2 - (k + 2)
-    return cor_pvalue(cor, k == 1 ? h->rows - 3 : h->rows - 2 - m);
+    return cor_pvalue(cor, test_df(h->rows, k));
 }
+
+namespace {
 
 // ---- MMPC ----------------------------------------------------------------------------------------------------------
 using IntSet = std::unordered_set<int>;
@@ -470,6 +407,8 @@ int pbn_lincor_create(pbn_ctx* ctx, const pbn_table* table, pbn_lincor** out) {
         h->n = n;
         h->rows = table->n_rows;
         h->cov.assign((size_t)n * n, 0.0);
+        h->ctx = ctx;
+        h->batch_threshold = LINCOR_BATCH_MIN_TESTS;
         std::vector<int> cols;
         std::vector<double> mu, sse;
         // 32-column blocks so that every pair of columns meets in one Gram launch (<= 64 columns per launch)
@@ -488,6 +427,11 @@ int pbn_lincor_create(pbn_ctx* ctx, const pbn_table* table, pbn_lincor** out) {
                 for (int j = 0; j < d; ++j)
                     for (int i = 0; i < d; ++i) h->cov[cols[i] + (size_t)cols[j] * n] = sse[i + (size_t)j * d] / (double)(table->n_rows - 1);
             }
+        // the device batch (lincor_batch.hip) gathers its blocks from a device copy
+        HIP_CHECK(hipSetDevice(ctx->device));
+        h->dcov.alloc((size_t)n * n);
+        HIP_CHECK(hipMemcpyAsync(h->dcov.p, h->cov.data(), (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
         *out = h.release();
     });
 }
@@ -504,7 +448,15 @@ int pbn_lincor_from_cov(int n, int64_t rows, const double* cov, pbn_lincor** out
     });
 }
 
-void pbn_lincor_destroy(pbn_lincor* h) { PBN_API_LOCK; delete h; }
+void pbn_lincor_destroy(pbn_lincor* h) {
+    if (!h) return;
+    if (!h->ctx) { PBN_API_LOCK; delete h; return; }
+    pbn::ctx_pin pin_(h->ctx);
+    std::lock_guard<std::recursive_mutex> lock_(mu_of(h));
+    (void)hipSetDevice(h->ctx->device);
+    (void)hipStreamSynchronize(h->ctx->stream);
+    delete h;
+}
 
 int pbn_lincor_cov(const pbn_lincor* h, double* cov) {
     return guarded([&] {

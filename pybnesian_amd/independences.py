@@ -126,10 +126,29 @@ class LinearCorrelation(IndependenceTest):
             _lib.check(lib.pbn_mi_set_order(self._per_test._handle, len(nodes), _lib.int_array([self._idx(n) for n in nodes])))
             return C.cast(lib.pbn_mi_lincor_pvalue, C.c_void_p), self._per_test._handle, self, []
         # native fast path: the C function itself is the callback, no Python frame per test
-        if all(n in self._index for n in nodes) and [self._index[n] for n in nodes] == list(range(len(nodes))) and len(nodes) == len(self._names):
+        self._native_order = all(n in self._index for n in nodes) and [self._index[n] for n in nodes] == list(range(len(nodes))) and len(nodes) == len(self._names)
+        if self._native_order:
             lib = _lib.load()
             return C.cast(lib.pbn_lincor_pvalue, C.c_void_p), self._handle, self, []
         return super()._ci_callback(nodes)
+
+    def _pc_batch_callback(self):
+        """Batched native callback for searches that guard their decisions against device rounding (PC's band): one test per lane on
+        the device for a handle made from a table, a host loop for one made from a covariance.  Only beside the native _ci_callback
+        (same handle, same index order); a table with nulls has no batch form."""
+        if self._per_test is not None or not getattr(self, "_native_order", False):
+            return None
+        return C.cast(_lib.load().pbn_lincor_pvalue_batch, C.c_void_p)
+
+    def batch_stats(self):
+        """Cumulative (device tests, host tests, device tests recomputed on the host) of the batched callback."""
+        d, h, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(_lib.load().pbn_lincor_batch_stats(self._handle, C.byref(d), C.byref(h), C.byref(r)))
+        return d.value, h.value, r.value
+
+    def set_batch_threshold(self, min_tests):
+        """Batches of fewer tests (per conditioning-set size) loop on the host; 0 sends every batch to the device."""
+        _lib.check(_lib.load().pbn_lincor_set_batch_threshold(self._handle, int(min_tests)))
 
     def __del__(self):
         try:

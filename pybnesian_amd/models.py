@@ -408,6 +408,12 @@ class Dag:
     def children(self, node):
         return [t for s, t in self._arcs if s == node]
 
+    def to_pdag(self):
+        """The CPDAG of this DAG's equivalence class, as a (Conditional)PartiallyDirectedGraph."""
+        from .graph import dag_to_pdag
+
+        return dag_to_pdag(self)
+
     def __eq__(self, other):
         return isinstance(other, Dag) and (self._nodes, self._interface, sorted(self._arcs)) == (other._nodes, other._interface, sorted(other._arcs))
 
