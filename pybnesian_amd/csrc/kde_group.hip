@@ -26,7 +26,7 @@ namespace {
 
 constexpr int GB = PBN_GROUP_BLOCK;
 constexpr int MORTON_BITS = 24;   // low bits of a sort key; the pool's index inside the batch sits above them
-// training rows scanned on either side of a query's position (kde_kernels.hip: PBN_PRUNE_WINDOW is the per-unit form's, 32).  Round 4: 8 - the
+// training rows scanned on either side of a query's position (kde_prepass.hip: PBN_PRUNE_WINDOW is the per-unit form's, 32).  Round 4: 8 - the
 // sum bound now comes from the boxes of the surrounding tiles, the row scan only has to find a near row for the offsets; the 64-row scan was
 // 0.36 s of C5's 8.2 s (8.17 -> 7.92 s, cv64 / C3 unchanged: profiles/r4/row_window_probe.txt)
 #define PBN_GROUP_WINDOW 8
@@ -48,7 +48,7 @@ struct GDev {   // argument block of the block-wise kernels
     int xstride, Rs;
     int nunits;
     int use_sum_bound;
-    int f16;                 // fp32 table: f16x2 fragments (kde_kernels.hip pack_rows_f16_kernel), KS = number of f16 MFMAs
+    int f16;                 // fp32 table: f16x2 fragments (kde_sweep_f16.inc pack_rows_f16_kernel), KS = number of f16 MFMAs
     int KS;                   // MFMAs per (tile, group) of the chunk's sweep shape
     int window;               // training rows the prepass scans on either side of a query's position (PBN_GROUP_WINDOW)
     unsigned long long* out_max;   // nullable: [sum_slot] bits of the largest |z|^2 of a unit's training rows (f16 chunks)
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(64) void group_scan_kernel(GDev g) {
     }
 }
 
-// whitened coordinates of one row, fragment stores shared by the two pack kernels (fp64 classic fragments, kde_kernels.hip
+// whitened coordinates of one row, fragment stores shared by the two pack kernels (fp64 classic fragments, kde_prepass.hip
 // pack_rows_kernel: training side norms in C-row order + weights 2^norm, query side norms by row; fp32: f16x2 fragments)
 // returns |z|^2 of the row (f16 chunks; 0 otherwise)
 __device__ __forceinline__ double pack_store(const GDev& g, const GUnit& U, const double* x, int d, int dest, bool query, int32_t tpos) {

@@ -85,7 +85,7 @@ size_t kde_group_pool_bytes(const GroupBatch& b, const GPool& P);
 // Whether a set of d variables over training sets of at least n_min rows takes this path.
 bool kde_group_applies(int dtype, int d, int64_t n_min, int R);
 
-// per-unit record the grouped sweep kernels read (kde_kernels.hip)
+// per-unit record the grouped sweep kernels read (kde_kernels.hip, kde_sweep_f16.inc, kde_moment.hip)
 struct GSweepUnit {
     const void* Apack;
     const void* nxpack;

@@ -1,4 +1,5 @@
-// Kernel argument blocks + launchers shared between kde_kernels.hip and the C-ABI glue.
+// Kernel argument blocks + launchers shared between the KDE kernel units (kde_kernels.hip, kde_moment.hip, kde_prepass.hip, kde_cdf.hip,
+// kde_finish.hip) and the C-ABI glue.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,7 +66,7 @@ struct PackArgs {
 };
 
 
-// ---- f16x2 fragments of fp32 tables (kde_kernels.hip, "fp32 path on the 16-bit matrix cores"): device helpers shared by the pack kernels ----
+// ---- f16x2 fragments of fp32 tables (kde_sweep_f16.inc, "fp32 path on the 16-bit matrix cores"): device helpers shared by the pack kernels ----
 typedef _Float16 hf8 __attribute__((ext_vector_type(8)));   // (eight 16-bit pieces of a fragment lane)
 typedef _Float16 hpiece;
 #define PBN_H_C1 32768.0f      // 2^15
@@ -150,7 +151,7 @@ struct SweepArgs {
     int64_t tiles_per_split;
     int fold;      // the packs carry the training norms in a free K slot (PackArgs::fold_norm)
     int count_redo; // measurement aid (PBN_SWEEP_COUNT_REDO): count the units of the unchecked pass that redo their split
-    int fast;      // fp64 plain sweeps whose result is a SUM over the test rows: 2^f on the fp32 transcendental unit (kde_kernels.hip: exp2_f64_fract<true>)
+    int fast;      // fp64 plain sweeps whose result is a SUM over the test rows: 2^f on the fp32 transcendental unit (kde_device.hpp: exp2_f64_fract<true>)
     int wmul;      // fp64 plain sweeps with d mod 4 == 0: training norms as weights 2^norm behind the norms (PackArgs::write_w)
     int w32;       // fp32 plain unpruned sweeps whose contraction leaves three slots free: the 32x32x16 f16 form (kde_sweep_f16_w32_kernel; f16x2_w32)
     // Tile pruning (low-dimensional fp64 sweeps of the score engine): both sides are packed in Morton order of their
@@ -159,7 +160,7 @@ struct SweepArgs {
     // (from a scan of the training rows next to them in Morton order).  A wave skips a training tile whose box is so far
     // from the box of its queries that every exponent is below that bound - prune_margin: such terms are < 2^-margin of their sums
     // each, i.e. at most N 2^-margin of a sum in total; the margin is 52 (fp64) / 40 (fp32) at 10^6 training rows and follows
-    // log2(N / 10^6), so that bound is 2.2e-10 (9.1e-7) of a sum for every N (kde_kernels.hip: prune_margin).
+    // log2(N / 10^6), so that bound is 2.2e-10 (9.1e-7) of a sum for every N (kde_prepass.hip: prune_margin).
     int prune;
     int pdims;
     double prune_margin;       // base-2 exponent distance below the queries' bound beyond which a tile is skipped (52 / 40)
@@ -263,6 +264,10 @@ struct SweepQG {
 #ifndef PBN_QG_PRUNE_COND
 #define PBN_QG_PRUNE_COND 2
 #endif
+// Pruned sweeps run ONE wave per workgroup: the kept tiles differ from wave to wave (each has its own query box), and a
+// 4-wave workgroup holds its slots until its slowest wave is done - measured at 0.67-0.77 of the unpruned rate per visited
+// tile at d = 2, 3 whatever the number of splits (tools/prune_visits.py); nothing in the kernel is shared between waves.
+constexpr int sweep_block_threads(bool prune) { return prune ? 64 : 256; }
 int sweep_qg(int dtype, bool cond, int KS, bool prune = false);
 bool sweep_folds_norm(int dtype, bool cond, int KS, int dm);   // see PackArgs::fold_norm
 bool sweep_weights_norm(int dtype, bool cond, int KS, int dm); // see SweepArgs::wmul
@@ -326,6 +331,9 @@ void launch_far_fix(const PackArgs& query_pack, const void* Apack, const void* A
                     int64_t nqtiles, bool cond, hipStream_t st);
 void launch_sweep(const SweepArgs& a, int dtype, int KS, bool cond, int nsplit, hipStream_t st);
 void launch_finish(const FinishArgs& a, bool cond, double* dev_sum_out, hipStream_t st, double* dev_sum_marg_out = nullptr);
+// out[0] = sum of in[0 .. n), fixed order (kde_finish.hip; launch_ucv in kde_cdf.hip ends with it too - a call between two units of the
+// library, not one of its exports)
+__attribute__((visibility("hidden"))) void launch_reduce_final(const double* in, int64_t n, double* out, hipStream_t st);
 // out[i] = a[i] - b[i] (CKDE as joint - marginal when the two come from separate sweeps)
 void launch_diff(double* out, const double* a, const double* b, int64_t n, hipStream_t st);
 

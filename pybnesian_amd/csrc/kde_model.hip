@@ -1,5 +1,5 @@
 // Host side of KDE / ProductKDE / CKDE fitting and evaluation, shared by the public handles and the score
-// engine.  See kde_kernels.hip for the device side.
+// engine.  See kde_kernels.hip (and the units its header lists) for the device side.
 #include <cstdio>
 #include <algorithm>
 #include <atomic>

@@ -1,4 +1,4 @@
-"""GPU tier, fp32 tables: adversarial inputs for the f16x2 fragments (round 6; csrc/kde_kernels.hip "fp32 path on the 16-bit matrix cores").
+"""GPU tier, fp32 tables: adversarial inputs for the f16x2 fragments (round 6; csrc/kde_sweep_f16.inc "fp32 path on the 16-bit matrix cores").
 Every whitened coordinate is cut into two f16 pieces z^ = a1 + a2; the products a1 b1, a1 b2, a2 b1 are exact, a2 b2 rides along only where
 the 32-slot blocks have room (spd = 4: d = 1...7, 10...15) and is DROPPED otherwise (spd = 3: d = 8, 9, 16...20).  On ordinary data the
 dropped products are zero-mean and tiny; here they are made one-sided and as large as the geometry allows: a training cluster and its

@@ -5,23 +5,16 @@ wait-count bookkeeping - and order the per-wave ring with hand-written `s_waitcn
 compiler puts NO other vector-memory instruction into the steady-state loop: a scratch spill or a re-materialised global load
 would shift it, and the MFMAs would read a stage before it has landed - silently wrong moments.  This test compiles the file for
 gfx950 and checks every basic block that holds both MFMAs and LDS-DMA loads."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pybnesian_amd", "csrc")
+from helpers import unit_asm
 
 
 @pytest.fixture(scope="module")
-def stats_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "stats_kernels.s"
-    p = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                        "stats_kernels.hip", "-o", str(out)], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return out.read_text()
+def stats_asm():
+    return unit_asm("stats_kernels")
 
 
 def kernels(asm, pattern):
@@ -65,15 +58,19 @@ def test_gather_ring_kernels_keep_their_stages_in_flight(stats_asm):
 
 
 @pytest.fixture(scope="module")
-def kde_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "kde_kernels.s"
-    p = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-slp-vectorize", "-S", "--cuda-device-only",
-                        "kde_kernels.hip", "-o", str(out)], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return out.read_text()
+def kde_asm():
+    """The sweeps' unit (fp64 and, through kde_sweep_f16.inc, fp32 on the 16-bit matrix cores)."""
+    return unit_asm("kde_kernels")
 
 
-def test_grouped_kernels_keep_their_register_budgets(kde_asm):
+@pytest.fixture(scope="module")
+def kde_grouped_asm(kde_asm):
+    """... and the moment pass that runs beside the grouped sweeps."""
+    return kde_asm + unit_asm("kde_moment")
+
+
+def test_grouped_kernels_keep_their_register_budgets(kde_grouped_asm):
+    kde_asm = kde_grouped_asm
     """The grouped score-engine kernels live on their occupancy (DESIGN.md 3.5c, profiles/r5/waves_probe.txt): the moment kernel of two-variable
     terms once ran 2x slower when a build spilled 42 of its coefficient registers, the fp64 sweeps are compiled for four waves per SIMD with two
     query groups per wave BECAUSE that shape fits 128 VGPRs nearly without scratch.  A compiler or source change that breaks this shows here,

@@ -8,14 +8,11 @@ source asks for but only the listing shows (profiles/r9/):
     run-time number of box dimensions every dimension was a basic block of its own with its own loads and waits: eight dependent trips);
   * its registers: three waves per SIMD, nothing in scratch, the 64-bit visit masks in scalar registers.
 Every assertion below fails on the source before round 9 (no blind loop for this shape, eight wait-separated load groups per test)."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pybnesian_amd", "csrc")
+from helpers import unit_asm
 
 # What launch_sweep_tf starts for the d = 8 sum-only sweep: kde_sweep_pruned_d8_kernel (the box dimensions at compile time) where the source has
 # it, else kde_sweep_kernel<double, 2, COND = false, QG = 2, FOLD = false, PRUNE = true, WMUL = true, EF32 = true>
@@ -23,12 +20,8 @@ HEADLINE = ("_ZN3pbn26kde_sweep_pruned_d8_kernelENS_9SweepArgsE", "_ZN3pbn16kde_
 
 
 @pytest.fixture(scope="module")
-def kde_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa_d8") / "kde_kernels.s"
-    p = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-slp-vectorize", "-S", "--cuda-device-only",
-                        "kde_kernels.hip", "-o", str(out)], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return out.read_text()
+def kde_asm():
+    return unit_asm("kde_kernels")   # the unit that holds the fp64 sweeps
 
 
 def headline(asm):

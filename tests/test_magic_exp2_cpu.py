@@ -1,4 +1,4 @@
-"""CPU tier: the arithmetic of exp2_magic (pybnesian_amd/csrc/kde_kernels.hip), word for word in numpy.  The kernel form cannot run here; what can be
+"""CPU tier: the arithmetic of exp2_magic (pybnesian_amd/csrc/kde_device.hpp), word for word in numpy.  The kernel form cannot run here; what can be
 checked without a GPU is that the bit manipulation IS 2^x: the constants the source defines (parsed from it), the fraction cut with its
 round-to-nearest, the exponent add on the high word, the clamp's two ends, and what accumulators outside the binade - |x| >= 2^19, inf, NaN - turn
 into.  v_exp_f32 is taken as numpy's float32 exp2 (the hardware instruction is good to 1 ulp; the GPU tier measures it)."""
@@ -8,7 +8,7 @@ import re
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = open(os.path.join(ROOT, "pybnesian_amd", "csrc", "kde_kernels.hip")).read()
+SRC = open(os.path.join(ROOT, "pybnesian_amd", "csrc", "kde_device.hpp")).read()
 
 
 def _constants():

@@ -1,4 +1,4 @@
-"""GPU tier, fp64 sum-only sweeps: the 2^x that reads the accumulator's own words (kde_kernels.hip: exp2_magic) at the edges of what it
+"""GPU tier, fp64 sum-only sweeps: the 2^x that reads the accumulator's own words (kde_device.hpp: exp2_magic) at the edges of what it
 assumes.  The form needs the accumulator inside [2^20, 2^21) - |exponent| < 2^19 - and an exponent inside +-1023 for the bare
 five-instruction form; a clamp (v_med3_i32 on the high word) makes it total, and the unpruned sweeps drop the clamp for chunks of training
 tiles whose radii PROVE the exponents inside +-1022 (SweepArgs::tile_r).  These tables put rows and queries where those assumptions fail:

@@ -1,4 +1,4 @@
-"""Coefficients of the 2^f polynomials used by kde_kernels.hip: Remez exchange (relative error) in 60-digit arithmetic.
+"""Coefficients of the 2^f polynomials used by the KDE kernels (csrc/kde_device.hpp): Remez exchange (relative error) in 60-digit arithmetic.
   python tools/exp2_coeffs.py 7 0 1      -> degree 7 on [0, 1)   (v_fract_f64 range reduction)
   python tools/exp2_coeffs.py 7 -0.5 0.5 -> degree 7 on [-1/2, 1/2] (v_rndne_f64 range reduction)
   python tools/exp2_coeffs.py 6 pinned   -> degree 6 on [0, 1) with p(0) = 1 and p(1) = 2 exactly (the sweep's default)

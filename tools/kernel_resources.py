@@ -6,7 +6,8 @@ import os, re, subprocess, sys
 
 src = os.path.abspath(sys.argv[1])
 pat = re.compile(sys.argv[2] if len(sys.argv) > 2 else ".")
-extra = ["-fno-slp-vectorize"] if os.path.basename(src) == "kde_kernels.hip" else []   # as csrc/Makefile builds it
+KDE_UNITS = ("kde_kernels.hip", "kde_moment.hip", "kde_prepass.hip", "kde_cdf.hip", "kde_finish.hip")   # csrc/Makefile: KDE_UNITS
+extra = ["-fno-slp-vectorize"] if os.path.basename(src) in KDE_UNITS else []   # as csrc/Makefile builds them
 out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", *extra, "-Rpass-analysis=kernel-resource-usage",
                       "-c", os.path.basename(src), "-o", "/tmp/kr_%d.o" % os.getpid()], cwd=os.path.dirname(src), capture_output=True, text=True).stderr
 os.path.exists("/tmp/kr_%d.o" % os.getpid()) and os.remove("/tmp/kr_%d.o" % os.getpid())

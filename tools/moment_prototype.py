@@ -1,4 +1,4 @@
-"""CPU prototype (numpy) of the tile-moment evaluation of csrc/kde_kernels.hip kde_moment_group_kernel (d = 2): exact sums vs (exact for non-qualifying tiles + order-P expansions about tile centroids for
+"""CPU prototype (numpy) of the tile-moment evaluation of csrc/kde_moment.hip kde_moment_group_kernel (d = 2): exact sums vs (exact for non-qualifying tiles + order-P expansions about tile centroids for
 qualifying ones) under the graded criterion; reports the realised relative error of the sums and the share of pairs expanded."""
 import sys, os, math, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

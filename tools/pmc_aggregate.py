@@ -28,7 +28,8 @@ import hashlib
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 res["_source_blob"] = {}
-for src in ("kde_kernels.hip", "kde_group.hip", "stats_kernels.hip"):
+for src in ("kde_kernels.hip", "kde_sweep_f16.inc", "kde_device.hpp", "kde_moment.hip", "kde_prepass.hip", "kde_cdf.hip", "kde_finish.hip", "kde_group.hip",
+            "stats_kernels.hip"):
     with open(os.path.join(root, "pybnesian_amd", "csrc", src), "rb") as f:
         data = f.read()
     res["_source_blob"][src] = hashlib.sha1(b"blob %d\0" % len(data) + data).hexdigest()

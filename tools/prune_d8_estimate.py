@@ -10,7 +10,7 @@ box and the group's box leaves some term within 2^-margin of the group's bound o
             with Morton in place of Hilbert and without its subsample bound)
   kd        raw axes, 8-D kd-tree order, 8-D boxes, exact row sums
   rot+kd    principal axes, 8-D kd-tree order, 8-D boxes, exact row sums
-  rot+kd+pre  the same with the prepass bound in place of the exact sums (kde_kernels.hip query_prepass_kernel: the 64 training rows
+  rot+kd+pre  the same with the prepass bound in place of the exact sums (kde_prepass.hip query_prepass_kernel: the 64 training rows
             around the group's position and the far corners of the 512 tiles around it)
   rot+kd4   principal axes, kd-tree splits on the widest of the first 4 principal axes only, 8-D boxes (+pre: prepass bound)
   rot+morton4+pre  principal axes, Morton order of the first 4, 8-D boxes, prepass bound - the shipped form sorts by the Hilbert

@@ -1,4 +1,4 @@
-"""Which bound should the pruned d = 8 sum-only sweep prune with?  The window-sum bound (kde_kernels.hip query_window_kernel) against the
+"""Which bound should the pruned d = 8 sum-only sweep prune with?  The window-sum bound (kde_prepass.hip query_window_kernel) against the
 prepass bound and the exact one, on bench.py's C2 table, CPU only.  python tools/prune_window_estimate.py [--groups G] [--seed S]
 
 The mirror of tools/prune_d8_estimate.py (same table, whitening, rotation and block rule), with the Morton order of the first four principal
