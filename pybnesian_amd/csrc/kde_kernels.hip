@@ -518,11 +518,28 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
         // -1/2|z|^2 = -1000 - and 2^x' = inf or NaN from a huge z_t.z_q both leave the batch's sum NaN or infinite, and the redo takes the batch
         // through process_tile, whose bad tiles add the norms back and take the classic exponents)
         constexpr bool FASTP = PBN_SWEEP_UNCHECKED && !COND && sizeof(T) == 8 && (FOLD || WMUL || KS == 1);   // the shapes that stay <= 168 VGPRs
-        if (a.count_redo && lane == 0) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
+        {
+            bool count_tiles = a.count_redo && lane == 0;
+            if constexpr (PDFIX != 0) count_tiles = count_tiles && a.live_mask == nullptr;   // (with masks the screen counted them)
+            if (count_tiles) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
+        }
         // Two levels: a SUPER-BATCH of 64 batches (4096 tiles) is classified first, lane = batch, against the batches' own boxes (grouped
         // sweeps: GSweepUnit::batch_box) - one round trip to L2 for 64 batches instead of one per batch, which is what the walk over a
         // split's tiles costs where most batches hold nothing for the wave (the test below is latency, not arithmetic).
         constexpr bool JOINT = GMASK && !FARP && PDFIX != 0;   // prune_group_masks_joint
+        // SCR (round 11, the d = 8 shape): with SweepArgs::live_mask the visit masks were prepared by kde_screen_d8_kernel - the box masks less the
+        // blocks its f16 exponents prove dead.  A super-batch's masks are loaded lane = batch with one 16-byte load (lv) and a batch takes its own
+        // from there with v_readlane: no box test and no memory round trip inside the walk.  Without the pointer the kernel walks as before.
+        constexpr bool SCR = GMASK && WMUL && KS == 2 && PDFIX != 0 && QG == 2;
+        // (every use below sits under `if constexpr (SCR)`: the other shapes of this body compile to the code they had without it)
+        bool scr = false;
+        unsigned long long lv[SCR ? QG : 1];
+        int jl = 0;   // the lane that holds the current batch's words
+        if constexpr (SCR) {
+            scr = a.live_mask != nullptr;
+#pragma unroll
+            for (int g = 0; g < QG; ++g) lv[g] = 0;
+        }
         auto do_batch = [&](const int64_t tb, const unsigned gsel, const bool bare) -> bool {   // true: the batch was redone checked
             unsigned long long mask = 0;
             // (QLDS: the boxes are read from LDS where they are used - without this compiler barrier the reads are hoisted out of the walk and the
@@ -530,7 +547,20 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
             if constexpr (QLDS) asm volatile("" ::: "memory");
             if constexpr (GMASK) {
                 mask = 0;
-                if (JOINT && gmasks && gsel == (1u << QG) - 1u) {   // in reach of every group of the wave: one pass over the tile boxes
+                bool taken = false;
+                if constexpr (SCR) {
+                    if (scr) {
+#pragma unroll
+                        for (int g = 0; g < QG; ++g) {
+                            const unsigned lo = __builtin_amdgcn_readlane((unsigned)lv[g], jl), hi = __builtin_amdgcn_readlane((unsigned)(lv[g] >> 32), jl);
+                            gm[g] = ((unsigned long long)hi << 32) | lo;
+                            mask |= gm[g];
+                        }
+                        taken = true;
+                    }
+                }
+                if (taken) {
+                } else if (JOINT && gmasks && gsel == (1u << QG) - 1u) {   // in reach of every group of the wave: one pass over the tile boxes
                     decltype(qbox_of(0, 0)) qb[QG];
                     double thr[QG];
 #pragma unroll
@@ -582,7 +612,9 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                 mask = prune_visit_mask(TBp, pd, tb, t1, wlo, whi, wthr, lane);
             }
             if (!mask) return false;
-            if (a.count_redo && lane == 0) {
+            bool count_visits = a.count_redo && lane == 0;
+            if constexpr (SCR) count_visits = count_visits && !scr;   // (the screen counted the blocks that pass the box test)
+            if (count_visits) {
                 unsigned long long v = 0;
 #pragma unroll
                 for (int g = 0; g < QG; ++g) v += (unsigned long long)__builtin_popcountll(GMASK ? gm[g] : mask);
@@ -629,10 +661,27 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                 if (bboxes) {
                     const PBN_GLOBAL double* bb = (const PBN_GLOBAL double*)a.batch_box + ((int64_t)split * a.batches_per_split + ((bt - t0) >> 6)) * 2 * pd;
                     bm = 0;
+                    if constexpr (SCR) {
+                      if (scr) {
+                        if (bt < t1) {
+                            const PBN_GLOBAL unsigned long long* lp = (const PBN_GLOBAL unsigned long long*)a.live_mask +
+                                                                      (((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split + ((bt - t0) >> 6)) * QG;
+#pragma unroll
+                            for (int g = 0; g < QG; ++g) lv[g] = lp[g];
+                        } else {
+#pragma unroll
+                            for (int g = 0; g < QG; ++g) lv[g] = 0;
+                        }
+                      }
+                    }
 #pragma unroll
                     for (int g = 0; g < QG; ++g) {
                         const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
-                        bmg[g] = __ballot(bt < t1 && batch_in_reach<PDW>(bb, qbox_of(g, qt), pd, thr_of(g, qt)));
+                        bool reach_known = false;
+                        if constexpr (SCR) {
+                            if (scr) { bmg[g] = __ballot(lv[g] != 0); reach_known = true; }
+                        }
+                        if (!reach_known) bmg[g] = __ballot(bt < t1 && batch_in_reach<PDW>(bb, qbox_of(g, qt), pd, thr_of(g, qt)));
                         bm |= bmg[g];
                         // open for the wave = proven for every group that reaches the batch (the batch with the table's last tile - padding
                         // rows, whose norm slot is not a distance - never)
@@ -660,6 +709,7 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                 unsigned gsel = 0;
 #pragma unroll
                 for (int g = 0; g < QG; ++g) gsel |= (unsigned)((bmg[g] >> j) & 1ull) << g;
+                if constexpr (SCR) jl = j;
                 const bool redone = do_batch(sb + 64 * (int64_t)j, gsel, (GUARDP || GUARDW) && ((bopen >> j) & 1ull));
                 if constexpr (GUARDW) { if (redone) bopen = 0; } else (void)redone;
             }
@@ -927,6 +977,8 @@ static void launch_sweep_t(const SweepArgs& a, int KS, dim3 grid, hipStream_t st
 // another instruction schedule (the order in which the compiler emits the inline helpers the two share changes with what else the unit
 // instantiates, and the optimiser's result follows it): one unit keeps every kernel's code what the measurements were taken on.
 #include "kde_sweep_f16.inc"
+// ... and so is the f16 screen of the pruned d = 8 sweep: it counts into this unit's g_sweep_visit / g_sweep_tiles
+#include "kde_screen_d8.inc"
 
 void launch_pack(const PackArgs& a, int dtype, hipStream_t st) {
     const int64_t npad = a.ntiles * 16;
@@ -987,6 +1039,13 @@ void launch_sweep_grouped(const GSweepArgs& g, int dtype, int KS, hipStream_t st
 
 }  // namespace pbn
 
+// measurement aid like pbn_debug_sweep_visits: blocks the d = 8 screen kept / blocks it tested (those that pass the box test)
+extern "C" void pbn_debug_d8_screen(unsigned long long* kept, unsigned long long* tested, int reset) {
+    unsigned long long z = 0;
+    if (kept) (void)hipMemcpyFromSymbol(kept, HIP_SYMBOL(pbn::g_screen_kept), sizeof z);
+    if (tested) (void)hipMemcpyFromSymbol(tested, HIP_SYMBOL(pbn::g_screen_tested), sizeof z);
+    if (reset) { (void)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_screen_kept), &z, sizeof z); (void)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_screen_tested), &z, sizeof z); }
+}
 extern "C" void pbn_debug_w32_launches(unsigned long long* n, int reset) {
     if (n) *n = pbn::g_w32_launches.load();
     if (reset) pbn::g_w32_launches.store(0);

@@ -190,6 +190,14 @@ struct SweepArgs {
     // (Measured and dropped, round 5: a bitmap written by the moment pass - the batches that still hold pairs for the sweep, 24 % of the
     //  (batch, group) masks at 300 000 rows - instead of the sweep's own batch test: sweep 2.03 -> 1.90 s, moment kernel 4.93 -> 5.04 s on C3's first iteration.)
     double* part;  // [nsplit][nqtiles*16][P]
+    // The f16 screen of the pruned sum-only d = 8 sweep (round 11, kde_screen_d8.inc): 32 B per sorted training row / per sorted query in the
+    // operand order of the 32x32x16 f16 MFMA, and per (sweep wave, batch of its split, group) the 64-bit mask of the tiles that pass the box
+    // test and hold a pair the screen could not prove below the drop threshold.  kde_screen_d8_kernel writes live_mask;
+    // kde_sweep_pruned_d8_kernel, given it, takes its visit masks from there and tests no box of its own (null = it walks the boxes itself).
+    const void* scr_train;
+    const void* scr_query;
+    unsigned long long* live_mask;   // [ceil(nqtiles / PBN_QG_PRUNE)][nsplit][batches_per_split][PBN_QG_PRUNE]
+    unsigned long long* box_mask;    // test aid (pbn_debug_d8_masks), nullable: the box masks alone, same layout
 };
 
 // Position along the Hilbert curve of a cell in n = 2 ... 4 dimensions, `bits` bits per axis (Skilling's transpose form: undo the excess rotations
@@ -330,6 +338,10 @@ void launch_max_norm2(const PackArgs& a, int src_dtype, double* dev_out, hipStre
 void launch_far_fix(const PackArgs& query_pack, const void* Apack, const void* Axpack, int NB, int64_t n_train, int64_t ntiles, double* part, int nsplit,
                     int64_t nqtiles, bool cond, hipStream_t st);
 void launch_sweep(const SweepArgs& a, int dtype, int KS, bool cond, int nsplit, hipStream_t st);
+// the f16 screen of the pruned sum-only d = 8 sweep: operands from whitened rows z [n][8] (perm: sorted position -> row, null = sorted already)
+// into out [ntiles * 16][32 B], and the pass that fills SweepArgs::live_mask for the sweep launched with the same arguments and nsplit
+void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t ntiles, bool is_query, void* out, hipStream_t st);
+void launch_screen_d8(const SweepArgs& a, int nsplit, hipStream_t st);
 void launch_finish(const FinishArgs& a, bool cond, double* dev_sum_out, hipStream_t st, double* dev_sum_marg_out = nullptr);
 // out[0] = sum of in[0 .. n), fixed order (kde_finish.hip; launch_ucv in kde_cdf.hip ends with it too - a call between two units of the
 // library, not one of its exports)

@@ -5,6 +5,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <numeric>
 #include <vector>
@@ -388,6 +389,7 @@ void kde_pack_train(pbn_ctx* ctx, KdeModel& m, const pbn_table* t, const int* co
     pa.is_query = 0;
     if (dev_max_norm2 && m.dtype == PBN_F32 && !m.widen) launch_max_norm2(pa, t->dtype, dev_max_norm2, ctx->stream);
     m.prune = false;
+    m.scr = nullptr;
     const bool rot = prune && kde_prune_rotates(m);
     if (rot || (prune && kde_prune_applies(m.fdtype(), m.dm, m.N))) {
         auto al = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -443,7 +445,10 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store) {
     const size_t box_b = al((size_t)m.ntiles * 2 * m.pdims * sizeof(double)), zs_b = al((size_t)m.N * m.zdims * sizeof(double)),
                  key_b = al((size_t)m.N * sizeof(uint32_t));
     const SubBytes sb = sub_bytes(m, m.nsub);
-    store.alloc(box_b + zs_b + key_b + (m.nsub ? sb.total : 0));
+    // the operands of the d = 8 screen (PBN_D8_SCREEN, read here and at every evaluation: 0 at either keeps today's path)
+    const bool screen = m.wfull && !m.cond && m.dm == 8 && m.zdims == 8 && m.pdims == PBN_PRUNE_PD && m.fdtype() == PBN_F64 && knob_int("PBN_D8_SCREEN", 1) != 0;
+    const size_t sub_b = m.nsub ? al(sb.total) : 0, scr_b = screen ? (size_t)m.ntiles * 16 * 32 : 0;
+    store.alloc(box_b + zs_b + key_b + sub_b + scr_b);
     HIP_CHECK(hipMemcpyAsync(store.p, m.tile_box, box_b, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(store.p + box_b, m.zsorted, (size_t)m.N * m.zdims * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(store.p + box_b + zs_b, m.keys_sorted, (size_t)m.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
@@ -455,7 +460,25 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store) {
         HIP_CHECK(hipMemcpyAsync(sp, m.Asub, sb.total, hipMemcpyDeviceToDevice, ctx->stream));
         m.Asub = sp; m.nxsub = sp + sb.a; m.Axsub = m.cond ? sp + sb.a + sb.n : nullptr;
     }
+    m.scr = nullptr;
+    if (screen) {
+        char* sp = store.p + box_b + zs_b + key_b + sub_b;
+        KernelTimer kt(ctx, PBN_K_PACK);
+        launch_screen_pack(m.zsorted, nullptr, m.N, m.ntiles, false, sp, ctx->stream);
+        m.scr = sp;
+    }
 }
+
+// pbn_debug_d8_masks (test aid, not part of the C ABI header): armed, the next screened d = 8 sweep also writes its box masks, and both mask
+// arrays are copied to the host behind it, with the launch's shape and the tables the masks were taken from
+static std::atomic<bool> g_masks_capture{false};
+static std::mutex g_masks_mu;
+struct MaskDump {
+    std::vector<unsigned long long> box, live;
+    std::vector<double> qthr, zq, zt;  // per query tile: sum bound less the margin; the sorted queries' / training rows' whitened rows [n][8]
+    long long dims[6] = {0, 0, 0, 0, 0, 0};   // sweep waves, splits, batches per split, tiles per split, training tiles, queries
+};
+static MaskDump g_masks;
 
 // pbn_debug_sum_window (test aid, not part of the C ABI header): capture the window bounds (query_window_kernel) of the sum-only evaluations
 // that follow; returns how many the last one produced and copies up to `cap` of them - log2 units, the table's row order, -inf = none
@@ -619,8 +642,19 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     static const int gmasks = PBN_TUNE(PRUNE_GROUP_MASKS, 1);
     const bool bboxes = prune && gmasks && !m.cond && fdt == PBN_F64 && PBN_TUNE(GROUP_BATCH_BOXES, 1) != 0;
     const size_t part_b = ((size_t)nsplit * nqtiles * 16 * P * sizeof(double) + 255) / 256 * 256;
-    const size_t bbox_b = bboxes ? (size_t)nsplit * ceil_div(tps, 64) * 2 * m.pdims * sizeof(double) : 0;
-    ctx->scratch_part.reserve(part_b + bbox_b);
+    const size_t bbox_b = bboxes ? ((size_t)nsplit * ceil_div(tps, 64) * 2 * m.pdims * sizeof(double) + 255) / 256 * 256 : 0;
+    // The f16 screen of the sum-only d = 8 sweep (kde_screen_d8.inc): the queries' operands and the mask words behind the batch boxes, in the same
+    // grow-only arena in stream order.  One 64-bit word per (sweep wave, batch of a split, group): 51 MB at 1e6 x 1e5 rows; beyond
+    // PBN_D8_SCREEN_MAX_MB (default 512) the step runs unscreened.
+    // (Both knobs are read through getenv at every evaluation, like PBN_SUM_WINDOW and PBN_MAGIC_GUARD beside them: two lookups per step, so that a test or a
+    // deployment can turn them between two calls of one process.)
+    const bool mdbg = g_masks_capture.load();
+    bool screen = prune && sum_only && m.scr != nullptr && bboxes && wmul && m.KS == 2 && m.pdims == PBN_PRUNE_PD && m.zdims == 8 && knob_int("PBN_D8_SCREEN", 1) != 0;
+    const size_t scrq_b = screen ? (size_t)nqtiles * 16 * 32 : 0;
+    size_t mask_b = screen ? (size_t)ceil_div(nqtiles, PBN_QG_PRUNE) * nsplit * ceil_div(tps, 64) * PBN_QG_PRUNE * sizeof(unsigned long long) : 0;
+    if (screen && (double)mask_b * (mdbg ? 2.0 : 1.0) > (double)knob_int("PBN_D8_SCREEN_MAX_MB", 512) * 1048576.0) screen = false;
+    if (!screen) mask_b = 0;
+    ctx->scratch_part.reserve(part_b + bbox_b + (screen ? scrq_b + mask_b * (mdbg ? 2 : 1) : 0));
     SweepArgs sa{};
     sa.Apack = m.Apack; sa.nxpack = m.nxpack; sa.Axpack = m.Axpack;
     sa.Bpack = pa.pack; sa.nypack = pa.npack; sa.Bxpack = pa.xpack; sa.Bxnorm = pa.xnorm;
@@ -644,7 +678,35 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     }
     static const bool log_sweeps = PBN_TUNE(SWEEP_LOG, 0) != 0;   // one line per sweep on stderr (tools/c5_sweeps.py)
     if (log_sweeps) std::fprintf(stderr, "pbn-sweep N=%lld n=%lld d=%d cond=%d prune=%d nsub=%lld nsplit=%lld\n", (long long)m.N, (long long)n, m.d, (int)m.cond, (int)prune, (long long)(prune ? m.nsub : 0), (long long)nsplit);
+    if (screen) {
+        char* sp = (char*)ctx->scratch_part.p + part_b + bbox_b;
+        sa.scr_train = m.scr; sa.scr_query = sp;
+        sa.live_mask = (unsigned long long*)(sp + scrq_b);
+        sa.box_mask = mdbg ? (unsigned long long*)(sp + scrq_b + mask_b) : nullptr;
+        KernelTimer kt(ctx, PBN_K_PACK);
+        launch_screen_pack(qs.zrow, qs.perm, n, nqtiles, true, sp, ctx->stream);
+        launch_screen_d8(sa, (int)nsplit, ctx->stream);
+    }
     { KernelTimer kt(ctx, PBN_K_SWEEP); launch_sweep(sa, fdt, m.KS, m.cond, (int)nsplit, ctx->stream); }
+    if (screen && mdbg) {
+        std::lock_guard<std::mutex> lk(g_masks_mu);
+        const size_t words = mask_b / sizeof(unsigned long long);
+        g_masks.box.resize(words); g_masks.live.resize(words); g_masks.qthr.resize((size_t)nqtiles); g_masks.zq.resize((size_t)n * 8); g_masks.zt.resize((size_t)m.N * 8);
+        HIP_CHECK(hipMemcpyAsync(g_masks.zt.data(), m.zsorted, (size_t)m.N * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        std::vector<int32_t> perm((size_t)n);
+        std::vector<double> zrow((size_t)n * 8);
+        HIP_CHECK(hipMemcpyAsync(g_masks.box.data(), sa.box_mask, mask_b, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(g_masks.live.data(), sa.live_mask, mask_b, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(g_masks.qthr.data(), qthr, (size_t)nqtiles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(zrow.data(), qs.zrow, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(perm.data(), qs.perm, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (int64_t i = 0; i < n; ++i)
+            for (int k = 0; k < 8; ++k) g_masks.zq[(size_t)i * 8 + k] = zrow[(size_t)perm[(size_t)i] * 8 + k];
+        for (auto& v : g_masks.qthr) v -= sa.prune_margin;
+        const long long dims[6] = {(long long)ceil_div(nqtiles, PBN_QG_PRUNE), (long long)nsplit, (long long)ceil_div(tps, 64), (long long)tps, (long long)m.ntiles, (long long)n};
+        for (int i = 0; i < 6; ++i) g_masks.dims[i] = dims[i];
+    }
     // f16x2 fragments: queries beyond the f16 range were clamped by the pack - their partials are recomputed in fp64 (a flag test otherwise)
     if (b3) launch_far_fix(pa, m.Apack, m.Axpack, m.KS, m.N, m.ntiles, sa.part, (int)nsplit, nqtiles, m.cond, ctx->stream);
 
@@ -659,6 +721,27 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
 }
 
 }  // namespace pbn
+
+// capture != 0 arms the aid; what = 0 the shape (six values into dims), 1 / 2 the box / live masks, 3 the groups' thresholds, 4 / 5 the sorted
+// queries' / training rows' whitened rows: copies up to cap items into out and returns how many the last screened sweep left
+extern "C" int64_t pbn_debug_d8_masks(int what, void* out, int64_t cap, int capture) {
+    pbn::g_masks_capture.store(capture != 0);
+    std::lock_guard<std::mutex> lk(pbn::g_masks_mu);
+    const pbn::MaskDump& d = pbn::g_masks;
+    auto copy = [&](const void* src, size_t count, size_t size) -> int64_t {
+        if (out && count) std::memcpy(out, src, std::min<size_t>(count, (size_t)std::max<int64_t>(cap, 0)) * size);
+        return (int64_t)count;
+    };
+    switch (what) {
+        case 0: return copy(d.dims, 6, sizeof(long long));
+        case 1: return copy(d.box.data(), d.box.size(), 8);
+        case 2: return copy(d.live.data(), d.live.size(), 8);
+        case 3: return copy(d.qthr.data(), d.qthr.size(), 8);
+        case 4: return copy(d.zq.data(), d.zq.size(), 8);
+        case 5: return copy(d.zt.data(), d.zt.size(), 8);
+        default: return -1;
+    }
+}
 
 extern "C" int64_t pbn_debug_sum_window(double* out, int64_t cap, int capture) {
     pbn::g_window_capture.store(capture != 0);

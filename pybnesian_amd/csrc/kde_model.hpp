@@ -52,6 +52,9 @@ struct KdeModel {
     void* Asub = nullptr;
     void* nxsub = nullptr;
     void* Axsub = nullptr;
+    // fitted d = 8 handles whose sum-only sweeps are pruned on rotated boxes: the sorted rows once more as the f16 operands of the screen
+    // (kde_screen_d8.inc; written by kde_prune_persist into the handle's store, 32 B per padded row); null = those sweeps run unscreened
+    const void* scr = nullptr;
 };
 
 // Bytes needed for the three training-side fragment arrays.

@@ -1,0 +1,235 @@
+// The f16 screen of the pruned sum-only d = 8 sweep (round 11; part of kde_kernels.hip's translation unit: the sweep counters stay one pair in
+// one unit).  kde_sweep_pruned_d8_kernel visits every (tile, group) block whose BOXES come within the group's drop threshold; on the bench table
+// 36 % of those blocks hold no pair above the threshold at all - boxes over eight dimensions are wide.  kde_screen_d8_kernel walks the same
+// boxes first and looks at the distances themselves, approximately: one v_mfma_f32_32x32x16_f16 gives the exponents of 32 training rows x 32
+// queries - two tiles x the wave's two groups, four blocks - in 8 passes, against the 2 x 16 passes per block of the fp64 MFMAs.  A block ALL
+// of whose 256 approximate exponents lie below the threshold by more than their error bound is taken out of the mask the sweep then reads
+// (SweepArgs::live_mask) instead of testing boxes itself.
+//
+// Operands (32 B per row, the K = 16 slots of the MFMA; training row t against query q):
+//   slot      0..7          8        9        10       11   12       13       14       15
+//   training  f16(z_t,k)    nt_hi    nt_lo    et       0    1        1        1        0
+//   query     f16(z_q,k)    1        1        1        0    nq_hi    nq_lo    eq       0
+// nt = -1/2|z_t|^2 as hi = f16(nt), lo = f16(nt - hi); et, eq = the row's share of the error bound, rounded UP to f16.  The accumulator is
+//   s~ + E,   s~ ~ s = z_t.z_q - 1/2|z_t|^2 - 1/2|z_q|^2 (the pair's exponent, base-2 units),   E = et + eq >= |s~ - s|:
+// a pair is dead when that is < thr = the group's sum bound less the margin - what the box test compares -1/2 dist^2 of the boxes against.
+//
+// The bound.  u = 2^-11 + 2^-24 (f16, round to nearest, a conversion by way of fp32 included), h = 2^-14 (the pack writes 0 for |x| < 2^-14:
+// no f16 subnormal reaches the matrix core, whatever it does with them), v = 2^-23 (one fp32 rounding, truncation included), R = |z|_2,
+// N = 1/2 R^2, |z|_1 <= sqrt(8) R, R_t R_q <= N_t + N_q:
+//   coordinates  |d a_k| <= u |z_tk| + h, |a_k| <= (1 + u)|z_tk|, the same for b:
+//                |z_t.z_q - a.b| <= (2u + u^2) R_t R_q + h (1 + u)(|z_t|_1 + |z_q|_1) + 8 h^2 <= (2u + u^2)(N_t + N_q) + 3 h (1 + u)(R_t + R_q) + 8 h^2
+//   norms        |nt - hi - lo| <= u |nt - hi| + h <= u^2 N_t + h  (hi is finite: rows with N > 60000 are flagged, below)
+//   fp32 sum     the 16 products are exact in fp32 (11 x 11 bits); adding them to C = 0 in any order errs by at most ((1 + v)^16 - 1) T <= 17 v T,
+//                T = sum of their magnitudes <= (1 + u)^2 R_t R_q + (1 + u^2)(N_t + N_q) + et16 + eq16 <= 2.02 (N_t + N_q) + 1.01 (R_t + R_q) 2^-12 + 2^-12
+//   together     E <= et + eq,   e = KAPPA N + LAMBDA R + MU,   KAPPA = 2^-10 + 2^-20 + 35 2^-23 = 9.82e-4, LAMBDA = 2^-12, MU = 2^-13
+// (2u + 2u^2 <= 2^-10 + 2^-22 + 2^-21 < 2^-10 + 2^-20;  3h (1 + u) + 17 v 1.01 2^-12 < 2^-12;  4 h^2 + h + 17 v 2^-13 < 2^-13 per side.)
+// tests/test_prune_d8_screen_cpu.py restates s~ and E in numpy and holds |s~ - s| <= E on adversarial rows.  Typical rows of the bench table
+// (N = 67, R = 11.6 by the bandwidth rule) carry E = 0.14 exponent units.
+// Rows that the f16 operands cannot hold - a NaN or infinite coordinate, |z_k| > 65504, N > 60000 - are FLAGGED: coordinates 0 and +inf in the
+// norm's hi slot, so every exponent of theirs is +inf (no slot of the other side is negative or non-finite but a flagged row's own +inf) and
+// v_max3_f32 cannot lose it as it would a NaN: the block is kept.  The comparison keeps on a NaN threshold too.  Padding rows (beyond the
+// table) carry nt = -60000: they have no term.
+#define PBN_SCREEN_KAPPA (0x1p-10 + 0x1p-20 + 35.0 * 0x1p-23)
+#define PBN_SCREEN_LAMBDA 0x1p-12
+#define PBN_SCREEN_MU 0x1p-13
+
+typedef float f16acc __attribute__((ext_vector_type(16)));
+
+// measurement aid, not part of the C ABI header: (tile, group) blocks the screen kept / blocks it tested (= the blocks that pass the box test)
+__device__ unsigned long long g_screen_kept = 0, g_screen_tested = 0;
+
+__device__ __forceinline__ _Float16 f16_up(double x) {   // the smallest f16 >= x, x >= 0 and far below the format's top
+    _Float16 hv = (_Float16)x;
+    if ((double)hv < x) {
+        unsigned short b = __builtin_bit_cast(unsigned short, hv);
+        hv = __builtin_bit_cast(_Float16, (unsigned short)(b + 1));
+    }
+    return hv;
+}
+
+// one thread per padded row: z [n][8] (logical order; perm: sorted position -> logical row, null = z is sorted) -> out [ntiles * 16][2] hf8
+__global__ __launch_bounds__(256) void kde_screen_pack_kernel(const double* __restrict__ z, const int32_t* __restrict__ perm, int64_t n, int64_t npad,
+                                                             int is_query, hf8* __restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= npad) return;
+    const _Float16 one = (_Float16)1.0f, zero = (_Float16)0.0f;
+    hf8 c, k;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { c[j] = zero; k[j] = zero; }
+    double hi = -60000.0, lo = 0.0, e = 0.0;
+    if (r < n) {
+        const double* zr = z + (perm ? (int64_t)perm[r] : r) * 8;
+        double n2 = 0.0;
+        bool ok = true;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const double v = zr[j];
+            ok = ok && __builtin_fabs(v) <= 65504.0;   // (false for a NaN)
+            n2 = __builtin_fma(v, v, n2);
+        }
+        const double N = 0.5 * n2;
+        ok = ok && N <= 60000.0;
+        if (ok) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) c[j] = h_piece((float)zr[j]);
+            hi = (double)h_piece((float)-N);
+            lo = (double)h_piece((float)(-N - hi));
+            e = PBN_SCREEN_KAPPA * N + PBN_SCREEN_LAMBDA * __builtin_sqrt(n2) + PBN_SCREEN_MU;
+        } else {
+            hi = INFINITY;
+        }
+    }
+    const _Float16 e16 = f16_up(e);
+    if (is_query) { k[0] = one; k[1] = one; k[2] = one; k[4] = (_Float16)hi; k[5] = (_Float16)lo; k[6] = e16; }
+    else { k[0] = (_Float16)hi; k[1] = (_Float16)lo; k[2] = e16; k[4] = one; k[5] = one; k[6] = one; }
+    out[r * 2] = c;
+    out[r * 2 + 1] = k;
+}
+
+// Grid and block placement of kde_sweep_pruned_d8_kernel (pruned_block): wave (qx, split) here prepares the masks of wave (qx, split) there.
+// live_mask[((qx * nsplit + split) * batches_per_split + batch) * QG + g]: bit b = tile 64 batch + b of the split passes group g's box test AND
+// holds a pair the screen could not prove dead; every batch of the split is written (0 = out of reach).  box_mask (test aid, nullable): the box
+// masks alone.
+#ifndef PBN_SCREEN_WAVES
+#define PBN_SCREEN_WAVES 4   // waves per SIMD the screen is compiled for (128 VGPRs: the joint box test of two groups over eight dimensions spills at 5 and more)
+#endif
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(SweepArgs a) {
+    constexpr int QG = PBN_QG_PRUNE, PD = PBN_PRUNE_PD;
+    static_assert(QG == 2, "two groups = the 32 columns of the MFMA");
+    const int lane = threadIdx.x & 63;
+    int qx, split;
+    pruned_block(a, QG, blockIdx.x, qx, split);
+    const int64_t qt0 = (int64_t)qx * QG;
+    if (qt0 >= a.nqtiles) return;
+    const int64_t t0 = (int64_t)split * a.tiles_per_split;
+    const int64_t t1 = (t0 + a.tiles_per_split < a.ntiles) ? t0 + a.tiles_per_split : a.ntiles;
+    const PBN_GLOBAL double* __restrict__ TBp = (const PBN_GLOBAL double*)a.tile_box;
+    const PBN_GLOBAL double* __restrict__ QBp = (const PBN_GLOBAL double*)a.qtile_box;
+    const PBN_GLOBAL double* __restrict__ QTp = (const PBN_GLOBAL double*)a.qtile_thr;
+    const PBN_GLOBAL hf8* __restrict__ SA = (const PBN_GLOBAL hf8*)a.scr_train;
+    const PBN_GLOBAL hf8* __restrict__ SQ = (const PBN_GLOBAL hf8*)a.scr_query;
+    // the groups' boxes and thresholds in LDS, as the sweep keeps them (kde_sweep_body: QLDS) - the same words into the same box tests
+    __shared__ double qbs[QG * (2 * PD + 1)];
+    if (lane < QG * 2 * PD) {
+        const int g = lane / (2 * PD);
+        const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+        qbs[lane] = QBp[qt * 2 * PD + (lane - g * 2 * PD)];
+    } else if (lane < QG * 2 * PD + QG) {
+        const int g = lane - QG * 2 * PD;
+        const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+        qbs[lane] = QTp[qt] - a.prune_margin;
+    }
+    asm volatile("" ::: "memory");   // (one wave per workgroup, LDS in order: no barrier)
+    const int r = lane & 31, h = lane >> 5, gl = r >> 4;   // my column's group
+    const int64_t qtl = qt0 + gl < a.nqtiles ? qt0 + gl : a.nqtiles - 1;
+    const hf8 bq = SQ[(qtl * 16 + (r & 15)) * 2 + h];
+    // the group's threshold as a float not above it (a NaN stays a NaN: nothing compares below it)
+    const double thrd = qbs[QG * 2 * PD + gl];
+    float thrf = (float)thrd;
+    if ((double)thrf > thrd) thrf = __builtin_fmaf(-__builtin_fabsf(thrf), 0x1p-23f, thrf) - 0x1p-126f;   // at least one ulp down
+    const unsigned long long G0 = 0x0000ffff0000ffffull;   // the lanes that hold group 0's columns
+    const bool count = a.count_redo != 0;
+    if (count && lane == 0) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
+    PBN_GLOBAL unsigned long long* LM = (PBN_GLOBAL unsigned long long*)a.live_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG;
+    PBN_GLOBAL unsigned long long* BM = a.box_mask ? (PBN_GLOBAL unsigned long long*)a.box_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG : nullptr;
+    auto frag = [&](int64_t tb, int bA, int bB) -> hf8 {
+        const int64_t t = tb + (r < 16 ? bA : bB);
+        return SA[(t * 16 + (r & 15)) * 2 + h];
+    };
+    for (int64_t sb = t0; sb < t1; sb += 4096) {
+        const int64_t bt = sb + 64 * lane;   // my batch's first tile
+        const PBN_GLOBAL double* bb = (const PBN_GLOBAL double*)a.batch_box + ((int64_t)split * a.batches_per_split + ((bt - t0) >> 6)) * 2 * PD;
+        unsigned long long bmg[QG], bm = 0;
+#pragma unroll
+        for (int g = 0; g < QG; ++g) {
+            bmg[g] = __ballot(bt < t1 && batch_in_reach<PD>(bb, (const double*)&qbs[g * 2 * PD], PD, qbs[QG * 2 * PD + g]));
+            bm |= bmg[g];
+        }
+        unsigned long long my_live[QG] = {0, 0}, my_box[QG] = {0, 0};   // of MY batch (lane = batch)
+        while (bm) {
+            const int j = __builtin_ctzll(bm);
+            bm &= bm - 1;
+            const int64_t tb = sb + 64 * (int64_t)j;
+            const unsigned gsel = (unsigned)((bmg[0] >> j) & 1ull) | ((unsigned)((bmg[1] >> j) & 1ull) << 1);
+            unsigned long long gm[QG];
+            if (gsel == 3u) {
+                const double* qb[QG] = {(const double*)&qbs[0], (const double*)&qbs[2 * PD]};
+                const double thr[QG] = {qbs[QG * 2 * PD], qbs[QG * 2 * PD + 1]};
+                prune_group_masks_joint<PD, QG>(TBp, qb, PD, tb, t1, thr, lane, gm);
+            } else {
+#pragma unroll
+                for (int g = 0; g < QG; ++g)
+                    gm[g] = ((gsel >> g) & 1u) ? prune_group_mask<PD>(TBp, (const double*)&qbs[g * 2 * PD], PD, tb, t1, qbs[QG * 2 * PD + g], lane) : 0ull;
+            }
+            unsigned long long mask = gm[0] | gm[1];
+            if (!mask) continue;
+            unsigned long long lm0 = 0, lm1 = 0;
+            int bA = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            int bB = mask ? __builtin_ctzll(mask) : bA;   // an odd number of tiles: the last MFMA takes its tile twice
+            mask &= mask - 1;
+            hf8 af = frag(tb, bA, bB);
+            for (;;) {
+                const bool more = mask != 0;
+                int nA = bA, nB = bB;
+                if (more) {
+                    nA = __builtin_ctzll(mask);
+                    mask &= mask - 1;
+                    nB = mask ? __builtin_ctzll(mask) : nA;
+                    mask &= mask - 1;
+                }
+                const hf8 an = frag(tb, nA, nB);   // (unconditional, like the sweep's prefetch: after the last pair it is loaded again)
+                f16acc acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bq, acc, 0, 0, 0);
+                // rows 0..15 of the product (tile A) sit in registers 0..7, rows 16..31 (tile B) in 8..15; the column - the query - is the lane
+                const float mA = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(acc[0], acc[1]), __builtin_fmaxf(acc[2], acc[3])),
+                                                 __builtin_fmaxf(__builtin_fmaxf(acc[4], acc[5]), __builtin_fmaxf(acc[6], acc[7])));
+                const float mB = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(acc[8], acc[9]), __builtin_fmaxf(acc[10], acc[11])),
+                                                 __builtin_fmaxf(__builtin_fmaxf(acc[12], acc[13]), __builtin_fmaxf(acc[14], acc[15])));
+                const unsigned long long kA = __ballot(!(mA < thrf)), kB = __ballot(!(mB < thrf));
+                lm0 |= ((kA & G0) ? 1ull << bA : 0ull) | ((kB & G0) ? 1ull << bB : 0ull);
+                lm1 |= ((kA & ~G0) ? 1ull << bA : 0ull) | ((kB & ~G0) ? 1ull << bB : 0ull);
+                if (!more) break;
+                af = an; bA = nA; bB = nB;
+            }
+            lm0 &= gm[0];
+            lm1 &= gm[1];
+            if (count && lane == 0) {
+                atomicAdd(&g_sweep_visit, (unsigned long long)(__builtin_popcountll(gm[0]) + __builtin_popcountll(gm[1])));
+                atomicAdd(&g_screen_tested, (unsigned long long)(__builtin_popcountll(gm[0]) + __builtin_popcountll(gm[1])));
+                atomicAdd(&g_screen_kept, (unsigned long long)(__builtin_popcountll(lm0) + __builtin_popcountll(lm1)));
+            }
+            if (lane == j) { my_live[0] = lm0; my_live[1] = lm1; my_box[0] = gm[0]; my_box[1] = gm[1]; }
+        }
+        if (bt < t1) {
+            const int64_t jb = (bt - t0) >> 6;
+            LM[jb * QG] = my_live[0];
+            LM[jb * QG + 1] = my_live[1];
+            if (BM) { BM[jb * QG] = my_box[0]; BM[jb * QG + 1] = my_box[1]; }
+        }
+    }
+    // the batch slots past the table's end in a short last split hold nothing: written too, so that no word of a launch's masks is left as
+    // an earlier launch had it (the sweep never reads them; pbn_debug_d8_masks copies them)
+    for (int64_t jb = ((t1 - t0 + 63) >> 6) + lane; jb < a.batches_per_split; jb += 64) {
+        LM[jb * QG] = 0;
+        LM[jb * QG + 1] = 0;
+        if (BM) { BM[jb * QG] = 0; BM[jb * QG + 1] = 0; }
+    }
+}
+
+void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t ntiles, bool is_query, void* out, hipStream_t st) {
+    const int64_t npad = ntiles * 16;
+    if (npad == 0) return;
+    hipLaunchKernelGGL(kde_screen_pack_kernel, dim3((unsigned)ceil_div(npad, 256)), dim3(256), 0, st, z, perm, n, npad, is_query ? 1 : 0, (hf8*)out);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_screen_d8(const SweepArgs& a_in, int nsplit, hipStream_t st) {
+    SweepArgs a = a_in;
+    a.nsplit_grid = nsplit;
+    if (!a.scr_train || !a.scr_query || !a.live_mask || !a.batch_box || a.pdims != PBN_PRUNE_PD) throw invalid_error("KDE: the d = 8 screen needs its operands, masks and batch boxes");
+    const dim3 grid((unsigned)(ceil_div(a.nqtiles, PBN_QG_PRUNE) * nsplit)), block(64);
+    hipLaunchKernelGGL(kde_screen_d8_kernel, grid, block, 0, st, a);
+    HIP_CHECK(hipGetLastError());
+}
