@@ -456,6 +456,26 @@ int pbn_mi_set_order(pbn_mi* h, int n, const int* ids);
 /* ChiSquare::pvalue (learning/independences/discrete/chi_square.cpp:8-139) over the discrete columns of the same
  * handle (pbn_ci_pvalue_fn signature). */
 double pbn_chisq_pvalue(void* user, int v1, int v2, int n_cond, const int* cond);
+/* ChiSquare::pvalue for many tests per call (chi_square.cpp:8-139 over the joint_counts layout of discrete_indices.cpp:134-150;
+ * pbn_ci_pvalue_batch_fn, user = the pbn_mi handle, indices mapped through pbn_mi_set_order when set).  The contingency tables of all
+ * tests with at most pbn_chisq_batch_max_cells() cells and pbn_chisq_batch_max_cond() conditioning variables are counted in one device
+ * pass per launch chunk (csrc/chisq_batch.hip: no sort, no row grouping); the statistic is pbn_chisq_pvalue's own host routine on those
+ * integer counts, so a batched p-value is bit-identical to pbn_chisq_pvalue of the same test.  Larger tests, and every test of a call
+ * with fewer eligible tests than the batch threshold, loop over pbn_chisq_pvalue inside the call.  A bad index or a non-categorical
+ * variable gives NaN in that slot (pbn_last_error has the reason).  A test of zero degrees of freedom (a one-category x or y) may give
+ * NaN without pbn_last_error, exactly as pbn_chisq_pvalue does for it. */
+void pbn_chisq_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond,
+                            double* out);
+/* chi_square.cpp:8-139, discrete_indices.cpp:134-150: cumulative tests counted on the device / looped on the host by
+ * pbn_chisq_pvalue_batch. */
+int pbn_chisq_batch_stats(const pbn_mi* h, int64_t* device_tests, int64_t* host_tests);
+/* chi_square.cpp:8-139, discrete_indices.cpp:134-150: calls with fewer eligible tests than min_tests loop on the host (0: every
+ * eligible test goes to the device).  Results do not depend on it. */
+int pbn_chisq_set_batch_threshold(pbn_mi* h, int64_t min_tests);
+/* chi_square.cpp:8-139, discrete_indices.cpp:134-150: the caps of the device form - cells of one contingency table (prod of the
+ * cardinalities of x, y and Z) and conditioning variables. */
+int pbn_chisq_batch_max_cells(void);
+int pbn_chisq_batch_max_cond(void);
 /* Tables with nulls (hybrid/mutual_information.cpp:152-215, the contains_null overloads): a discrete null is code -1 in
  * pbn_mi_create; continuous nulls are NaN cells of the columns flagged here, with the pilot shift to use for them.  A
  * test then counts only the rows valid in all of its variables. */

@@ -457,7 +457,19 @@ class ChiSquare(MutualInformation):
         raise AttributeError("ChiSquare has no mi()")
 
     def _ci_batch_callback(self):
-        return None
+        """Batched native callback (same handle / index order as _ci_callback): the contingency tables of all tests of a call are
+        counted in one device pass (csrc/chisq_batch.hip); p-values are bit-identical to pvalue()."""
+        return C.cast(_lib.load().pbn_chisq_pvalue_batch, C.c_void_p)
+
+    def batch_stats(self):
+        """Cumulative (tests counted on the device, tests looped on the host) of the batched callback."""
+        d, h = C.c_int64(0), C.c_int64(0)
+        _lib.check(_lib.load().pbn_chisq_batch_stats(self._handle, C.byref(d), C.byref(h)))
+        return d.value, h.value
+
+    def set_batch_threshold(self, min_tests):
+        """Calls with fewer device-eligible tests loop on the host; 0 sends every eligible test to the device."""
+        _lib.check(_lib.load().pbn_chisq_set_batch_threshold(self._handle, int(min_tests)))
 
     def _ci_callback(self, nodes):
         lib = _lib.load()
