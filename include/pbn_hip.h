@@ -459,7 +459,7 @@ double pbn_chisq_pvalue(void* user, int v1, int v2, int n_cond, const int* cond)
 /* ChiSquare::pvalue for many tests per call (chi_square.cpp:8-139 over the joint_counts layout of discrete_indices.cpp:134-150;
  * pbn_ci_pvalue_batch_fn, user = the pbn_mi handle, indices mapped through pbn_mi_set_order when set).  The contingency tables of all
  * tests with at most pbn_chisq_batch_max_cells() cells and pbn_chisq_batch_max_cond() conditioning variables are counted in one device
- * pass per launch chunk (csrc/chisq_batch.hip: no sort, no row grouping); the statistic is pbn_chisq_pvalue's own host routine on those
+ * pass per launch chunk (csrc/chisq.hip: no sort, no row grouping); the statistic is pbn_chisq_pvalue's own host routine on those
  * integer counts, so a batched p-value is bit-identical to pbn_chisq_pvalue of the same test.  Larger tests, and every test of a call
  * with fewer eligible tests than the batch threshold, loop over pbn_chisq_pvalue inside the call.  A bad index or a non-categorical
  * variable gives NaN in that slot (pbn_last_error has the reason).  A test of zero degrees of freedom (a one-category x or y) may give

@@ -1,0 +1,488 @@
+// ChiSquare (learning/independences/discrete/chi_square.{hpp,cpp}) over the discrete columns of a pbn_mi handle (mi_internal.hpp): the
+// scalar test on the counts of the handle's row groupings, and many tests per call - the contingency tables of a whole skeleton level
+// counted in one device pass.
+//
+// A purely discrete test needs the cell counts of ONE contingency table and nothing else.  The scalar routine gets them as the segment
+// lengths of a row grouping (mi.hip, Engine::group_for: a key kernel, a radix sort of all N rows, a segment kernel, two synchronisations
+// and an N-entry permutation kept in the grouping cache) - built for the continuous moments of hybrid tests, and one of it per variable
+// set.  A PC or MMPC level asks for 10^3 ... 10^6 tables over nearly as many distinct variable sets.  Here one workgroup counts one
+// (test, row slice): every lane forms the keys of its rows from the code columns of the test and adds 1 into a table in LDS; the
+// workgroup then adds its table into the test's table in global memory.  No sort, no permutation, one launch per chunk of tests.
+//
+// LDS atomics on one address serialise: a 2 x 2 table takes the 64 lanes of a wave to 4 addresses, a constant column to 1.  The table is
+// therefore replicated R times (copies_for): a lane adds into copy (lane mod R), and the copies are staggered by one
+// bank, so that the lanes of a 32-lane group that meet in one cell are spread over R banks.  All sums are integer: neither the order of the LDS adds nor
+// the order in which the slices of a test reach global memory can change a count.
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+#include "common.hpp"
+#include "specfun.hpp"
+#include "hostmath.hpp"
+#include "mi_internal.hpp"
+
+namespace pbn {
+namespace chisq {
+
+constexpr int MAX_CELLS = 4096;            // cells of one contingency table counted on the device (pbn_chisq_batch_max_cells)
+constexpr int MAX_COND = 6;                // conditioning variables of a device test (pbn_chisq_batch_max_cond); fixes the descriptor's arrays
+constexpr int MAX_VARS = MAX_COND + 2;
+constexpr int BLOCK = 256;
+constexpr int LDS_WORDS = 8192;            // 32 KiB of counters per workgroup: five workgroups per CU of the 160 KiB
+constexpr int MAX_COPIES = 32;             // replicated sub-tables of one workgroup
+constexpr int ROWS_PER_LANE_U8 = 8;        // one 8-byte load per column and step
+constexpr int ROWS_PER_LANE_I32 = 4;       // four coalesced 4-byte loads per column and step
+constexpr int SLICE_ALIGN = BLOCK * ROWS_PER_LANE_U8;   // a slice starts on a multiple of it: the 8-byte loads stay aligned
+constexpr int MIRROR_ALIGN = 16;           // the byte mirror's leading dimension is a multiple of it (rows past N hold 0xFF)
+
+// One test = one contingency table.  key of a row = sum_j code[col[j]][row] * stride[j]; the row counts when code_j < card[j] for all j.
+struct Desc {
+    int m;                    // 2 + k variables: x, y, Z in the order given
+    int col[MAX_VARS];        // discrete column index
+    int stride[MAX_VARS];     // x fastest
+    int card[MAX_VARS];
+    int G;                    // prod card
+    int copies, copy_stride;  // R replicated sub-tables in LDS, copy c at c * copy_stride (copies_for)
+    int slices;               // workgroups of this test: slice s counts rows [row0 + s * rows_per_slice, ...) up to row1
+    int64_t table_off;        // first cell of its table in the launch's count buffer
+    int64_t row0, row1, rows_per_slice;
+};
+
+// R = the largest power of two <= r_max for which R padded tables fit LDS_WORDS.  The copy stride is G rounded up to the 32 banks a
+// 4-byte LDS atomic sees, plus one: cell c of copy r lies on bank (r + c) mod 32, so the lanes of a 32-lane group that hit one cell -
+// every lane, for a constant column - go to R different banks.  (Per 32-lane group: lanes l and l + 32 of a wave share a copy and are
+// served in different LDS passes, so more than 32 copies would buy nothing.)  One copy needs no padding.
+inline void copies_for(int G, int r_max, int* copies, int* copy_stride) {
+    const int padded = ((G + 31) & ~31) + 1;
+    int r = 1;
+    while (2 * r <= r_max && 2 * r <= MAX_COPIES && (int64_t)2 * r * padded <= LDS_WORDS) r *= 2;
+    *copies = r;
+    *copy_stride = r == 1 ? G : padded;
+}
+
+namespace {
+
+// CodeT = uint8_t: the byte mirror, ROWS_PER_LANE_U8 consecutive rows per lane and step from one 8-byte load per column.
+// CodeT = int32_t: the handle's codes as they are, ROWS_PER_LANE_I32 rows per lane and step, BLOCK rows apart (coalesced 4-byte loads;
+// the columns of codes_dev are N elements apart, which aligns nothing wider).
+template <typename CodeT>
+__global__ __launch_bounds__(BLOCK) void chisq_count_kernel(const Desc* __restrict__ descs, const CodeT* __restrict__ codes, int64_t ld,
+                                                             uint32_t* __restrict__ counts) {
+    extern __shared__ uint32_t cells[];   // [copies][copy_stride]
+    const Desc& d = descs[blockIdx.x];
+    const int slice = blockIdx.y;
+    if (slice >= d.slices) return;
+    const int tid = threadIdx.x, m = d.m, G = d.G, copies = d.copies, copy_stride = d.copy_stride;
+    const int words = copies * copy_stride;
+    for (int i = tid; i < words; i += BLOCK) cells[i] = 0u;
+    __syncthreads();
+    uint32_t* mine = cells + (tid & (copies - 1)) * copy_stride;
+    const int64_t r0 = d.row0 + (int64_t)slice * d.rows_per_slice;
+    const int64_t r1 = r0 + d.rows_per_slice < d.row1 ? r0 + d.rows_per_slice : d.row1;
+    if constexpr (sizeof(CodeT) == 1) {
+        constexpr int V = ROWS_PER_LANE_U8;
+        for (int64_t r = r0 + (int64_t)tid * V; r < r1; r += (int64_t)BLOCK * V) {
+            uint32_t key[V];
+#pragma unroll
+            for (int i = 0; i < V; ++i) key[i] = 0u;
+            uint32_t bad = 0u;
+            for (int j = 0; j < m; ++j) {
+                const uint2 v = *reinterpret_cast<const uint2*>(codes + (int64_t)d.col[j] * ld + r);
+                const uint32_t stride = (uint32_t)d.stride[j], card = (uint32_t)d.card[j];
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const uint32_t c = ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 0xFFu;
+                    key[i] += c * stride;
+                    bad |= (c >= card ? 1u : 0u) << i;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < V; ++i)
+                if (!((bad >> i) & 1u) && r + i < r1) atomicAdd(mine + key[i], 1u);
+        }
+    } else {
+        constexpr int V = ROWS_PER_LANE_I32;
+        for (int64_t r = r0 + tid; r < r1; r += (int64_t)BLOCK * V) {
+            uint32_t key[V];
+#pragma unroll
+            for (int i = 0; i < V; ++i) key[i] = 0u;
+            uint32_t bad = 0u;
+#pragma unroll
+            for (int i = 0; i < V; ++i) bad |= (r + (int64_t)i * BLOCK < r1 ? 0u : 1u) << i;
+            for (int j = 0; j < m; ++j) {
+                const CodeT* col = codes + (int64_t)d.col[j] * ld + r;
+                const uint32_t stride = (uint32_t)d.stride[j], card = (uint32_t)d.card[j];
+#pragma unroll
+                for (int i = 0; i < V; ++i) {
+                    const uint32_t c = ((bad >> i) & 1u) ? card : (uint32_t)col[(int64_t)i * BLOCK];
+                    key[i] += c * stride;
+                    bad |= (c >= card ? 1u : 0u) << i;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < V; ++i)
+                if (!((bad >> i) & 1u)) atomicAdd(mine + key[i], 1u);
+        }
+    }
+    __syncthreads();
+    // flush: the R copies of a cell, summed; a test of one slice owns its table (plain stores over the zeroed buffer)
+    uint32_t* out = counts + d.table_off;
+    const bool single = d.slices == 1;
+    for (int cell = tid; cell < G; cell += BLOCK) {
+        uint32_t s = 0u;
+        for (int c = 0; c < copies; ++c) s += cells[c * copy_stride + cell];
+        if (s == 0u) continue;
+        if (single) out[cell] = s;
+        else atomicAdd(out + cell, s);
+    }
+}
+
+// one thread packs four rows of one column
+__global__ __launch_bounds__(BLOCK) void chisq_byte_mirror_kernel(const int32_t* __restrict__ codes, int64_t n, uint8_t* __restrict__ mirror,
+                                                                   int64_t ld8) {
+    const int64_t r = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * 4;
+    if (r >= ld8) return;
+    const int32_t* col = codes + (int64_t)blockIdx.y * n;
+    uint32_t packed = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) packed |= (r + i < n ? (uint32_t)col[r + i] & 0xFFu : 0xFFu) << (8 * i);
+    *reinterpret_cast<uint32_t*>(mirror + (int64_t)blockIdx.y * ld8 + r) = packed;
+}
+
+// descs: n_tests descriptors in device memory; codes: the byte mirror ([n_disc][ld], bytes = true) or the handle's int32 codes; the
+// count buffer must be zero where a test has more than one slice.  lds_words = max over the tests of copies * copy_stride.
+void launch_count(const Desc* descs, int n_tests, int max_slices, int lds_words, bool bytes, const void* codes, int64_t ld, uint32_t* counts,
+                  hipStream_t stream) {
+    if (n_tests <= 0) return;
+    if (lds_words < 1 || lds_words > LDS_WORDS || max_slices < 1 || max_slices > 65535) throw invalid_error("ChiSquare batch: bad launch shape");
+    const dim3 grid((unsigned)n_tests, (unsigned)max_slices), block(BLOCK);
+    const size_t lds = (size_t)lds_words * sizeof(uint32_t);
+    if (bytes) hipLaunchKernelGGL(chisq_count_kernel<uint8_t>, grid, block, lds, stream, descs, (const uint8_t*)codes, ld, counts);
+    else hipLaunchKernelGGL(chisq_count_kernel<int32_t>, grid, block, lds, stream, descs, (const int32_t*)codes, ld, counts);
+    HIP_CHECK(hipGetLastError());
+}
+
+// mirror[j * ld8 + r] = (uint8_t)codes[j * n + r], 0xFF in the padding rows n ... ld8 - 1 (ld8 a multiple of MIRROR_ALIGN)
+void launch_byte_mirror(const int32_t* codes, int64_t n, int n_disc, uint8_t* mirror, int64_t ld8, hipStream_t stream) {
+    if (n_disc <= 0 || ld8 <= 0) return;
+    if (ld8 % MIRROR_ALIGN != 0 || ld8 < n) throw invalid_error("ChiSquare batch: bad mirror shape");
+    hipLaunchKernelGGL(chisq_byte_mirror_kernel, dim3((unsigned)ceil_div(ld8 / 4, BLOCK), (unsigned)n_disc), dim3(BLOCK), 0, stream, codes, n, mirror,
+                       ld8);
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+}  // namespace chisq
+}  // namespace pbn
+
+using namespace pbn;
+
+// pbn_chisq_pvalue_batch: a call with fewer device-eligible tests loops over the scalar routine.  The crossover that tools/chisq_timing.py
+// measured on an MI355X (profiles/chisq/chisq_timing.json): a batch of ONE test already beats the scalar routine - 1.9x at
+// 5e3 rows, 2.8x at 1e5, 5-10x at 1e6, k = 0 ... 4 (a scalar test: 77-460 us around its sort; a batch of one: 40-50 us) - so every non-empty
+// call goes to the device.  Results are bit-identical either way, so this value can only cost time.
+#define CHISQ_BATCH_MIN_TESTS 1
+#define CHISQ_CHUNK_CELLS ((size_t)1 << 26)   // cells of one launch chunk's count buffer: 256 MB of uint32
+
+namespace {
+
+// ChiSquare's p-value from the cell counts of one contingency table (chi_square.cpp:8-139): c[i + j * cx + k * cx * cy] rows with
+// x = i, y = j and configuration k of the conditioning set.  The ONE text behind pbn_chisq_pvalue and pbn_chisq_pvalue_batch - never
+// inlined, so that both callers run the same instructions: equal counts give the same bits.
+__attribute__((noinline)) double chisq_from_counts(const double* counts, int cx, int cy, int zc, int n_cond) {
+    const int vc = cx * cy;
+    double statistic = 0;
+    for (int k = 0; k < zc; ++k) {
+        const double* c = counts + (size_t)k * vc;
+        std::vector<double> mx(cx, 0.0), my(cy, 0.0);
+        double tot = 0;
+        for (int i = 0; i < cx; ++i)
+            for (int j = 0; j < cy; ++j) { mx[i] += c[i + j * cx]; my[j] += c[i + j * cx]; tot += c[i + j * cx]; }
+        if (tot == 0) continue;
+        const double inv = 1.0 / tot;
+        for (int i = 0; i < cx; ++i)
+            for (int j = 0; j < cy; ++j) {
+                const double expected = mx[i] * my[j] * inv;
+                if (expected != 0) { const double dd = c[i + j * cx] - expected; statistic += dd * dd / expected; }
+            }
+    }
+    if (n_cond > 1 && statistic < 1.4901161193847656e-08) return 1.0;   // chi_square.cpp:130-134
+    const double df = (cx - 1.0) * (cy - 1.0) * zc;
+    return gamma_q(0.5 * df, 0.5 * statistic);
+}
+
+// pbn_debug_chisq (test aid, not part of the C ABI header; see its definition)
+std::atomic<int> g_chisq_capture{0};   // bit 0: record every batch call, bit 1: time its phases
+std::mutex g_chisq_mu;
+std::vector<int64_t> g_chisq_rec;
+double g_chisq_phase[5] = {0, 0, 0, 0, 0};   // seconds: request and descriptors, memset, kernel, download, host finish
+
+struct ChisqTest {   // one slot of a batch call
+    int m = 0;
+    int vars[chisq::MAX_VARS];   // variable ids, x, y, Z
+    int G = 0;
+    int where = -1;              // 1 device, 0 host, -1 refused (NaN)
+    int slices = 0, copies = 0;
+};
+
+// The device part of pbn_chisq_pvalue_batch: the tests `which` (all eligible), chunk by chunk - descriptors up, one memset, one launch,
+// the chunk's tables down, chisq_from_counts on the host threads.  `tables` (capture only) receives every test's integer table.
+void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vector<int>& which, const int* cond_off, double* out, int* width,
+                        std::vector<std::vector<uint32_t>>* tables) {
+    pbn_ctx* ctx = h->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t N = h->N;
+    const bool timing = (g_chisq_capture.load() & 2) != 0;
+    double tp = mi_now();
+    auto phase = [&](int i) {
+        if (!timing) return;
+        HIP_CHECK(hipStreamSynchronize(st));
+        const double t = mi_now();
+        g_chisq_phase[i] += t - tp;
+        tp = t;
+    };
+    if (h->cs.codes8_state == 0) {   // the byte mirror: a quarter of the bytes of every later pass
+        // built when every CODE fits a byte: card - 1, or card where the column has a null bucket, <= 255.  256 categories without a null
+        // still fit; their code 255 is also the byte that pads the mirror past N, which the kernel's row bound keeps out, not its value.
+        int max_code = 0;
+        for (int j = 0; j < h->n_disc; ++j) max_code = std::max(max_code, h->card[j] - 1 + (int)h->disc_null[j]);
+        h->cs.codes8_state = -1;
+        static const bool allow = PBN_TUNE(CHISQ_BYTES, 1) != 0;
+        if (allow && max_code <= 255 && h->n_disc <= 65535) {
+            h->cs.ld8 = ceil_div(N, chisq::MIRROR_ALIGN) * chisq::MIRROR_ALIGN;
+            h->cs.codes8.alloc((size_t)h->cs.ld8 * h->n_disc);
+            chisq::launch_byte_mirror(h->codes_dev.p, N, h->n_disc, h->cs.codes8.p, h->cs.ld8, st);
+            h->cs.codes8_state = 1;
+        }
+    }
+    const bool bytes = h->cs.codes8_state == 1;
+    *width = bytes ? 1 : 4;
+    static const int r_max = PBN_TUNE(CHISQ_COPIES, chisq::MAX_COPIES);
+    static const int blocks_per_cu = PBN_TUNE(CHISQ_BLOCKS_PER_CU, 8);
+    std::vector<chisq::Desc> descs;
+    for (size_t base = 0; base < which.size();) {
+        // a chunk: as many tests as keep the count buffer within CHISQ_CHUNK_CELLS
+        size_t end = base, cells = 0;
+        while (end < which.size() && end - base < ((size_t)1 << 18) && cells + (size_t)tests[which[end]].G <= CHISQ_CHUNK_CELLS) cells += (size_t)tests[which[end++]].G;
+        const int T = (int)(end - base);
+        // slices: enough workgroups to fill the chip when the chunk has few tests, while a slice's flush (G cells) stays small against
+        // its row work: at least max(4096, 8 G) rows per slice, slice bounds on multiples of SLICE_ALIGN
+        const int64_t want = std::max<int64_t>(1, ceil_div((int64_t)ctx->num_cus * blocks_per_cu, T));
+        descs.assign((size_t)T, chisq::Desc{});
+        int max_slices = 1, lds_words = 1;
+        size_t off = 0;
+        for (int i = 0; i < T; ++i) {
+            ChisqTest& t = tests[which[base + i]];
+            chisq::Desc& d = descs[i];
+            d.m = t.m; d.G = t.G;
+            int stride = 1;
+            for (int j = 0; j < t.m; ++j) {
+                d.col[j] = t.vars[j] - h->n_cont;
+                d.card[j] = h->card[d.col[j]];
+                d.stride[j] = stride;
+                stride *= d.card[j];
+            }
+            chisq::copies_for(t.G, r_max, &d.copies, &d.copy_stride);
+            const int64_t cap = std::max<int64_t>(1, N / std::max<int64_t>(4096, 8 * (int64_t)t.G));
+            const int64_t s = std::min<int64_t>(std::min(want, cap), 65535);
+            d.rows_per_slice = ceil_div(ceil_div(N, s), chisq::SLICE_ALIGN) * chisq::SLICE_ALIGN;
+            d.slices = (int)ceil_div(N, d.rows_per_slice);
+            d.row0 = 0; d.row1 = N;
+            d.table_off = (int64_t)off;
+            off += (size_t)t.G;
+            t.slices = d.slices; t.copies = d.copies;
+            max_slices = std::max(max_slices, d.slices);
+            lds_words = std::max(lds_words, d.copies * d.copy_stride);
+        }
+        h->cs.descs.reserve((size_t)T);
+        h->cs.counts.reserve(cells);
+        if (h->cs.host.size() < cells) h->cs.host.resize(cells);
+        HIP_CHECK(hipMemcpyAsync(h->cs.descs.p, descs.data(), (size_t)T * sizeof(chisq::Desc), hipMemcpyHostToDevice, st));
+        phase(0);
+        HIP_CHECK(hipMemsetAsync(h->cs.counts.p, 0, cells * sizeof(uint32_t), st));
+        phase(1);
+        chisq::launch_count(h->cs.descs.p, T, max_slices, lds_words, bytes, bytes ? (const void*)h->cs.codes8.p : (const void*)h->codes_dev.p,
+                            bytes ? h->cs.ld8 : N, h->cs.counts.p, st);
+        phase(2);
+        HIP_CHECK(hipMemcpyAsync(h->cs.host.data(), h->cs.counts.p, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));   // (the descriptors are read by then as well)
+        phase(3);
+        const uint32_t* all = h->cs.host.data();
+        host_finish(T, [&](int i) {
+            const int slot = which[base + i];
+            const ChisqTest& t = tests[slot];
+            const uint32_t* c = all + descs[i].table_off;
+            std::vector<double> cnt((size_t)t.G);
+            for (int g = 0; g < t.G; ++g) cnt[g] = (double)c[g];
+            const int cx = descs[i].card[0], cy = descs[i].card[1];
+            out[slot] = chisq_from_counts(cnt.data(), cx, cy, t.G / (cx * cy), cond_off[slot + 1] - cond_off[slot]);
+            if (tables) (*tables)[slot].assign(c, c + t.G);
+        });
+        if (timing) { const double t = mi_now(); g_chisq_phase[4] += t - tp; tp = t; }
+        h->cs.device_tests += T;
+        base = end;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// ChiSquare::pvalue (learning/independences/discrete/chi_square.cpp:8-139) over the discrete columns of a pbn_mi handle:
+// Pearson's statistic summed over the configurations of the conditioning set, df = (|X|-1)(|Y|-1) prod |Z|.  Counts come
+// from the same device pass as the mutual information (no continuous statistics).  Expected counts are formed in
+// double; the reference multiplies two int marginals (chi_square.cpp:21,62,116), which overflows beyond ~46 000 rows
+// per cell pair.  pbn_ci_pvalue_fn signature, indices mapped through pbn_mi_set_order when set.
+double pbn_chisq_pvalue(void* user, int v1, int v2, int n_cond, const int* cond) {
+    pbn_mi* h = (pbn_mi*)user;
+    double result = std::nan("");
+    const int rc = guarded([&] {
+        if (!h || (n_cond > 0 && !cond)) throw invalid_error("pbn_chisq_pvalue: null argument");
+        std::vector<int> vars;
+        if (!mi::map_request(h, v1, v2, n_cond, cond, vars)) throw invalid_error("ChiSquare: variable index out of range");
+        int64_t G = 1;
+        for (int v : vars) {
+            if (v < h->n_cont || v >= h->n_cont + h->n_disc) throw invalid_error("ChiSquare: variable is not categorical");
+            G *= h->card[v - h->n_cont];
+            if (G > (1 << 24)) throw invalid_error("ChiSquare: too many discrete configurations");
+        }
+        std::vector<double> st;
+        mi::group_stats(h, {}, vars, st);
+        const int cx = h->card[vars[0] - h->n_cont], cy = h->card[vars[1] - h->n_cont];
+        result = chisq_from_counts(st.data(), cx, cy, (int)(G / (cx * cy)), n_cond);
+    });
+    return rc == PBN_OK ? result : std::nan("");
+}
+
+// ChiSquare::pvalue for many tests per call (chi_square.cpp:8-139 on the joint_counts layout of discrete_indices.cpp:134-150;
+// pbn_ci_pvalue_batch_fn, user = the pbn_mi handle, indices mapped through pbn_mi_set_order when set).  Tests of at most
+// chisq::MAX_CELLS cells and chisq::MAX_COND conditioning variables are counted by the kernels above - no DiscGroup, no sort, no
+// permutation - and finished by chisq_from_counts, the scalar routine's own arithmetic on the same integers: out[i] is bit-identical to
+// pbn_chisq_pvalue of test i, wherever it ran.  Every other test, and every test of a call with fewer eligible tests than the handle's
+// threshold, goes through pbn_chisq_pvalue here; so does a test with a bad index or a non-categorical variable, which that routine
+// refuses with NaN and pbn_last_error.  One NaN comes WITHOUT pbn_last_error, from the scalar routine and from here alike: a test of zero
+// degrees of freedom (a one-category x or y), where chisq_from_counts answers 1 when its statistic is exactly 0 and NaN when rounding
+// left it a few ulps above (gamma_q(0, tiny)).
+void pbn_chisq_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond, double* out) {
+    pbn_mi* h = (pbn_mi*)user;
+    if (!out || n_tests <= 0) return;
+    for (int i = 0; i < n_tests; ++i) out[i] = std::nan("");
+    if (!h || !v1 || !v2 || !cond_off) { set_last_error("pbn_chisq_pvalue_batch: null argument"); return; }
+    (void)guarded(mu_of(h), [&] {
+        const int64_t groups0 = h->groups_built;
+        const int nv = h->n_cont + h->n_disc;
+        std::vector<ChisqTest> tests((size_t)n_tests);
+        std::vector<int> device, vars;
+        for (int i = 0; i < n_tests; ++i) {
+            ChisqTest& t = tests[i];
+            const int k = cond_off[i + 1] - cond_off[i];
+            if (k < 0 || (k > 0 && !cond)) continue;   // refused by the scalar routine below
+            t.where = 0;
+            if (k > chisq::MAX_COND || h->N <= 0) continue;
+            t.m = 2 + k;
+            if (!mi::map_request(h, v1[i], v2[i], k, k > 0 ? cond + cond_off[i] : nullptr, vars)) continue;
+            bool ok = true;
+            int64_t G = 1;
+            for (int j = 0; j < t.m && ok; ++j) {
+                const int v = vars[j];
+                if (v < h->n_cont || v >= nv) { ok = false; break; }
+                for (int q = 0; q < j; ++q) ok = ok && t.vars[q] != v;   // a repeated variable: the scalar routine's own reading of it
+                t.vars[j] = v;
+                G *= h->card[v - h->n_cont];
+                ok = ok && G >= 1 && G <= chisq::MAX_CELLS;
+            }
+            if (!ok) continue;
+            t.G = (int)G;
+            device.push_back(i);
+        }
+        if ((int64_t)device.size() < (h->cs.threshold < 0 ? CHISQ_BATCH_MIN_TESTS : h->cs.threshold)) device.clear();
+        const bool capture = (g_chisq_capture.load() & 1) != 0;
+        std::vector<std::vector<uint32_t>> tables;
+        if (capture) tables.resize((size_t)n_tests);
+        int width = 0;
+        if (!device.empty()) {
+            chisq_batch_device(h, tests, device, cond_off, out, &width, capture ? &tables : nullptr);
+            for (int i : device) tests[i].where = 1;
+        }
+        const bool timing = (g_chisq_capture.load() & 2) != 0;
+        const double th0 = mi_now();
+        int64_t looped = 0;
+        for (int i = 0; i < n_tests; ++i) {
+            if (tests[i].where == 1) continue;
+            const int k = cond_off[i + 1] - cond_off[i];
+            out[i] = pbn_chisq_pvalue(user, v1[i], v2[i], k, (cond && k > 0) ? cond + cond_off[i] : nullptr);
+            if (out[i] == out[i]) ++looped; else tests[i].where = -1;
+        }
+        if (timing) g_chisq_phase[4] += mi_now() - th0;
+        h->cs.host_tests += looped;
+        if (capture) {
+            std::vector<int64_t> r{3, n_tests, groups0, h->groups_built};
+            for (int i = 0; i < n_tests; ++i) {
+                const ChisqTest& t = tests[i];
+                const bool dev = t.where == 1;
+                r.insert(r.end(), {(int64_t)t.where, dev ? width : 0, dev ? t.slices : 0, dev ? t.copies : 0, (int64_t)t.G, (int64_t)tables[i].size()});
+                r.insert(r.end(), tables[i].begin(), tables[i].end());
+            }
+            std::lock_guard<std::mutex> lk(g_chisq_mu);
+            g_chisq_rec.insert(g_chisq_rec.end(), r.begin(), r.end());
+        }
+    });
+}
+
+int pbn_chisq_batch_stats(const pbn_mi* h, int64_t* device_tests, int64_t* host_tests) {
+    return guarded(mu_of(h), [&] {
+        if (!h) throw invalid_error("pbn_chisq_batch_stats: null argument");
+        if (device_tests) *device_tests = h->cs.device_tests;
+        if (host_tests) *host_tests = h->cs.host_tests;
+    });
+}
+
+int pbn_chisq_set_batch_threshold(pbn_mi* h, int64_t min_tests) {
+    return guarded(mu_of(h), [&] {
+        if (!h || min_tests < 0) throw invalid_error("pbn_chisq_set_batch_threshold: bad argument");
+        h->cs.threshold = min_tests;
+    });
+}
+
+int pbn_chisq_batch_max_cells(void) { return chisq::MAX_CELLS; }
+int pbn_chisq_batch_max_cond(void) { return chisq::MAX_COND; }
+
+// pbn_debug_chisq (test aid, not part of the C ABI header).  op 1 arms the capture and clears it, op 0 disarms everything and clears,
+// op 2 copies up to `cap` int64 of the records into out and returns how many are held.  While armed, every pbn_chisq_pvalue_batch call
+// appends one record:
+//   3, n_tests, the handle's count of row groupings built before the call and after it, then per test in call order
+//      where (1 = counted on the device, 0 = looped on the host, -1 = refused with NaN), code width in bytes (1 = the byte mirror, 4 =
+//      int32; 0 off the device), slices, R (the replicated LDS sub-tables; both 0 off the device), G (cells; 0 when the test was not
+//      sized for the device), n (G on the device, else 0), and the n cell counts as copied back from the device, x fastest.
+// op 3 arms the phase clock and clears it, op 4 copies the 5 accumulated phase times in nanoseconds into out (request and descriptors,
+// memset, kernel, download, host finish): while it runs a batch call synchronises the stream after every phase.
+// Unarmed, a call pays two flag tests; no kernel and no result depends on any of it.
+int64_t pbn_debug_chisq(int op, int64_t* out, int64_t cap) {
+    std::lock_guard<std::mutex> lk(g_chisq_mu);
+    if (op == 0 || op == 1) {
+        g_chisq_rec.clear();
+        g_chisq_capture.store(op == 1 ? (g_chisq_capture.load() | 1) : 0);
+        return 0;
+    }
+    if (op == 2) {
+        for (int64_t i = 0; out && i < (int64_t)g_chisq_rec.size() && i < cap; ++i) out[i] = g_chisq_rec[(size_t)i];
+        return (int64_t)g_chisq_rec.size();
+    }
+    if (op == 3) {
+        for (double& p : g_chisq_phase) p = 0;
+        g_chisq_capture.store(g_chisq_capture.load() | 2);
+        return 0;
+    }
+    if (op == 4) {
+        for (int i = 0; out && i < 5 && i < cap; ++i) out[i] = (int64_t)(g_chisq_phase[i] * 1e9);
+        return 5;
+    }
+    return -1;
+}
+
+}  // extern "C"

@@ -1,11 +1,18 @@
 // Small dense linear algebra on the host (d <= a few dozen): the O(d^3) glue the reference does with
 // Eigen (LLT, SelfAdjointEigenSolver, inverse, determinant) between its device calls.  Written from
-// the textbook algorithms; nothing here touches O(N) data.
+// the textbook algorithms; nothing here touches O(N) data.  Behind them, what the batch entry points of the independence tests
+// share on the host: a wall clock and the few threads their per-test arithmetic is spread over.
 #pragma once
+#include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <exception>
 #include <limits>
+#include <thread>
 #include <vector>
+
+#include "common.hpp"
 
 namespace pbn {
 namespace hm {
@@ -141,4 +148,36 @@ inline bool is_psd(const double* a, int n, bool f32) {
 }
 
 }  // namespace hm
+
+inline double mi_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// The host arithmetic a batch spreads over a few threads (PBN_MI_THREADS, at most 16 by default): finish(i) for i = 0 ... n - 1, test
+// i on thread i mod nth; the first exception of a worker is rethrown on the caller.
+template <typename F>
+void host_finish(int n, F&& finish) {
+    static const int max_threads = [] {
+        const int hw = (int)std::thread::hardware_concurrency();
+        const int nt = knob_int("PBN_MI_THREADS", std::min(hw > 0 ? hw : 1, 16));
+        return nt < 1 ? 1 : nt;
+    }();
+    const int nth = std::min(max_threads, n / 64);
+    if (nth <= 1) {
+        for (int i = 0; i < n; ++i) finish(i);
+        return;
+    }
+    std::vector<std::thread> pool;
+    std::vector<std::exception_ptr> errs((size_t)nth);
+    for (int w = 0; w < nth; ++w)
+        pool.emplace_back([&, w] {
+            try {
+                for (int i = w; i < n; i += nth) finish(i);
+            } catch (...) {
+                errs[w] = std::current_exception();
+            }
+        });
+    for (auto& th : pool) th.join();
+    for (auto& ep : errs)
+        if (ep) std::rethrow_exception(ep);
+}
+
 }  // namespace pbn

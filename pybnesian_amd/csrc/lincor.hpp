@@ -1,4 +1,4 @@
-// LinearCorrelation's handle and the p-value arithmetic its host routine (mmpc.hip) and its device batch
+// LinearCorrelation's handle and the p-value arithmetic its host routine (lincor.hip) and its device batch
 // (lincor_batch.hip) share: one text for both sides, so that they can differ by rounding only (hipcc contracts a * b + c
 // into an FMA for the device; the host build has none).
 #pragma once
@@ -120,7 +120,7 @@ PBN_HD int64_t test_df(int64_t rows, int k) { return k == 0 ? rows - 2 : (k == 1
 
 #undef PBN_HD
 
-// the scalar host test (mmpc.hip): cor_0cond / cyclic Jacobi + pseudo-inverse, then cor_pvalue
+// the scalar host test (lincor.hip): cor_0cond / cyclic Jacobi + pseudo-inverse, then cor_pvalue
 double lincor_pvalue(const pbn_lincor* h, int v1, int v2, int k, const int* cond);
 
 }  // namespace lincor

@@ -8,18 +8,13 @@
 // the discrete variables involved, the count and the pilot-shifted first and second moments of the continuous ones;
 // moments are additive, so every pooled covariance is a sum of per-configuration moments on the host.
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <memory>
-#include <mutex>
-#include <thread>
-#include <exception>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -27,7 +22,7 @@
 #include "specfun.hpp"
 #include "hostmath.hpp"
 #include "stats_kernels.hpp"
-#include "chisq_batch.hpp"
+#include "mi_internal.hpp"
 
 using namespace pbn;
 
@@ -36,74 +31,6 @@ using namespace pbn;
 #define MI_SORTED_MAX_CONT 16     // continuous variables the register-accumulator kernel is instantiated for (152 accumulators)
 #define MI_SORTED_ROWS 4096       // rows of one configuration a 256-thread block sums
 #define MI_GROUP_CACHE 1024       // cached row groupings (one per set of discrete variables), least recently used out
-// pbn_chisq_pvalue_batch: a call with fewer device-eligible tests loops over the scalar routine.  The crossover that tools/chisq_timing.py
-// measured on an MI355X (profiles/chisq/chisq_timing.json): a batch of ONE test already beats the scalar routine - 1.9x at
-// 5e3 rows, 2.8x at 1e5, 5-10x at 1e6, k = 0 ... 4 (a scalar test: 77-460 us around its sort; a batch of one: 40-50 us) - so every non-empty
-// call goes to the device.  Results are bit-identical either way, so this value can only cost time.
-#define CHISQ_BATCH_MIN_TESTS 1
-#define CHISQ_CHUNK_CELLS ((size_t)1 << 26)   // cells of one launch chunk's count buffer: 256 MB of uint32
-
-// Rows grouped by the configuration of one set of discrete variables (sorted ids, first id fastest): `perm` lists the
-// rows configuration by configuration, ascending inside a configuration (stable radix sort), `off` are the segment
-// bounds = the counts, `blk` cuts every segment into pieces of at most MI_SORTED_ROWS rows.  Built once per set and
-// reused by every test over it; the set of no variables is the identity (perm empty).
-struct DiscGroup {
-    std::vector<int> vars;
-    int G = 1;
-    dev_buf<int32_t> perm;          // [N]
-    std::vector<int64_t> off;       // [G + 1]
-    dev_buf<int32_t> blk;           // [nblk][4]: configuration, first position, end position, unused
-    std::vector<int> blk_off;       // [G + 1] first block of every configuration
-    int nblk = 0;
-    uint64_t stamp = 0;
-    // configuration id in this grouping's order -> id in a test's own (x, y, z...) order, per variable order seen
-    std::map<std::vector<int>, std::vector<int>> order_maps;
-    // per configuration, the pilot-shifted sums and products of ALL continuous columns (Engine::ensure_full): every test over
-    // this set of discrete variables reads its moments out of them
-    bool full_ready = false;
-    std::vector<double> fullS, fullP;   // [G][nc], [G][nc][nc]
-};
-
-struct pbn_mi {
-    pbn::ctx_ptr ctx;
-    const pbn_table* table = nullptr;  // continuous columns (borrowed), null when there are none
-    int n_cont = 0, n_disc = 0;
-    int64_t N = 0;
-    bool asymptotic = true;
-    std::vector<int> card;
-    std::vector<char> disc_null, cont_null;   // columns holding nulls: code == card[j] / NaN; such rows drop out of a test
-    bool any_null = false;
-    dev_buf<int32_t> codes_dev;               // [n_disc][N]
-    std::vector<double> shift;                // pilot mean of every continuous column
-    int64_t device_passes = 0, host_passes = 0, device_launches = 0;
-    std::vector<int> order;  // external index -> variable id for the callback form (empty = identity)
-    std::map<std::vector<int>, std::unique_ptr<DiscGroup>> groups;
-    uint64_t clock = 0;
-    int64_t groups_built = 0, count_only = 0;
-    dev_buf<int32_t> iota;       // [N] 0..N-1, the values the radix sort permutes
-    dev_buf<uint32_t> keys[2];   // [N] configuration ids, unsorted / sorted
-    dev_buf<int32_t> first;      // [G] first sorted position of every configuration
-    dev_buf<char> sort_tmp;
-    dev_buf<double> shift_dev;   // the pilot means on the device, indexed by table column (Engine::ensure_full)
-    dev_buf<char> rowmajor;      // row-major mirror of the continuous columns for the gathered Gram of the groupings (Engine::ensure_full)
-    bool rowmajor_tried = false;
-    int64_t full_grams = 0;      // groupings whose full per-configuration moments were taken
-    size_t full_bytes_held = 0;  // host bytes of the cached full moments
-    // PBN_MI_TIMING=1: wall seconds per phase, printed when the handle is destroyed
-    double t_group = 0, t_device = 0, t_host = 0, t_prep = 0;
-    int64_t batches = 0;
-    // pbn_chisq_pvalue_batch (chisq_batch.hip): the byte mirror of the codes ([n_disc][ld8], built by the first batch when every code
-    // fits a byte), the grow-only descriptor / count buffers of a launch chunk and the host copy of the counts
-    dev_buf<uint8_t> codes8;
-    int64_t ld8 = 0;
-    int codes8_state = 0;        // 0 not tried yet, 1 built, -1 the codes need int32
-    dev_buf<chisq::Desc> cs_descs;
-    dev_buf<uint32_t> cs_counts;
-    std::vector<uint32_t> cs_host;
-    int64_t cs_device_tests = 0, cs_host_tests = 0, cs_threshold = CHISQ_BATCH_MIN_TESTS;
-};
-
-static inline double mi_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 namespace {
 
@@ -858,14 +785,6 @@ struct Engine {
         }
     }
 
-    void group_stats(const std::vector<int>& cont, const std::vector<int>& disc, int G, std::vector<double>& out) {
-        std::vector<Plan> one{plan(cont, disc)};
-        (void)G;
-        std::vector<std::vector<double>> o;
-        group_stats_many(one, o);
-        out.swap(o[0]);
-    }
-
     // MI(X; Y | Z) (mutual_information.cpp:926-1055 no conditioning, :1139-1312 one variable, :1391-1658 general);
     // every overload of the reference is the general formula with the matching emptiness of zD / zC.
     double mi(const Query& q, double* rows = nullptr) {
@@ -1011,175 +930,33 @@ struct Engine {
     }
 };
 
-// The host arithmetic a batch spreads over a few threads (PBN_MI_THREADS, at most 16 by default): finish(i) for i = 0 ... n - 1, test
-// i on thread i mod nth; the first exception of a worker is rethrown on the caller.
-template <typename F>
-void host_finish(int n, F&& finish) {
-    static const int max_threads = [] {
-        const int hw = (int)std::thread::hardware_concurrency();
-        const int nt = knob_int("PBN_MI_THREADS", std::min(hw > 0 ? hw : 1, 16));
-        return nt < 1 ? 1 : nt;
-    }();
-    const int nth = std::min(max_threads, n / 64);
-    if (nth <= 1) {
-        for (int i = 0; i < n; ++i) finish(i);
-        return;
-    }
-    std::vector<std::thread> pool;
-    std::vector<std::exception_ptr> errs((size_t)nth);
-    for (int w = 0; w < nth; ++w)
-        pool.emplace_back([&, w] {
-            try {
-                for (int i = w; i < n; i += nth) finish(i);
-            } catch (...) {
-                errs[w] = std::current_exception();
-            }
-        });
-    for (auto& th : pool) th.join();
-    for (auto& ep : errs)
-        if (ep) std::rethrow_exception(ep);
-}
-
-// ChiSquare's p-value from the cell counts of one contingency table (chi_square.cpp:8-139): c[i + j * cx + k * cx * cy] rows with
-// x = i, y = j and configuration k of the conditioning set.  The ONE text behind pbn_chisq_pvalue and pbn_chisq_pvalue_batch - never
-// inlined, so that both callers run the same instructions: equal counts give the same bits.
-__attribute__((noinline)) double chisq_from_counts(const double* counts, int cx, int cy, int zc, int n_cond) {
-    const int vc = cx * cy;
-    double statistic = 0;
-    for (int k = 0; k < zc; ++k) {
-        const double* c = counts + (size_t)k * vc;
-        std::vector<double> mx(cx, 0.0), my(cy, 0.0);
-        double tot = 0;
-        for (int i = 0; i < cx; ++i)
-            for (int j = 0; j < cy; ++j) { mx[i] += c[i + j * cx]; my[j] += c[i + j * cx]; tot += c[i + j * cx]; }
-        if (tot == 0) continue;
-        const double inv = 1.0 / tot;
-        for (int i = 0; i < cx; ++i)
-            for (int j = 0; j < cy; ++j) {
-                const double expected = mx[i] * my[j] * inv;
-                if (expected != 0) { const double dd = c[i + j * cx] - expected; statistic += dd * dd / expected; }
-            }
-    }
-    if (n_cond > 1 && statistic < 1.4901161193847656e-08) return 1.0;   // chi_square.cpp:130-134
-    const double df = (cx - 1.0) * (cy - 1.0) * zc;
-    return gamma_q(0.5 * df, 0.5 * statistic);
-}
-
-// pbn_debug_chisq (test aid, not part of the C ABI header; see its definition)
-std::atomic<int> g_chisq_capture{0};   // bit 0: record every batch call, bit 1: time its phases
-std::mutex g_chisq_mu;
-std::vector<int64_t> g_chisq_rec;
-double g_chisq_phase[5] = {0, 0, 0, 0, 0};   // seconds: request and descriptors, memset, kernel, download, host finish
-
-struct ChisqTest {   // one slot of a batch call
-    int m = 0;
-    int vars[chisq::MAX_VARS];   // variable ids, x, y, Z
-    int G = 0;
-    int where = -1;              // 1 device, 0 host, -1 refused (NaN)
-    int slices = 0, copies = 0;
-};
-
-// The device part of pbn_chisq_pvalue_batch: the tests `which` (all eligible), chunk by chunk - descriptors up, one memset, one launch,
-// the chunk's tables down, chisq_from_counts on the host threads.  `tables` (capture only) receives every test's integer table.
-void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vector<int>& which, const int* cond_off, double* out, int* width,
-                        std::vector<std::vector<uint32_t>>* tables) {
-    pbn_ctx* ctx = h->ctx;
-    HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int64_t N = h->N;
-    const bool timing = (g_chisq_capture.load() & 2) != 0;
-    double tp = mi_now();
-    auto phase = [&](int i) {
-        if (!timing) return;
-        HIP_CHECK(hipStreamSynchronize(st));
-        const double t = mi_now();
-        g_chisq_phase[i] += t - tp;
-        tp = t;
-    };
-    if (h->codes8_state == 0) {   // the byte mirror: a quarter of the bytes of every later pass
-        // built when every CODE fits a byte: card - 1, or card where the column has a null bucket, <= 255.  256 categories without a null
-        // still fit; their code 255 is also the byte that pads the mirror past N, which the kernel's row bound keeps out, not its value.
-        int max_code = 0;
-        for (int j = 0; j < h->n_disc; ++j) max_code = std::max(max_code, h->card[j] - 1 + (int)h->disc_null[j]);
-        h->codes8_state = -1;
-        static const bool allow = PBN_TUNE(CHISQ_BYTES, 1) != 0;
-        if (allow && max_code <= 255 && h->n_disc <= 65535) {
-            h->ld8 = ceil_div(N, chisq::MIRROR_ALIGN) * chisq::MIRROR_ALIGN;
-            h->codes8.alloc((size_t)h->ld8 * h->n_disc);
-            chisq::launch_byte_mirror(h->codes_dev.p, N, h->n_disc, h->codes8.p, h->ld8, st);
-            h->codes8_state = 1;
-        }
-    }
-    const bool bytes = h->codes8_state == 1;
-    *width = bytes ? 1 : 4;
-    static const int r_max = PBN_TUNE(CHISQ_COPIES, chisq::MAX_COPIES);
-    static const int blocks_per_cu = PBN_TUNE(CHISQ_BLOCKS_PER_CU, 8);
-    std::vector<chisq::Desc> descs;
-    for (size_t base = 0; base < which.size();) {
-        // a chunk: as many tests as keep the count buffer within CHISQ_CHUNK_CELLS
-        size_t end = base, cells = 0;
-        while (end < which.size() && end - base < ((size_t)1 << 18) && cells + (size_t)tests[which[end]].G <= CHISQ_CHUNK_CELLS) cells += (size_t)tests[which[end++]].G;
-        const int T = (int)(end - base);
-        // slices: enough workgroups to fill the chip when the chunk has few tests, while a slice's flush (G cells) stays small against
-        // its row work: at least max(4096, 8 G) rows per slice, slice bounds on multiples of SLICE_ALIGN
-        const int64_t want = std::max<int64_t>(1, ceil_div((int64_t)ctx->num_cus * blocks_per_cu, T));
-        descs.assign((size_t)T, chisq::Desc{});
-        int max_slices = 1, lds_words = 1;
-        size_t off = 0;
-        for (int i = 0; i < T; ++i) {
-            ChisqTest& t = tests[which[base + i]];
-            chisq::Desc& d = descs[i];
-            d.m = t.m; d.G = t.G;
-            int stride = 1;
-            for (int j = 0; j < t.m; ++j) {
-                d.col[j] = t.vars[j] - h->n_cont;
-                d.card[j] = h->card[d.col[j]];
-                d.stride[j] = stride;
-                stride *= d.card[j];
-            }
-            chisq::copies_for(t.G, r_max, &d.copies, &d.copy_stride);
-            const int64_t cap = std::max<int64_t>(1, N / std::max<int64_t>(4096, 8 * (int64_t)t.G));
-            const int64_t s = std::min<int64_t>(std::min(want, cap), 65535);
-            d.rows_per_slice = ceil_div(ceil_div(N, s), chisq::SLICE_ALIGN) * chisq::SLICE_ALIGN;
-            d.slices = (int)ceil_div(N, d.rows_per_slice);
-            d.row0 = 0; d.row1 = N;
-            d.table_off = (int64_t)off;
-            off += (size_t)t.G;
-            t.slices = d.slices; t.copies = d.copies;
-            max_slices = std::max(max_slices, d.slices);
-            lds_words = std::max(lds_words, d.copies * d.copy_stride);
-        }
-        h->cs_descs.reserve((size_t)T);
-        h->cs_counts.reserve(cells);
-        if (h->cs_host.size() < cells) h->cs_host.resize(cells);
-        HIP_CHECK(hipMemcpyAsync(h->cs_descs.p, descs.data(), (size_t)T * sizeof(chisq::Desc), hipMemcpyHostToDevice, st));
-        phase(0);
-        HIP_CHECK(hipMemsetAsync(h->cs_counts.p, 0, cells * sizeof(uint32_t), st));
-        phase(1);
-        chisq::launch_count(h->cs_descs.p, T, max_slices, lds_words, bytes, bytes ? (const void*)h->codes8.p : (const void*)h->codes_dev.p,
-                            bytes ? h->ld8 : N, h->cs_counts.p, st);
-        phase(2);
-        HIP_CHECK(hipMemcpyAsync(h->cs_host.data(), h->cs_counts.p, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));   // (the descriptors are read by then as well)
-        phase(3);
-        const uint32_t* all = h->cs_host.data();
-        host_finish(T, [&](int i) {
-            const int slot = which[base + i];
-            const ChisqTest& t = tests[slot];
-            const uint32_t* c = all + descs[i].table_off;
-            std::vector<double> cnt((size_t)t.G);
-            for (int g = 0; g < t.G; ++g) cnt[g] = (double)c[g];
-            const int cx = descs[i].card[0], cy = descs[i].card[1];
-            out[slot] = chisq_from_counts(cnt.data(), cx, cy, t.G / (cx * cy), cond_off[slot + 1] - cond_off[slot]);
-            if (tables) (*tables)[slot].assign(c, c + t.G);
-        });
-        if (timing) { const double t = mi_now(); g_chisq_phase[4] += t - tp; tp = t; }
-        h->cs_device_tests += T;
-        base = end;
-    }
-}
-
 }  // namespace
+
+// ---- what chisq.hip and lincor.hip use of this unit (mi_internal.hpp) ----------------------------------------------
+void pbn::mi::group_stats(pbn_mi* h, const std::vector<int>& cont, const std::vector<int>& disc, std::vector<double>& out) {
+    Engine e{h};
+    std::vector<Engine::Plan> one{e.plan(cont, disc)};
+    std::vector<std::vector<double>> o;
+    e.group_stats_many(one, o);
+    out.swap(o[0]);
+}
+
+// external indices -> variable ids, in place: THE reading of pbn_mi_set_order's order
+static bool map_indices(const pbn_mi* h, int n, int* v) {
+    if (h->order.empty()) return true;
+    const int no = (int)h->order.size();
+    for (int i = 0; i < n; ++i) {
+        if (v[i] < 0 || v[i] >= no) return false;
+        v[i] = h->order[v[i]];
+    }
+    return true;
+}
+
+bool pbn::mi::map_request(const pbn_mi* h, int v1, int v2, int n_cond, const int* cond, std::vector<int>& vars) {
+    vars.assign({v1, v2});
+    if (n_cond > 0) vars.insert(vars.end(), cond, cond + n_cond);
+    return map_indices(h, (int)vars.size(), vars.data());
+}
 
 extern "C" {
 
@@ -1272,70 +1049,20 @@ int pbn_mi_value(pbn_mi* h, int v1, int v2, int n_cond, const int* cond, double*
 // pbn_ci_pvalue_fn over a pbn_mi handle: P(chi2_df > 2 N MI) (mutual_information.cpp:1125-1137,1377-1389,1733-1750)
 double pbn_mi_pvalue(void* user, int v1, int v2, int n_cond, const int* cond) {
     pbn_mi* h = (pbn_mi*)user;
-    double mi = 0, df = 0;
-    std::vector<int> mapped;
-    if (h && !h->order.empty()) {
-        const int no = (int)h->order.size();
-        if (v1 < 0 || v2 < 0 || v1 >= no || v2 >= no) return std::nan("");
-        v1 = h->order[v1]; v2 = h->order[v2];
-        mapped.resize(n_cond);
-        for (int i = 0; i < n_cond; ++i) {
-            if (cond[i] < 0 || cond[i] >= no) return std::nan("");
-            mapped[i] = h->order[cond[i]];
-        }
-        cond = mapped.data();
-    }
-    double rows = 0;
+    double value = 0, df = 0, rows = 0;
+    bool in_order = true;
     const int rc = guarded([&] {
         if (!h || (n_cond > 0 && !cond)) throw invalid_error("pbn_mi_pvalue: null argument");
+        std::vector<int> vars;
+        in_order = mi::map_request(h, v1, v2, n_cond, cond, vars);
+        if (!in_order) return;   // an index outside the order: NaN, and pbn_last_error stays what it was
         Engine e{h};
-        const Query q = e.make(v1, v2, n_cond, cond);
-        mi = e.mi(q, &rows);
+        const Query q = e.make(vars[0], vars[1], (int)vars.size() - 2, vars.data() + 2);
+        value = e.mi(q, &rows);
         df = e.df(q);
     });
-    if (rc != PBN_OK) return std::nan("");
-    return gamma_q(0.5 * df, 0.5 * (mi * 2.0 * rows));
-}
-
-// LinearCorrelation::pvalue on a table with nulls (continuous/linearcorrelation.cpp:20-122, the pvalue_impl branch): the
-// covariance of [v1, v2, cond...] over the rows valid in all of them - one pass of the NaN-skipping moments kernel - then
-// the same partial-correlation t-test as the cached form, with `valid rows - 2 - |cond|` degrees of freedom.
-// pbn_ci_pvalue_fn signature over a pbn_mi handle whose variables are all continuous.
-double pbn_mi_lincor_pvalue(void* user, int v1, int v2, int n_cond, const int* cond) {
-    pbn_mi* h = (pbn_mi*)user;
-    double result = std::nan("");
-    (void)guarded([&] {
-        if (!h || (n_cond > 0 && !cond)) throw invalid_error("pbn_mi_lincor_pvalue: null argument");
-        std::vector<int> vars{v1, v2};
-        vars.insert(vars.end(), cond, cond + n_cond);
-        if (!h->order.empty())
-            for (int& v : vars) {
-                if (v < 0 || v >= (int)h->order.size()) throw invalid_error("LinearCorrelation: variable index out of range");
-                v = h->order[v];
-            }
-        for (int v : vars)
-            if (v < 0 || v >= h->n_cont) throw invalid_error("LinearCorrelation: variable is not continuous");
-        Engine e{h};
-        std::vector<double> st;
-        e.group_stats(vars, {}, 1, st);
-        const int c = (int)vars.size();
-        const double n = st[0];
-        if (!(n > c)) throw invalid_error("LinearCorrelation: not enough valid rows");
-        std::vector<double> cov((size_t)c * c);
-        int pos = 1 + c;
-        for (int i = 0; i < c; ++i)
-            for (int j = i; j < c; ++j) {
-                const double v = (st[pos++] - st[1 + i] * st[1 + j] / n) / (n - 1.0);
-                cov[i + (size_t)j * c] = cov[j + (size_t)i * c] = v;
-            }
-        pbn_lincor* lc = nullptr;
-        if (pbn_lincor_from_cov(c, (int64_t)n, cov.data(), &lc) != PBN_OK) throw device_error(pbn_last_error());
-        std::vector<int> zc(std::max(1, n_cond));
-        for (int i = 0; i < n_cond; ++i) zc[i] = 2 + i;
-        result = pbn_lincor_pvalue(lc, 0, 1, n_cond, zc.data());
-        pbn_lincor_destroy(lc);
-    });
-    return result;
+    if (rc != PBN_OK || !in_order) return std::nan("");
+    return gamma_q(0.5 * df, 0.5 * (value * 2.0 * rows));
 }
 
 // Batched form: n_tests independence tests in as few launches as scratch memory allows (pbn_ci_pvalue_batch_fn).
@@ -1346,18 +1073,14 @@ void pbn_mi_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, 
     (void)guarded([&] {
         if (!h || !v1 || !v2 || !cond_off || !out) throw invalid_error("pbn_mi_pvalue_batch: null argument");
         Engine e{h};
-        auto map = [&](int v) {
-            if (h->order.empty()) return v;
-            if (v < 0 || v >= (int)h->order.size()) throw invalid_error("MutualInformation: variable index out of range");
-            return h->order[v];
-        };
         std::vector<Query> qs(n_tests);
         std::vector<Engine::Plan> plans(n_tests);
-        std::vector<int> cm;
+        std::vector<int> vars;
         for (int i = 0; i < n_tests; ++i) {
-            cm.clear();
-            for (int j = cond_off[i]; j < cond_off[i + 1]; ++j) cm.push_back(map(cond[j]));
-            qs[i] = e.make(map(v1[i]), map(v2[i]), (int)cm.size(), cm.data());
+            const int k = cond_off[i + 1] - cond_off[i];
+            if (!mi::map_request(h, v1[i], v2[i], k, k > 0 ? cond + cond_off[i] : nullptr, vars))
+                throw invalid_error("MutualInformation: variable index out of range");
+            qs[i] = e.make(vars[0], vars[1], (int)vars.size() - 2, vars.data() + 2);
             plans[i] = e.plan(qs[i]);
         }
         std::vector<std::vector<double>> st;
@@ -1387,167 +1110,6 @@ int pbn_mi_set_order(pbn_mi* h, int n, const int* ids) {
     });
 }
 
-// ChiSquare::pvalue (learning/independences/discrete/chi_square.cpp:8-139) over the discrete columns of a pbn_mi handle:
-// Pearson's statistic summed over the configurations of the conditioning set, df = (|X|-1)(|Y|-1) prod |Z|.  Counts come
-// from the same device pass as the mutual information (no continuous statistics).  Expected counts are formed in
-// double; the reference multiplies two int marginals (chi_square.cpp:21,62,116), which overflows beyond ~46 000 rows
-// per cell pair.  pbn_ci_pvalue_fn signature, indices mapped through pbn_mi_set_order when set.
-double pbn_chisq_pvalue(void* user, int v1, int v2, int n_cond, const int* cond) {
-    pbn_mi* h = (pbn_mi*)user;
-    double result = std::nan("");
-    const int rc = guarded([&] {
-        if (!h || (n_cond > 0 && !cond)) throw invalid_error("pbn_chisq_pvalue: null argument");
-        std::vector<int> vars{v1, v2};
-        vars.insert(vars.end(), cond, cond + n_cond);
-        if (!h->order.empty())
-            for (int& v : vars) {
-                if (v < 0 || v >= (int)h->order.size()) throw invalid_error("ChiSquare: variable index out of range");
-                v = h->order[v];
-            }
-        Engine e{h};
-        int64_t G = 1;
-        for (int v : vars) {
-            if (v < h->n_cont || v >= h->n_cont + h->n_disc) throw invalid_error("ChiSquare: variable is not categorical");
-            G *= e.card(v);
-            if (G > (1 << 24)) throw invalid_error("ChiSquare: too many discrete configurations");
-        }
-        std::vector<double> st;
-        e.group_stats({}, vars, (int)G, st);
-        const int cx = e.card(vars[0]), cy = e.card(vars[1]);
-        result = chisq_from_counts(st.data(), cx, cy, (int)(G / (cx * cy)), n_cond);
-    });
-    return rc == PBN_OK ? result : std::nan("");
-}
-
-// ChiSquare::pvalue for many tests per call (chi_square.cpp:8-139 on the joint_counts layout of discrete_indices.cpp:134-150;
-// pbn_ci_pvalue_batch_fn, user = the pbn_mi handle, indices mapped through pbn_mi_set_order when set).  Tests of at most
-// chisq::MAX_CELLS cells and chisq::MAX_COND conditioning variables are counted by chisq_batch.hip - no DiscGroup, no sort, no
-// permutation - and finished by chisq_from_counts, the scalar routine's own arithmetic on the same integers: out[i] is bit-identical to
-// pbn_chisq_pvalue of test i, wherever it ran.  Every other test, and every test of a call with fewer eligible tests than the handle's
-// threshold, goes through pbn_chisq_pvalue here; so does a test with a bad index or a non-categorical variable, which that routine
-// refuses with NaN and pbn_last_error.  One NaN comes WITHOUT pbn_last_error, from the scalar routine and from here alike: a test of zero
-// degrees of freedom (a one-category x or y), where chisq_from_counts answers 1 when its statistic is exactly 0 and NaN when rounding
-// left it a few ulps above (gamma_q(0, tiny)).
-void pbn_chisq_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond, double* out) {
-    pbn_mi* h = (pbn_mi*)user;
-    if (!out || n_tests <= 0) return;
-    for (int i = 0; i < n_tests; ++i) out[i] = std::nan("");
-    if (!h || !v1 || !v2 || !cond_off) { set_last_error("pbn_chisq_pvalue_batch: null argument"); return; }
-    (void)guarded(mu_of(h), [&] {
-        const int64_t groups0 = h->groups_built;
-        const int nv = h->n_cont + h->n_disc;
-        std::vector<ChisqTest> tests((size_t)n_tests);
-        std::vector<int> device;
-        for (int i = 0; i < n_tests; ++i) {
-            ChisqTest& t = tests[i];
-            const int k = cond_off[i + 1] - cond_off[i];
-            if (k < 0 || (k > 0 && !cond)) continue;   // refused by the scalar routine below
-            t.where = 0;
-            if (k > chisq::MAX_COND || h->N <= 0) continue;
-            t.m = 2 + k;
-            bool ok = true;
-            int64_t G = 1;
-            for (int j = 0; j < t.m && ok; ++j) {
-                int v = j == 0 ? v1[i] : (j == 1 ? v2[i] : cond[cond_off[i] + j - 2]);
-                if (!h->order.empty()) {
-                    if (v < 0 || v >= (int)h->order.size()) { ok = false; break; }
-                    v = h->order[v];
-                }
-                if (v < h->n_cont || v >= nv) { ok = false; break; }
-                for (int q = 0; q < j; ++q) ok = ok && t.vars[q] != v;   // a repeated variable: the scalar routine's own reading of it
-                t.vars[j] = v;
-                G *= h->card[v - h->n_cont];
-                ok = ok && G >= 1 && G <= chisq::MAX_CELLS;
-            }
-            if (!ok) continue;
-            t.G = (int)G;
-            device.push_back(i);
-        }
-        if ((int64_t)device.size() < h->cs_threshold) device.clear();
-        const bool capture = (g_chisq_capture.load() & 1) != 0;
-        std::vector<std::vector<uint32_t>> tables;
-        if (capture) tables.resize((size_t)n_tests);
-        int width = 0;
-        if (!device.empty()) {
-            chisq_batch_device(h, tests, device, cond_off, out, &width, capture ? &tables : nullptr);
-            for (int i : device) tests[i].where = 1;
-        }
-        const bool timing = (g_chisq_capture.load() & 2) != 0;
-        const double th0 = mi_now();
-        int64_t looped = 0;
-        for (int i = 0; i < n_tests; ++i) {
-            if (tests[i].where == 1) continue;
-            const int k = cond_off[i + 1] - cond_off[i];
-            out[i] = pbn_chisq_pvalue(user, v1[i], v2[i], k, (cond && k > 0) ? cond + cond_off[i] : nullptr);
-            if (out[i] == out[i]) ++looped; else tests[i].where = -1;
-        }
-        if (timing) g_chisq_phase[4] += mi_now() - th0;
-        h->cs_host_tests += looped;
-        if (capture) {
-            std::vector<int64_t> r{3, n_tests, groups0, h->groups_built};
-            for (int i = 0; i < n_tests; ++i) {
-                const ChisqTest& t = tests[i];
-                const bool dev = t.where == 1;
-                r.insert(r.end(), {(int64_t)t.where, dev ? width : 0, dev ? t.slices : 0, dev ? t.copies : 0, (int64_t)t.G, (int64_t)tables[i].size()});
-                r.insert(r.end(), tables[i].begin(), tables[i].end());
-            }
-            std::lock_guard<std::mutex> lk(g_chisq_mu);
-            g_chisq_rec.insert(g_chisq_rec.end(), r.begin(), r.end());
-        }
-    });
-}
-
-int pbn_chisq_batch_stats(const pbn_mi* h, int64_t* device_tests, int64_t* host_tests) {
-    return guarded(mu_of(h), [&] {
-        if (!h) throw invalid_error("pbn_chisq_batch_stats: null argument");
-        if (device_tests) *device_tests = h->cs_device_tests;
-        if (host_tests) *host_tests = h->cs_host_tests;
-    });
-}
-
-int pbn_chisq_set_batch_threshold(pbn_mi* h, int64_t min_tests) {
-    return guarded(mu_of(h), [&] {
-        if (!h || min_tests < 0) throw invalid_error("pbn_chisq_set_batch_threshold: bad argument");
-        h->cs_threshold = min_tests;
-    });
-}
-
-int pbn_chisq_batch_max_cells(void) { return chisq::MAX_CELLS; }
-int pbn_chisq_batch_max_cond(void) { return chisq::MAX_COND; }
-
-// pbn_debug_chisq (test aid, not part of the C ABI header).  op 1 arms the capture and clears it, op 0 disarms everything and clears,
-// op 2 copies up to `cap` int64 of the records into out and returns how many are held.  While armed, every pbn_chisq_pvalue_batch call
-// appends one record:
-//   3, n_tests, the handle's count of row groupings built before the call and after it, then per test in call order
-//      where (1 = counted on the device, 0 = looped on the host, -1 = refused with NaN), code width in bytes (1 = the byte mirror, 4 =
-//      int32; 0 off the device), slices, R (the replicated LDS sub-tables; both 0 off the device), G (cells; 0 when the test was not
-//      sized for the device), n (G on the device, else 0), and the n cell counts as copied back from the device, x fastest.
-// op 3 arms the phase clock and clears it, op 4 copies the 5 accumulated phase times in nanoseconds into out (request and descriptors,
-// memset, kernel, download, host finish): while it runs a batch call synchronises the stream after every phase.
-// Unarmed, a call pays two flag tests; no kernel and no result depends on any of it.
-int64_t pbn_debug_chisq(int op, int64_t* out, int64_t cap) {
-    std::lock_guard<std::mutex> lk(g_chisq_mu);
-    if (op == 0 || op == 1) {
-        g_chisq_rec.clear();
-        g_chisq_capture.store(op == 1 ? (g_chisq_capture.load() | 1) : 0);
-        return 0;
-    }
-    if (op == 2) {
-        for (int64_t i = 0; out && i < (int64_t)g_chisq_rec.size() && i < cap; ++i) out[i] = g_chisq_rec[(size_t)i];
-        return (int64_t)g_chisq_rec.size();
-    }
-    if (op == 3) {
-        for (double& p : g_chisq_phase) p = 0;
-        g_chisq_capture.store(g_chisq_capture.load() | 2);
-        return 0;
-    }
-    if (op == 4) {
-        for (int i = 0; out && i < 5 && i < cap; ++i) out[i] = (int64_t)(g_chisq_phase[i] * 1e9);
-        return 5;
-    }
-    return -1;
-}
-
 // Joint counts of discrete variables (factors/discrete/discrete_indices.cpp:134-150 joint_counts): out[sum_i code_i *
 // stride_i], the first variable fastest, prod(cardinality) entries, rows with a null in any of the variables left out.
 // The counts are the segment lengths of the cached row grouping of that variable set.
@@ -1555,16 +1117,11 @@ int pbn_mi_counts(pbn_mi* h, int n_vars, const int* vars, double* out) {
     return guarded(mu_of(h), [&] {
         if (!h || !vars || !out || n_vars < 1) throw invalid_error("pbn_mi_counts: null argument");
         std::vector<int> v(vars, vars + n_vars);
-        if (!h->order.empty())
-            for (int& x : v) {
-                if (x < 0 || x >= (int)h->order.size()) throw invalid_error("pbn_mi_counts: variable index out of range");
-                x = h->order[x];
-            }
+        if (!map_indices(h, n_vars, v.data())) throw invalid_error("pbn_mi_counts: variable index out of range");
         for (int x : v)
             if (x < h->n_cont || x >= h->n_cont + h->n_disc) throw invalid_error("pbn_mi_counts: variable is not categorical");
-        Engine e{h};
         std::vector<double> st;
-        e.group_stats({}, v, 1, st);
+        mi::group_stats(h, {}, v, st);
         std::copy(st.begin(), st.end(), out);
     });
 }

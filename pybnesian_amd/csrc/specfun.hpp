@@ -1,4 +1,4 @@
-// Special functions shared by the host side of the independence tests (mi.hip: chi-square p-values; rcot.hip: the gamma
+// Special functions shared by the host side of the independence tests (mi.hip, chisq.hip: chi-square p-values; rcot.hip: the gamma
 // tails of the weighted chi-square sums).
 #pragma once
 #include <cmath>

@@ -458,7 +458,7 @@ class ChiSquare(MutualInformation):
 
     def _ci_batch_callback(self):
         """Batched native callback (same handle / index order as _ci_callback): the contingency tables of all tests of a call are
-        counted in one device pass (csrc/chisq_batch.hip); p-values are bit-identical to pvalue()."""
+        counted in one device pass (csrc/chisq.hip); p-values are bit-identical to pvalue()."""
         return C.cast(_lib.load().pbn_chisq_pvalue_batch, C.c_void_p)
 
     def batch_stats(self):

@@ -1,9 +1,9 @@
-"""GPU tier: the batch form of ChiSquare (csrc/chisq_batch.hip behind pbn_chisq_pvalue_batch).
+"""GPU tier: the batch form of ChiSquare (csrc/chisq.hip behind pbn_chisq_pvalue_batch).
 
 The contract has no tolerance in it.  The integer table the kernel counts must equal np.bincount of the keys over the rows valid in the
 test's variables, and the p-value - the scalar routine's own arithmetic on those integers - must equal ChiSquare.pvalue of the same
 test on the same handle bit for bit, whether the test was counted on the device or looped on the host.  The test aid pbn_debug_chisq
-(layout at its definition in csrc/mi.hip) says where every test ran, with which code width, in how many slices and LDS copies, and hands
+(layout at its definition in csrc/chisq.hip) says where every test ran, with which code width, in how many slices and LDS copies, and hands
 back the table as it came off the device.
 
 One case cannot go through ChiSquare.pvalue: a one-category x or y has zero degrees of freedom, where the scalar routine answers 1 or -

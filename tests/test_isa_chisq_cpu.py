@@ -1,4 +1,4 @@
-"""CPU tier (cross-compile only): ISA invariants of the batched joint-count kernel of ChiSquare (csrc/chisq_batch.hip).
+"""CPU tier (cross-compile only): ISA invariants of the batched joint-count kernel of ChiSquare (csrc/chisq.hip).
 
 The kernel is latency-bound on its code loads and on LDS adds: what hides both is eight waves per SIMD, which needs at most 64 VGPRs
 and no scratch memory, and LDS adds that return nothing (a returning add makes the wave wait for a value nobody reads).  None of that
@@ -15,9 +15,9 @@ CSRC = os.path.join(ROOT, "pybnesian_amd", "csrc")
 
 @pytest.fixture(scope="module")
 def count_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "chisq_batch.s"
+    out = tmp_path_factory.mktemp("isa") / "chisq.s"
     p = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                        "chisq_batch.hip", "-o", str(out)], cwd=CSRC, capture_output=True, text=True, timeout=900)
+                        "chisq.hip", "-o", str(out)], cwd=CSRC, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     return out.read_text()
 

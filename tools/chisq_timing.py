@@ -6,7 +6,7 @@
               batch keeps no cache, so a repeated variable set costs it what a fresh one costs).  The loop is
               timed on tests whose variable sets the handle has not grouped yet - a repeated set is served by the grouping cache and
               says nothing about a skeleton level - so it gets at most 200 tests per repetition and its rate is used for every size.
-              CHISQ_BATCH_MIN_TESTS in csrc/mi.hip is the smallest size from which the device wins for every row count and k.
+              CHISQ_BATCH_MIN_TESTS in csrc/chisq.hip is the smallest size from which the device wins for every row count and k.
   widths      the same batch on the byte mirror and on int32 codes (a 300-category column added), 1e6 rows
   contention  x, y constant columns of cardinality 2 - every row in one cell - against uniform columns, 1e6 rows, with the LDS copies as
               built (32) and capped at 1, 8 and 16 (needs the experiments build: PBN_LIB=.../libpbn_hip_exp.so; the contention_r<N>
