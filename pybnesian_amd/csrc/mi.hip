@@ -8,6 +8,7 @@
 // the discrete variables involved, the count and the pilot-shifted first and second moments of the continuous ones;
 // moments are additive, so every pooled covariance is a sum of per-configuration moments on the host.
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -33,6 +34,10 @@ using namespace pbn;
 #define MI_GROUP_CACHE 1024       // cached row groupings (one per set of discrete variables), least recently used out
 
 namespace {
+
+// one record per plan of pbn_debug_mi_moments (test aid; the layout is documented at its definition)
+enum { DBG_PATH, DBG_C, DBG_NULLS, DBG_DTYPE, DBG_G, DBG_WINDOWS, DBG_NBLOCKS, DBG_CHUNKS, DBG_ROWS, DBG_NCT, DBG_FORM, DBG_NBLK, DBG_LAUNCHED,
+       DBG_ORDER, DBG_GRID_X, DBG_BATCH, DBG_FIELDS };
 
 struct GroupArgs {
     const void* base;
@@ -310,7 +315,7 @@ struct Engine {
 
     // per-configuration statistics (count, sums, upper-triangle products of the pilot-shifted continuous variables) of
     // several tests in ONE launch: grid row = test, so launch / sync latency is paid once per batch
-    void group_stats_device(const std::vector<const Plan*>& plans, std::vector<std::vector<double>>& outs) {
+    void group_stats_device(const std::vector<const Plan*>& plans, std::vector<std::vector<double>>& outs, int64_t* shape = nullptr) {
         pbn_ctx* ctx = h->ctx;
         HIP_CHECK(hipSetDevice(ctx->device));
         const int64_t N = h->N, chunks = ceil_div(N, 64);
@@ -365,13 +370,16 @@ struct Engine {
         }
         h->device_passes += B;
         ++h->device_launches;
+        if (shape) { shape[0] = nblocks; shape[1] = ceil_div(chunks, nblocks); shape[2] = B; }
     }
 
     // statistics of a list of plans: launch rows bounded by scratch memory.  A test with more configurations than fit
     // the LDS accumulators is covered by several rows, each accumulating one window of configurations (rows of other
     // windows are skipped), stitched back together here - still device only.
-    void group_stats_legacy(const std::vector<Plan>& plans, std::vector<std::vector<double>>& outs) {
+    // info (test aid, nullable): per plan its windows and the launch of the first of them - nblocks, chunks_per_block, launch rows
+    void group_stats_legacy(const std::vector<Plan>& plans, std::vector<std::vector<double>>& outs, std::vector<std::array<int64_t, 4>>* info = nullptr) {
         outs.assign(plans.size(), {});
+        if (info) info->assign(plans.size(), {0, 0, 0, 0});
         if (h->N <= 0) { for (size_t t = 0; t < plans.size(); ++t) outs[t].assign((size_t)plans[t].G * plans[t].stats, 0.0); return; }
         const int64_t chunks = ceil_div(h->N, 64);
         std::vector<Plan> rows;                 // launch rows (windows)
@@ -394,10 +402,15 @@ struct Engine {
         auto flush = [&] {
             if (cur.empty()) return;
             std::vector<std::vector<double>> o(cur.size());
-            group_stats_device(cur, o);
+            int64_t shape[3] = {0, 0, 0};
+            group_stats_device(cur, o, info ? shape : nullptr);
             for (size_t i = 0; i < cur.size(); ++i) {
                 const auto [t, g0] = row_of[cur_idx[i]];
                 std::copy(o[i].begin(), o[i].end(), outs[t].begin() + (size_t)g0 * plans[t].stats);
+                if (info) {
+                    std::array<int64_t, 4>& f = (*info)[t];
+                    if (f[0]++ == 0) { f[1] = shape[0]; f[2] = shape[1]; f[3] = shape[2]; }
+                }
             }
             cur.clear(); cur_idx.clear(); cur_doubles = 0;
         };
@@ -542,6 +555,7 @@ struct Engine {
         static const int order = PBN_TUNE(MI_GRAM_ORDER, 2);
         dev_buf<int32_t> ordered;
         int nlaunch = g.nblk;
+        g.full_order = 2;
         if (order != 0 && g.G > 1) {
             int T = 1;
             for (int cg = 0; cg < g.G; ++cg) T = std::max(T, g.blk_off[cg + 1] - g.blk_off[cg]);
@@ -582,11 +596,14 @@ struct Engine {
                     for (int32_t slot : cell[(size_t)st]) piece(t, slot);
             }
             nlaunch = (int)(t.size() / 4);
+            g.full_order = aligned ? 1 : 0;
             ordered.alloc(t.size());
             HIP_CHECK(hipMemcpyAsync(ordered.p, t.data(), t.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
             HIP_CHECK(hipStreamSynchronize(ctx->stream));   // t is a local
             a.blk = ordered.p;
         }
+        g.full_form = a.rows ? (a.rowmajor ? 1 : 0) : 2;
+        g.full_launched = nlaunch;
         launch_gram_segments(a, h->table->dtype, nlaunch, g.blk.p + 4 * (size_t)g.nblk, g.G, out, ctx->stream);
         std::vector<double> hs((size_t)g.G * WS);
         HIP_CHECK(hipMemcpyAsync(hs.data(), out, hs.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -659,6 +676,10 @@ struct Engine {
             a.nblk = g.nblk; a.G = g.G;
             a.partial = dpart + po; a.out = dout + oo;
             po += (size_t)g.nblk * S; oo += (size_t)g.G * S;
+            if (h->dbg) {
+                int64_t* rec = h->dbg->data() + items[i].first * DBG_FIELDS;
+                rec[DBG_PATH] = 2; rec[DBG_NULLS] = nulls; rec[DBG_NBLK] = g.nblk; rec[DBG_GRID_X] = max_nblk; rec[DBG_BATCH] = B;
+            }
         }
         HIP_CHECK(hipMemcpyAsync(base, descs.data(), (size_t)B * sizeof(SortedArgs), hipMemcpyHostToDevice, ctx->stream));
         const bool f64 = h->table->dtype == PBN_F64;
@@ -713,6 +734,10 @@ struct Engine {
         std::vector<std::vector<std::pair<size_t, DiscGroup*>>> by_c(2 * MI_SORTED_MAX_CONT + 2);   // index 2 c + (continuous nulls ? 1 : 0)
         for (size_t t = 0; t < plans.size(); ++t) {
             const Plan& p = plans[t];
+            if (h->dbg) {
+                int64_t* rec = h->dbg->data() + t * DBG_FIELDS;
+                rec[DBG_C] = p.c; rec[DBG_G] = p.G; rec[DBG_DTYPE] = h->table ? (int64_t)dtype_size(h->table->dtype) : 0;
+            }
             if (p.c > MI_SORTED_MAX_CONT || p.G > (1 << 22)) {
                 if (h->any_null) throw invalid_error("MutualInformation: tables with nulls support at most 16 continuous variables per test");
                 legacy.push_back(p); legacy_idx.push_back(t); continue;
@@ -755,6 +780,11 @@ struct Engine {
             if (!nulls && full_applies(g)) {   // entries of the grouping's full moments
                 ensure_full(g);
                 const int nc = h->n_cont;
+                if (h->dbg) {
+                    int64_t* rec = h->dbg->data() + t * DBG_FIELDS;
+                    rec[DBG_PATH] = 1; rec[DBG_NCT] = (nc + 15) / 16; rec[DBG_FORM] = g.full_form; rec[DBG_NBLK] = g.nblk;
+                    rec[DBG_LAUNCHED] = g.full_launched; rec[DBG_ORDER] = g.full_order;
+                }
                 for (int cg = 0; cg < g.G; ++cg) {
                     if (map[cg] < 0) continue;
                     double* dst = outs[t].data() + (size_t)map[cg] * p.stats + 1;
@@ -779,9 +809,16 @@ struct Engine {
         if (!legacy.empty()) {
             std::vector<std::vector<double>> lo;
             const double tl = mi_now();
-            group_stats_legacy(legacy, lo);
+            std::vector<std::array<int64_t, 4>> info;
+            group_stats_legacy(legacy, lo, h->dbg ? &info : nullptr);
             h->t_device += mi_now() - tl;
-            for (size_t i = 0; i < legacy.size(); ++i) outs[legacy_idx[i]].swap(lo[i]);
+            for (size_t i = 0; i < legacy.size(); ++i) {
+                outs[legacy_idx[i]].swap(lo[i]);
+                if (h->dbg) {
+                    int64_t* rec = h->dbg->data() + legacy_idx[i] * DBG_FIELDS;
+                    rec[DBG_PATH] = 3; rec[DBG_WINDOWS] = info[i][0]; rec[DBG_NBLOCKS] = info[i][1]; rec[DBG_CHUNKS] = info[i][2]; rec[DBG_ROWS] = info[i][3];
+                }
+            }
         }
     }
 
@@ -1123,6 +1160,83 @@ int pbn_mi_counts(pbn_mi* h, int n_vars, const int* vars, double* out) {
         std::vector<double> st;
         mi::group_stats(h, {}, v, st);
         std::copy(st.begin(), st.end(), out);
+    });
+}
+
+// ---- test aids (not part of the C ABI header) -----------------------------------------------------------------------
+// pbn_debug_mi_moments: the raw moments of a batch of plans and the device path that served each of them.  Plan i is the
+// continuous variable ids cont[cont_off[i] .. cont_off[i + 1]) and the discrete ones disc[disc_off[i] .. disc_off[i + 1]) (offset
+// arrays of n_plans + 1 entries, like pbn_mi_pvalue_batch's cond_off; variable ids, pbn_mi_set_order does not apply).  The batch
+// goes through Engine::group_stats_many in ONE call, as pbn_mi_pvalue_batch's does.  out receives up to `cap` doubles: the plans'
+// statistics one after the other, per plan G x stats with the first discrete variable the fastest index and per configuration
+// [count, c sums, c (c + 1) / 2 products for i <= j] of the pilot-shifted columns.  rec (nullable) receives 16 int64 per plan:
+//   0 path: 0 counts only (segment lengths, no data pass), 1 entries of the grouping's full Gram (ensure_full), 2 the per-test sorted
+//     kernels (moments_sorted_kernel), 3 the LDS-cell kernel (group_moments_kernel)
+//   1 c, the plan's continuous variables (C of moments_sorted_kernel)   2 the NULLS flag of the sorted kernel
+//   3 bytes of a table element (8 / 4; 0 without a table)              4 G
+//   5 .. 8 (path 3) windows of the plan; nblocks, chunks_per_block and grid rows of the launch that held its first window
+//   9 .. 13 (path 1) NCT; the kernels: 0 gram_gring_kernel gathering from the columns, 1 the same through the row-major mirror, 2 the
+//     contiguous gram_glds kernels (no discrete variable); the grouping's nblk; the blocks launched, padding included; the order of
+//     the pieces: 0 stripe-major, 1 stripe-major aligned in groups of 8 with padding blocks, 2 the partial slots' own (G == 1)
+//   11, 14, 15 (path 2) the grouping's nblk; grid.x (the largest nblk of the launch) and grid.y (its tests)
+// Returns the doubles all plans hold together, or -1 after an error (pbn_last_error).  The records cost the product path one pointer
+// test per plan and launch, and ensure_full three stores per grouping; no kernel and no result depends on them.
+int64_t pbn_debug_mi_moments(pbn_mi* h, int n_plans, const int* cont_off, const int* cont, const int* disc_off, const int* disc, double* out,
+                             int64_t cap, int64_t* rec) {
+    int64_t total = 0;
+    const int rc = guarded(mu_of(h), [&] {
+        if (!h || n_plans < 0 || !cont_off || !disc_off) throw invalid_error("pbn_debug_mi_moments: null argument");
+        Engine e{h};
+        std::vector<Engine::Plan> plans(n_plans);
+        for (int i = 0; i < n_plans; ++i) {
+            std::vector<int> c, d;
+            if (cont_off[i + 1] > cont_off[i]) c.assign(cont + cont_off[i], cont + cont_off[i + 1]);
+            if (disc_off[i + 1] > disc_off[i]) d.assign(disc + disc_off[i], disc + disc_off[i + 1]);
+            for (int v : c) if (v < 0 || v >= h->n_cont) throw invalid_error("pbn_debug_mi_moments: not a continuous variable");
+            for (int v : d) if (v < h->n_cont || v >= h->n_cont + h->n_disc) throw invalid_error("pbn_debug_mi_moments: not a discrete variable");
+            plans[i] = e.plan(c, d);
+        }
+        std::vector<int64_t> recs((size_t)n_plans * DBG_FIELDS, 0);
+        std::vector<std::vector<double>> st;
+        h->dbg = &recs;
+        try { e.group_stats_many(plans, st); } catch (...) { h->dbg = nullptr; throw; }
+        h->dbg = nullptr;
+        for (int i = 0; i < n_plans; ++i)
+            for (double v : st[i]) { if (out && total < cap) out[total] = v; ++total; }
+        if (rec) std::copy(recs.begin(), recs.end(), rec);
+    });
+    return rc == PBN_OK ? total : -1;
+}
+
+// pbn_debug_mi_full: all moments of the grouping of the discrete variables vars (ids, sorted ascending; none: the whole table) as
+// ensure_full unpacks them - S[G][n_cont] sums and P[G][n_cont][n_cont] products of the pilot-shifted columns, configurations in the
+// grouping's order (first variable fastest).  rec (nullable): fields 9 .. 13 of pbn_debug_mi_moments' record.  Returns G, 0 when the
+// full Gram does not apply to this grouping (nothing is written), -1 after an error.
+int64_t pbn_debug_mi_full(pbn_mi* h, int n_vars, const int* vars, double* S, double* P, int64_t* rec) {
+    int64_t G = 0;
+    const int rc = guarded(mu_of(h), [&] {
+        if (!h || (n_vars > 0 && !vars)) throw invalid_error("pbn_debug_mi_full: null argument");
+        std::vector<int> v(vars, vars + n_vars);
+        for (int i = 0; i < n_vars; ++i)
+            if (v[i] < h->n_cont || v[i] >= h->n_cont + h->n_disc || (i > 0 && v[i] <= v[i - 1])) throw invalid_error("pbn_debug_mi_full: sorted discrete variable ids");
+        if (h->N <= 0) return;
+        Engine e{h};
+        DiscGroup& g = e.group_for(v);
+        if (!e.full_applies(g)) return;
+        e.ensure_full(g);
+        if (S) std::copy(g.fullS.begin(), g.fullS.end(), S);
+        if (P) std::copy(g.fullP.begin(), g.fullP.end(), P);
+        if (rec) { rec[0] = (h->n_cont + 15) / 16; rec[1] = g.full_form; rec[2] = g.nblk; rec[3] = g.full_launched; rec[4] = g.full_order; }
+        G = g.G;
+    });
+    return rc == PBN_OK ? G : -1;
+}
+
+// pbn_debug_mi_shifts: the handle's pilot shifts, n_cont doubles.
+int pbn_debug_mi_shifts(const pbn_mi* h, double* out) {
+    return guarded(mu_of(h), [&] {
+        if (!h || !out) throw invalid_error("pbn_debug_mi_shifts: null argument");
+        std::copy(h->shift.begin(), h->shift.end(), out);
     });
 }
 

@@ -28,6 +28,10 @@ struct DiscGroup {
     // this set of discrete variables reads its moments out of them
     bool full_ready = false;
     std::vector<double> fullS, fullP;   // [G][nc], [G][nc][nc]
+    // how ensure_full launched the pass (read by the test aid pbn_debug_mi_moments only): the kernel family - 0 gram_gring_kernel gathering
+    // from the columns, 1 the same through the row-major mirror, 2 the contiguous gram_glds kernels -, the blocks launched (padding
+    // included) and the order of the pieces - 0 stripe-major, 1 stripe-major aligned in groups of 8, 2 the partial slots' own
+    int full_form = -1, full_launched = 0, full_order = -1;
 };
 
 struct pbn_mi {
@@ -58,6 +62,8 @@ struct pbn_mi {
     // PBN_MI_TIMING=1: wall seconds per phase, printed when the handle is destroyed
     double t_group = 0, t_device = 0, t_host = 0, t_prep = 0;
     int64_t batches = 0;
+    // test aid (pbn_debug_mi_moments, mi.hip): non-null only inside its call - one record per plan of the batch, filled by group_stats_many
+    std::vector<int64_t>* dbg = nullptr;
     // pbn_chisq_pvalue_batch (chisq.hip): the byte mirror of the codes ([n_disc][ld8], built by the first batch when every code fits a
     // byte), the grow-only descriptor / count buffers of a launch chunk and the host copy of the counts
     struct ChisqState {
