@@ -182,7 +182,8 @@ typedef enum {
     PBN_SCORE_BIC = 0,    /* learning/scores/bic.cpp:12-27                                      */
     PBN_SCORE_BGE = 1,    /* learning/scores/bge.hpp:154-234; params = iss_mu, iss_w, total_nodes[, nu x n] */
     PBN_SCORE_CVLIK = 2,  /* learning/scores/cv_likelihood.cpp:11-25                            */
-    PBN_SCORE_HOLDOUT = 3 /* learning/scores/holdout_likelihood.cpp:14-23 (ValidatedScore::vlocal_score) */
+    PBN_SCORE_HOLDOUT = 3,/* learning/scores/holdout_likelihood.cpp:14-23 (ValidatedScore::vlocal_score) */
+    PBN_SCORE_BDE = 4     /* learning/scores/bde.cpp:5-47; params = iss; PBN_NODE_DISCRETE, discrete parents only  */
 } pbn_score_kind;
 typedef enum { PBN_NODE_LG = 0, PBN_NODE_CKDE = 1, PBN_NODE_DISCRETE = 2 } pbn_node_type; /* LinearGaussianCPDType / CKDEType / DiscreteFactorType */
 
@@ -212,6 +213,17 @@ void pbn_scoredata_destroy(pbn_scoredata* sd);
  * a continuous column with discrete parents is scored as CLinearGaussianCPD / HCKDE (DiscreteAdaptator.hpp:201-348),
  * a discrete column (node type PBN_NODE_DISCRETE, discrete parents only) as DiscreteFactor. */
 int pbn_scoredata_set_discrete(pbn_scoredata* sd, int n_disc, const int32_t* const* codes, const int* cardinality);
+/* Score data of a table WITHOUT continuous columns (the DataFrame of a DiscreteBN under BIC / CVLikelihood / HoldoutLikelihood /
+ * ValidatedLikelihood / BDe: learning/scores/bic.cpp:66-96, cv_likelihood.cpp:5-25 with learning/parameters/
+ * mle_DiscreteFactor.cpp:5-41, bde.cpp:5-47): the split layout pbn_scoredata_create gives the same rows, split, k, seed and ratio,
+ * no table, no moments.  The discrete columns are ids 0 .. n_disc-1 once pbn_scoredata_set_discrete attached them; every entry
+ * point that needs a table (the moments, BGe, continuous candidates, pbn_scoredata_set_comm) answers PBN_ERR_INVALID. */
+int pbn_scoredata_create_discrete(pbn_ctx* ctx, int64_t n_rows, int split, int k, uint32_t seed, double test_ratio,
+                                  pbn_scoredata** out);
+/* The discrete candidates of pbn_score_batch (variable and parents all dictionary columns) get the joint counts of
+ * factors/discrete/discrete_indices.cpp:134-150 for all their families in one device pass: cumulative (family, region) tables counted
+ * on the device and by the host loop (tables above 2^20 cells, more than 7 parents, PBN_DISCRETE_COUNTS=0), and kernel launches. */
+int pbn_scoredata_discrete_stats(const pbn_scoredata* sd, int64_t* device_units, int64_t* host_units, int64_t* launches);
 /* BIC / BGe on tables with nulls: masks[c] = byte array (1 = valid) of continuous column c in source row order, or
  * NULL when the column has no nulls (valid_rows / combined_bitmap semantics of bic.cpp:12-27, bge.hpp:184-234). */
 int pbn_scoredata_set_validity(pbn_scoredata* sd, const uint8_t* const* masks);

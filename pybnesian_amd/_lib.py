@@ -17,7 +17,7 @@ PBN_BW_FULL, PBN_BW_DIAG = 0, 1
 PBN_SEL_NORMAL_REFERENCE, PBN_SEL_SCOTT = 0, 1
 PBN_K_PACK, PBN_K_SWEEP, PBN_K_FINISH, PBN_K_GRAM, PBN_K_MOMENT, PBN_K_RCOT_PROD = 0, 1, 2, 3, 4, 5
 PBN_SPLIT_NONE, PBN_SPLIT_CV, PBN_SPLIT_HOLDOUT, PBN_SPLIT_VALIDATED = 0, 1, 2, 3
-PBN_SCORE_BIC, PBN_SCORE_BGE, PBN_SCORE_CVLIK, PBN_SCORE_HOLDOUT = 0, 1, 2, 3
+PBN_SCORE_BIC, PBN_SCORE_BGE, PBN_SCORE_CVLIK, PBN_SCORE_HOLDOUT, PBN_SCORE_BDE = 0, 1, 2, 3, 4
 PBN_NODE_LG, PBN_NODE_CKDE, PBN_NODE_DISCRETE = 0, 1, 2
 PBN_BN_GAUSSIAN, PBN_BN_SEMIPARAMETRIC, PBN_BN_KDE, PBN_BN_CLG = 0, 1, 2, 3
 
@@ -74,6 +74,8 @@ SIGNATURES = {
     "pbn_scoredata_cache_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_destroy": (None, [_vp]),
     "pbn_scoredata_set_discrete": (_int, [_vp, _int, C.POINTER(_vp), _ip]),
+    "pbn_scoredata_create_discrete": (_int, [_vp, _i64, _int, _int, C.c_uint32, C.c_double, C.POINTER(_vp)]),
+    "pbn_scoredata_discrete_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_set_validity": (_int, [_vp, C.POINTER(_vp)]),
     "pbn_split_layout": (_int, [_i64, _int, _int, C.c_uint32, C.c_double, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_layout": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),

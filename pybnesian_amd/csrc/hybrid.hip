@@ -16,6 +16,7 @@
 // (region, configuration) - additive, so the statistics of a training fold are sums over the other folds -
 // and, for CKDE, pack(train slice) -> pack(test slice) -> fused sweep -> finish.
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <memory>
@@ -31,10 +32,6 @@
 namespace pbn {
 namespace score {
 
-namespace {
-
-struct Region { int64_t r0, r1; };
-
 std::vector<Region> regions_of(const pbn_scoredata* sd, int kind) {
     std::vector<Region> r;
     if (kind == PBN_SCORE_CVLIK) {
@@ -48,32 +45,42 @@ std::vector<Region> regions_of(const pbn_scoredata* sd, int kind) {
     return r;
 }
 
-// ---- discrete variable: DiscreteFactor MLE + slogl, bic_discrete --------------------------------------------
-double score_discrete(const pbn_scoredata* sd, int kind, int var, const int* parents_in, int p) {
-    const int n = sd->n;
-    for (int i = 0; i < p; ++i)
-        if (parents_in[i] < n)
-            throw invalid_error("Local score for a discrete variable cannot be calculated because the parents/evidence contains non-discrete variables.");
-    // parents in ascending order: the configurations are then visited - and their terms added - in one order whatever order the
-    // parents came in, so the score is a function of (variable, parent SET) to the last bit and can be memoised like the others
-    std::vector<int> psorted(parents_in, parents_in + p);
-    std::sort(psorted.begin(), psorted.end());
-    const int* parents = psorted.data();
-    const int card0 = sd->card[var - n];
-    std::vector<int> strides(p + 1);
-    int joint = card0;
-    strides[0] = 1;
-    for (int i = 0; i < p; ++i) { strides[i + 1] = joint; joint *= sd->card[parents[i] - n]; }
-    const int configs = joint / card0;
+// ---- discrete variable: DiscreteFactor MLE + slogl, bic_discrete, BDe -------------------------------------------------------------
+// parents in ascending order: the configurations are then visited - and their terms added - in one order whatever order the
+// parents came in, so the score is a function of (variable, parent SET) to the last bit and can be memoised like the others
+Family make_family(const pbn_scoredata* sd, int var, const int* parents, int p) {
+    Family f;
+    f.cols.assign(parents, parents + p);
+    std::sort(f.cols.begin(), f.cols.end());
+    f.cols.insert(f.cols.begin(), var);
+    for (int& c : f.cols) {
+        c -= sd->n;
+        f.G *= sd->card[c];
+        if (f.G > INT32_MAX) throw invalid_error("pbn_score_batch: too many configurations of the discrete parents");
+    }
+    return f;
+}
+
+// the host loop: one pass over the rows of every region
+void family_counts_host(const pbn_scoredata* sd, const std::vector<Region>& regions, const Family& f, std::vector<std::vector<int64_t>>& counts) {
+    const int m = (int)f.cols.size();
+    std::vector<int> strides(m);
+    int joint = 1;
+    for (int i = 0; i < m; ++i) { strides[i] = joint; joint *= sd->card[f.cols[i]]; }
     auto index = [&](int64_t r) {
-        int c = sd->codes[var - n][r];
-        for (int i = 0; i < p; ++i) c += sd->codes[parents[i] - n][r] * strides[i + 1];
+        int c = 0;
+        for (int i = 0; i < m; ++i) c += sd->codes[f.cols[i]][r] * strides[i];
         return c;
     };
-    std::vector<Region> regions = regions_of(sd, kind);
-    std::vector<std::vector<int64_t>> counts(regions.size(), std::vector<int64_t>(joint, 0));
+    counts.assign(regions.size(), std::vector<int64_t>((size_t)joint, 0));
     for (size_t ri = 0; ri < regions.size(); ++ri)
         for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r) ++counts[ri][index(r)];
+}
+
+// The score of a discrete candidate from the counts of its family in the regions of `kind`: the ONE text behind the host loop and the
+// device pass - never inlined, so that both run the same instructions: equal counts give the same bits.
+__attribute__((noinline)) double discrete_from_counts(int kind, double iss, int n_parents, int card0, int joint, const std::vector<std::vector<int64_t>>& counts) {
+    const int configs = joint / card0;
     if (kind == PBN_SCORE_BIC) {  // bic.cpp:66-96
         const auto& jc = counts[0];
         double ll = 0;
@@ -91,6 +98,24 @@ double score_discrete(const pbn_scoredata* sd, int kind, int var, const int* par
             }
         }
         return ll - std::log((double)total) * 0.5 * (card0 - 1) * configs;
+    }
+    if (kind == PBN_SCORE_BDE) {  // bde.cpp:5-47, summed in one order: -G lgamma(alpha), the cells, then the configurations
+        const auto& jc = counts[0];
+        const double alpha = iss / (double)joint;
+        double res = -(double)joint * std::lgamma(alpha);
+        for (int c = 0; c < joint; ++c) res += std::lgamma((double)jc[(size_t)c] + alpha);
+        if (n_parents == 0) {   // bde_impl_noparents
+            int64_t rows = 0;
+            for (int i = 0; i < card0; ++i) rows += jc[(size_t)i];
+            return res + (std::lgamma(iss) - std::lgamma(iss + (double)rows));
+        }
+        const double sum_alpha = alpha * card0;
+        for (int k = 0; k < configs; ++k) {
+            int64_t sum = 0;
+            for (int i = 0; i < card0; ++i) sum += jc[(size_t)k * card0 + i];
+            res += std::lgamma(sum_alpha) - std::lgamma(sum_alpha + (double)sum);
+        }
+        return res;
     }
     // likelihood scores: fit on train counts, slogl on test counts (mle_DiscreteFactor.cpp:5-41)
     auto unit = [&](const std::vector<int64_t>& train, const std::vector<int64_t>& test) {
@@ -114,11 +139,53 @@ double score_discrete(const pbn_scoredata* sd, int kind, int var, const int* par
     for (auto& c : counts)
         for (int i = 0; i < joint; ++i) all[i] += c[i];
     double acc = 0;
-    for (size_t f = 0; f < regions.size(); ++f) {
+    for (size_t f = 0; f < counts.size(); ++f) {
         for (int i = 0; i < joint; ++i) train[i] = all[i] - counts[f][i];
         acc += unit(train, counts[f]);
     }
     return acc;
+}
+
+void check_discrete_candidate(const pbn_scoredata* sd, int kind, int node_type, const int* parents, int p) {
+    if (kind == PBN_SCORE_BGE) throw invalid_error("BGe is not defined for networks with discrete variables.");
+    if (node_type != PBN_NODE_DISCRETE) throw invalid_error("pbn_score_batch: discrete column scored with a continuous node type");
+    for (int i = 0; i < p; ++i)
+        if (parents[i] < sd->n)
+            throw invalid_error("Local score for a discrete variable cannot be calculated because the parents/evidence contains non-discrete variables.");
+}
+
+// Families repeated in the batch - a flip cell and an add cell of the same (variable, parent set) - are counted and finished once.
+void score_discrete_batch(pbn_scoredata* sd, int kind, double iss, std::vector<DiscreteCand>& cands) {
+    if (cands.empty()) return;
+    const bool device = knob_int("PBN_DISCRETE_COUNTS", 1) != 0;   // (per call: the tests switch it)
+    const std::vector<Region> regions = regions_of(sd, kind);
+    std::map<std::vector<int>, size_t> seen;
+    std::vector<Family> fams;
+    std::vector<size_t> fam_of(cands.size());
+    for (size_t i = 0; i < cands.size(); ++i) {
+        Family f = make_family(sd, cands[i].var, cands[i].parents.data(), (int)cands[i].parents.size());
+        auto it = seen.find(f.cols);
+        if (it == seen.end()) { it = seen.emplace(f.cols, fams.size()).first; fams.push_back(std::move(f)); }
+        fam_of[i] = it->second;
+    }
+    std::vector<double> value(fams.size());
+    count_families(sd, regions, fams, device, [&](size_t f, const std::vector<std::vector<int64_t>>& tables, int) {
+        value[f] = discrete_from_counts(kind, iss, (int)fams[f].cols.size() - 1, sd->card[fams[f].cols[0]], (int)fams[f].G, tables);
+    });
+    for (size_t i = 0; i < cands.size(); ++i) {
+        *cands[i].out = value[fam_of[i]];
+        if (!cands[i].memo_key.empty()) sd->score_memo[cands[i].memo_key] = value[fam_of[i]];
+    }
+}
+
+namespace {
+
+double score_discrete(pbn_scoredata* sd, int kind, int var, int node_type, const int* parents, int p) {
+    check_discrete_candidate(sd, kind, node_type, parents, p);
+    double value = 0;
+    std::vector<DiscreteCand> one{DiscreteCand{var, std::vector<int>(parents, parents + p), &value, {}}};
+    score_discrete_batch(sd, kind, 1.0, one);
+    return value;
 }
 
 // ---- rows grouped by (configuration, region), cached per set of discrete parents -----------------------------------------
@@ -588,11 +655,9 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
     const int n = sd->n;
     if (parts && (node_type != PBN_NODE_CKDE || var >= n || (kind != PBN_SCORE_CVLIK && kind != PBN_SCORE_HOLDOUT)))
         throw invalid_error("pbn_score_batch_parts: CKDE candidates of a likelihood score only");
+    if (var >= n) return score_discrete(sd, kind, var, node_type, parents, p);   // (pbn_score_batch batches them before they get here)
     if (kind == PBN_SCORE_BGE) throw invalid_error("BGe is not defined for networks with discrete variables.");
-    if (var >= n) {
-        if (node_type != PBN_NODE_DISCRETE) throw invalid_error("pbn_score_batch: discrete column scored with a continuous node type");
-        return score_discrete(sd, kind, var, parents, p);
-    }
+    if (kind == PBN_SCORE_BDE) throw invalid_error("BDe is defined for discrete variables with discrete parents only.");
     if (node_type == PBN_NODE_DISCRETE) throw invalid_error("pbn_score_batch: continuous column scored as DiscreteFactor");
     std::vector<int> dpar, cols{var};
     for (int i = 0; i < p; ++i) (parents[i] >= n ? dpar : cols).push_back(parents[i]);

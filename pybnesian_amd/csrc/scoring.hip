@@ -534,12 +534,31 @@ int pbn_scoredata_create_sharded(pbn_ctx* ctx, const pbn_table* table, int split
     return scoredata_create_impl(ctx, table, split, k, seed, test_ratio, rank, world, out);
 }
 
+// Score data without a table (learning/scores/bic.cpp:66-96, cv_likelihood.cpp:5-25, bde.cpp:5-47 on an all-discrete DataFrame): the split
+// layout of scoredata_create_impl for the same rows, split, k, seed and ratio; n = 0, no pilot shifts, no moments.  The codes follow
+// through pbn_scoredata_set_discrete as ids 0 .. n_disc - 1.
+int pbn_scoredata_create_discrete(pbn_ctx* ctx, int64_t n_rows, int split, int k, uint32_t seed, double test_ratio, pbn_scoredata** out) {
+    return guarded(mu_of(ctx), [&] {
+        if (!ctx || !out) throw invalid_error("pbn_scoredata_create_discrete: null argument");
+        if (n_rows <= 0 || n_rows > INT32_MAX) throw invalid_error("pbn_scoredata_create_discrete: row count out of range");
+        if (split < PBN_SPLIT_NONE || split > PBN_SPLIT_VALIDATED) throw invalid_error("pbn_scoredata_create_discrete: unknown split");
+        HIP_CHECK(hipSetDevice(ctx->device));
+        auto sd = std::make_unique<pbn_scoredata>();
+        sd->ctx = ctx; sd->n = 0; sd->split = split; sd->discrete_only = true;
+        SplitLayout lay = split_layout(n_rows, split, k, seed, test_ratio);
+        sd->n_cv = lay.n_cv; sd->n_hold = lay.n_hold; sd->k = lay.k; sd->limits = lay.limits;
+        sd->perm = std::move(lay.idx);
+        *out = sd.release();
+    });
+}
+
 // Serialised moments: for each SEGMENT (scoredata_create_impl: the regions' super-blocks, in order) S[n] then G[n*n].
 // set == 0 copies them out (segments this rank did not compute are zero), set != 0 installs all of them, rebuilds the
 // regions' totals in segment order and clears the partial flag.
 int pbn_scoredata_moments(pbn_scoredata* sd, double* buf, int64_t* len, int set) {
     return guarded(mu_of(sd), [&] {
         if (!sd) throw invalid_error("pbn_scoredata_moments: null argument");
+        if (sd->discrete_only) throw invalid_error("pbn_scoredata_moments: discrete-only score data has no table and no moments");
         const size_t per = (size_t)sd->n + (size_t)sd->n * sd->n;
         if (len) *len = (int64_t)(per * sd->seg.size());
         if (!buf) return;
@@ -593,6 +612,7 @@ int pbn_scoredata_set_discrete(pbn_scoredata* sd, int n_disc, const int32_t* con
                 if (v < 0 || v >= cardinality[j]) throw invalid_error("pbn_scoredata_set_discrete: code out of range");
                 sd->codes[j][r] = v;
             }
+        family_codes_upload(sd);
     });
 }
 
@@ -603,6 +623,7 @@ int pbn_scoredata_set_discrete(pbn_scoredata* sd, int n_disc, const int32_t* con
 int pbn_scoredata_set_validity(pbn_scoredata* sd, const uint8_t* const* masks) {
     return guarded(mu_of(sd), [&] {
         if (!sd || !masks) throw invalid_error("pbn_scoredata_set_validity: null argument");
+        if (sd->discrete_only) throw invalid_error("pbn_scoredata_set_validity: discrete-only score data has no continuous columns");
         if (sd->split != PBN_SPLIT_NONE) throw invalid_error("pbn_scoredata_set_validity: only for BIC / BGe score data");
         const int64_t rows = (int64_t)sd->perm.size();
         sd->valid.assign(sd->n, {});
@@ -665,6 +686,7 @@ int pbn_scoredata_layout(const pbn_scoredata* sd, int32_t* perm, int32_t* limits
 int pbn_lg_fit(const pbn_scoredata* sd, int var, const int* parents, int p, double* beta, double* variance) {
     return guarded(mu_of(sd), [&] {
         if (!sd || !beta || !variance) throw invalid_error("pbn_lg_fit: null argument");
+        if (sd->discrete_only) throw invalid_error("pbn_lg_fit: discrete-only score data has no continuous columns");
         if (sd->partial) throw invalid_error("pbn_lg_fit: row-sharded score data needs pbn_scoredata_moments(set) first");
         std::vector<int> cols(p + 1);
         cols[0] = var;
@@ -773,6 +795,13 @@ static int score_batch_impl(pbn_scoredata* sd, int kind, int n_cand, const int* 
         double iss_mu = 1, iss_w = sd->n + 2;
         int total_nodes = sd->n;
         const double* nu = nullptr;
+        if (kind < PBN_SCORE_BIC || kind > PBN_SCORE_BDE) throw invalid_error("pbn_score_batch: unknown score kind");
+        if (kind == PBN_SCORE_BGE && sd->discrete_only) throw invalid_error("BGe is not defined for networks with discrete variables.");
+        // BDe: the imaginary sample size; the discrete candidates of the call (variable a dictionary column) are collected here, counted
+        // together - all their families in one device pass - and finished after the loop (hybrid.hip, family_counts.hip)
+        const double bde_iss = (kind == PBN_SCORE_BDE && n_params >= 1 && params) ? params[0] : 1.0;
+        if (kind == PBN_SCORE_BDE && !(bde_iss > 0)) throw invalid_error("BDe: the imaginary sample size must be positive");
+        std::vector<DiscreteCand> discrete;
         if (kind == PBN_SCORE_BGE) {
             if (n_params >= 1) iss_mu = params[0];
             if (n_params >= 2) iss_w = params[1];
@@ -817,7 +846,7 @@ static int score_batch_impl(pbn_scoredata* sd, int kind, int n_cand, const int* 
                     out[c] = score_hybrid(sd, kind, cols[0], nt, cols.data() + 1, p, &hp, hybrid_batch(), &sink);
                     continue;
                 }
-                const bool memo = score_memo_on() && !sd->force_precise && (kind == PBN_SCORE_CVLIK || kind == PBN_SCORE_HOLDOUT);   // (discrete factors too: a count over all rows on the host each)
+                const bool memo = score_memo_on() && !sd->force_precise && (kind == PBN_SCORE_CVLIK || kind == PBN_SCORE_HOLDOUT);   // (discrete factors too)
                 std::vector<int> key;
                 if (memo) {
                     key.assign(cols.begin() + 1, cols.end());
@@ -826,12 +855,18 @@ static int score_batch_impl(pbn_scoredata* sd, int kind, int n_cand, const int* 
                     auto it = sd->score_memo.find(key);
                     if (it != sd->score_memo.end()) { out[c] = it->second; ++sd->memo_hits; continue; }
                 }
+                if (cols[0] >= sd->n) {
+                    check_discrete_candidate(sd, kind, nt, cols.data() + 1, p);
+                    discrete.push_back(DiscreteCand{cols[0], std::vector<int>(cols.begin() + 1, cols.end()), out + c, key});
+                    continue;
+                }
                 HybridSink sink{out + c, key};   // (key empty without the memo)
                 bool deferred = false;
                 out[c] = score_hybrid(sd, kind, cols[0], nt, cols.data() + 1, p, nullptr, hybrid_batch(), &sink, &deferred);
                 if (memo && !deferred) sd->score_memo[key] = out[c];
                 continue;
             }
+            if (kind == PBN_SCORE_BDE) throw invalid_error("BDe is defined for discrete variables with discrete parents only.");
             mu.resize(d); sse.resize((size_t)d * d); beta.resize(d);
             const Stats* full = &sd->all;
             Stats gathered;
@@ -912,6 +947,7 @@ static int score_batch_impl(pbn_scoredata* sd, int kind, int n_cand, const int* 
         }
         hybrid_batch_flush(hbatch.get());   // (before the plain CKDE units below take the context's result slots)
         hbatch.reset();
+        score_discrete_batch(sd, kind, bde_iss, discrete);
         if (!pending.empty()) {
             // ---- CKDE likelihood units through the set-function cache ------------------------------------------------
             // slogl of a CKDE on a test region = A(vars, d) - A(parents, d), with A(S, m) = sum_q log KDE(S) under the

@@ -1,6 +1,7 @@
 // Internal declarations shared by scoring.hip and hybrid.hip (score engine).
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <limits>
 #include <map>
 #include <set>
@@ -99,6 +100,17 @@ struct pbn_scoredata {
     pbn::dev_buf<int32_t> rows_dev;  // gather lists (valid rows of BIC / BGe candidates on tables with nulls)
     // by [kind, sorted discrete parents...]; shared: a HybridBatch keeps the groupings its enqueued work reads alive until it has flushed
     std::map<std::vector<int>, std::shared_ptr<HybridGrouping>> groupings;
+    // the codes once more on the device, and the family-count pass over them (family_counts.hip): int32 [n_disc][rows] in permuted row
+    // order, and a byte mirror [n_disc][ld8] (0xFF past the last row, ld8 a multiple of 16) when every cardinality is <= 255
+    pbn::dev_buf<int32_t> codes_dev;
+    pbn::dev_buf<uint8_t> codes8;
+    int64_t ld8 = 0;                 // 0: no byte mirror
+    pbn::dev_buf<char> fc_descs;     // grow-only: a launch chunk's descriptors, count buffer and its host copy
+    pbn::dev_buf<uint32_t> fc_counts;
+    std::vector<uint32_t> fc_host;
+    int64_t fc_device_units = 0, fc_host_units = 0, fc_launches = 0;   // pbn_scoredata_discrete_stats
+    // pbn_scoredata_create_discrete: no table, n = 0, the discrete columns are ids 0 .. n_disc - 1
+    bool discrete_only = false;
     // validity of the continuous columns (BIC / BGe on tables with nulls): byte masks, empty = no nulls
     std::vector<std::vector<uint8_t>> valid;
     bool has_nulls = false;
@@ -149,6 +161,37 @@ int score_batch_local(pbn_scoredata* sd, int kind, int n_cand, const int* var, c
                       const double* params, int n_params, double* out);
 void score_batch_sharded(pbn_scoredata* sd, int kind, int n_cand, const int* var, const int* node_type, const int* par_off, const int* parents,
                          const double* params, int n_params, double* out);
+// Discrete candidates (variable and parents all discrete columns; hybrid.hip, family_counts.hip).  A region is a contiguous row range of
+// the permuted table: a CV fold, the hold-out train or test part, or all of [0, n_cv).
+struct Region { int64_t r0, r1; };
+std::vector<Region> regions_of(const pbn_scoredata* sd, int kind);
+// A family: the variable (fastest) and its parents in ascending column order, as indices into the DISCRETE columns; G = prod card.
+constexpr int FAMILY_MAX_VARS = 8;                 // variable + 7 parents: the arrays of the device descriptor
+constexpr int64_t FAMILY_MAX_CELLS = 1ll << 20;    // cells of one table counted on the device
+constexpr int FAMILY_LDS_CELLS = 4096;             // up to here in LDS, above with global atomics
+enum { FAMILY_HOST = 0, FAMILY_LDS_U8 = 1, FAMILY_LDS_I32 = 2, FAMILY_GLOBAL = 3 };   // what served a unit (pbn_debug_family_counts)
+struct Family {
+    std::vector<int> cols;
+    int64_t G = 1;
+};
+// tables[ri][cell]: the family's counts in region ri
+using FamilySink = std::function<void(size_t family, const std::vector<std::vector<int64_t>>& tables, int form)>;
+// counts every family in every region - on the device where `device` allows it and the family fits (family_counts.hip), else with the
+// host loop - and hands each family's tables to `sink`; the families are distinct
+void count_families(pbn_scoredata* sd, const std::vector<Region>& regions, const std::vector<Family>& fams, bool device, const FamilySink& sink);
+void family_counts_host(const pbn_scoredata* sd, const std::vector<Region>& regions, const Family& f, std::vector<std::vector<int64_t>>& tables);
+void family_codes_upload(pbn_scoredata* sd);   // after pbn_scoredata_set_discrete filled sd->codes
+Family make_family(const pbn_scoredata* sd, int var, const int* parents, int p);   // column ids of the score data; sorts the parents
+// The discrete candidates of one pbn_score_batch call: checked as they come (check_discrete_candidate throws what the single-candidate
+// path threw), counted together and finished on the host by score_discrete_batch, which writes *out and the memo.
+struct DiscreteCand {
+    int var;
+    std::vector<int> parents;
+    double* out;
+    std::vector<int> memo_key;   // non-empty: also remembered in pbn_scoredata::score_memo
+};
+void check_discrete_candidate(const pbn_scoredata* sd, int kind, int node_type, const int* parents, int p);
+void score_discrete_batch(pbn_scoredata* sd, int kind, double iss, std::vector<DiscreteCand>& cands);
 struct HybridBatch;
 HybridBatch* hybrid_batch_begin(pbn_scoredata* sd);
 void hybrid_batch_flush(HybridBatch* hb);

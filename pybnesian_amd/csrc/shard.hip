@@ -416,6 +416,7 @@ double pbn_shard_term_cost(int dims, int64_t train_rows, int64_t test_rows) { re
 int pbn_scoredata_set_comm(pbn_scoredata* sd, const pbn_comm* comm) {
     return guarded(mu_of(sd), [&] {
         if (!sd) throw invalid_error("pbn_scoredata_set_comm: null handle");
+        if (comm && sd->discrete_only) throw invalid_error("pbn_scoredata_set_comm: discrete-only score data is not sharded (integer counts, host arithmetic: every rank scores its batches itself)");
         if (comm && (!comm->all_gather || comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world)) throw invalid_error("pbn_scoredata_set_comm: bad communicator");
         sd->has_comm = comm != nullptr;
         if (comm) sd->comm = *comm;

@@ -240,7 +240,7 @@ def sharded_batch(score, model, var, ntype, off, par, kind, shard_all=False):
             raise err
         _lib.check(_lib.load().pbn_scoredata_set_comm(score._handle, cm.ref() if cm is not None else None))
         score._comm = cm
-    if cm is None or n == 0:
+    if cm is None or n == 0 or getattr(score, "_discrete_only", False):   # (discrete-only: integer counts, host arithmetic - every rank, itself)
         return score._batch_raw(model, var, ntype, off, par, kind)
     if getattr(score, "_comm", None) is cm and not shard_all:
         try:

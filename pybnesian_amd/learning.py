@@ -336,7 +336,7 @@ class _EngineBinding:
         cfg.near_tie_abs = 0.0
         if device_score and os.environ.get("PBN_NEAR_TIE", "1") != "0" and getattr(score, "_kind", None) in (_lib.PBN_SCORE_CVLIK, _lib.PBN_SCORE_HOLDOUT):
             try:
-                if score._table.dtype == _lib.PBN_F64:
+                if score._table is not None and score._table.dtype == _lib.PBN_F64:
                     _, _, n_cv, n_hold = score._layout()
                     cfg.near_tie_abs = 4.0 * 3.3e-7 * float(n_cv if score._kind == _lib.PBN_SCORE_CVLIK else n_hold)
             except Exception:   # a score without a device layout: no check

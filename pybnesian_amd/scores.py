@@ -143,12 +143,19 @@ def _engine_selector(construction_args):
     raise ValueError("The device score engine only accepts NormalReferenceRule() or ScottsBandwidth() as the CKDE bandwidth selector.")
 
 
+def _discrete_stats(handle):
+    d, h, l = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().pbn_scoredata_discrete_stats(handle, C.byref(d), C.byref(h), C.byref(l)))
+    return d.value, h.value, l.value
+
+
 class _DeviceScore(Score):
     """Score evaluated by the batched HIP engine (pbn_score_batch)."""
 
     _kind = None
     _split = _lib.PBN_SPLIT_NONE
     _allowed_types = (LinearGaussianCPDType(), DiscreteFactorType())
+    _discrete_only_ok = True   # a table without continuous columns: discrete-only score data (pbn_scoredata_create_discrete)
 
     def __init__(self, df, split_args=(0, 0, 0.0), ctx=None, table=None):
         self._ctx = ctx or (table.ctx if table is not None else default_context())
@@ -170,23 +177,31 @@ class _DeviceScore(Score):
                     self._categories[f.name] = arr.dictionary.to_pylist()
                 else:
                     cont.append(f.name)
-            if not cont:
+            if cont:
+                table, _ = DeviceTable.from_dataframe(self._ctx, rb, cont, drop_null=False)
+            elif not self._discrete_only_ok:
                 raise ValueError("The device score engine needs at least one continuous column.")
-            table, _ = DeviceTable.from_dataframe(self._ctx, rb, cont, drop_null=False)
             self._df = rb
             self._cont_names = cont
+            self._num_rows = rb.num_rows
         else:
             self._df = None
+            self._num_rows = table.num_rows
         self._table = table
-        self._names = list(table.names) + self._disc_names
+        self._discrete_only = table is None
+        self._names = (list(table.names) if table is not None else []) + self._disc_names
         self._col = {n: i for i, n in enumerate(self._names)}
         k, seed, ratio = split_args
         h = C.c_void_p()
         from .distributed import comm
 
-        cm = comm()
+        # (discrete-only score data is never bound to a process group: integer counts and host arithmetic, the same on every rank)
+        cm = None if self._discrete_only else comm()
         self._comm = cm
-        if cm is None:
+        if self._discrete_only:
+            _lib.check(_lib.load().pbn_scoredata_create_discrete(self._ctx.handle, int(self._num_rows), self._split, int(k), C.c_uint32(int(seed)),
+                                                                 float(ratio), C.byref(h)))
+        elif cm is None:
             _lib.check(_lib.load().pbn_scoredata_create(self._ctx.handle, table.handle, self._split, int(k), C.c_uint32(int(seed)),
                                                         float(ratio), C.byref(h)))
         else:
@@ -344,10 +359,14 @@ class _DeviceScore(Score):
         _lib.check(_lib.load().pbn_scoredata_cache_stats(self._handle, C.byref(e), C.byref(w)))
         return e.value, w.value
 
+    def discrete_stats(self):
+        """(device units, host units, launches) of the family-count pass behind the discrete candidates (pbn_scoredata_discrete_stats)."""
+        return _discrete_stats(self._handle)
+
     # -- split layout ------------------------------------------------------------------------------------------
     def _layout(self):
         """(perm, limits, n_cv, n_hold): source row of every split-ordered row, fold limits, region sizes."""
-        n = self._table.num_rows
+        n = self._num_rows
         perm = np.zeros(n, dtype=np.int32)
         limits = np.zeros(max(getattr(self, "_k", 0), 0) + 1, dtype=np.int32)
         n_cv, n_hold = C.c_int64(0), C.c_int64(0)
@@ -394,6 +413,7 @@ class BGe(_DeviceScore):
     """learning/scores/bge.hpp:14-234.  BGe(df, iss_mu=1, iss_w=None, nu=None)."""
 
     _kind = _lib.PBN_SCORE_BGE
+    _discrete_only_ok = False
 
     def __init__(self, df, iss_mu=1.0, iss_w=None, nu=None, ctx=None, table=None):
         super().__init__(df, ctx=ctx, table=table)
@@ -536,23 +556,43 @@ class _ScoreView:
 
 
 class BDe(Score):
-    """learning/scores/bde.{hpp,cpp}: Bayesian Dirichlet equivalent score of discrete networks, BDe(df, iss=1).  The joint
-    counts come from the device (the cached row groupings of pbn_mi, `pbn_mi_counts`); the log-gamma sums over the counts
-    are host arithmetic on at most prod(cardinality) numbers."""
+    """learning/scores/bde.{hpp,cpp}: Bayesian Dirichlet equivalent score of discrete networks, BDe(df, iss=1).  A device score: the
+    categorical columns become discrete-only score data (pbn_scoredata_create_discrete) and every local score is a PBN_SCORE_BDE candidate
+    of pbn_score_batch - the hill-climb hands it whole batches, whose family tables are counted in one device pass.  A table whose
+    categorical columns hold nulls keeps the counts of `MutualInformation` (`pbn_mi_counts`, one row grouping per family) and Python
+    arithmetic: the engine takes no null codes."""
+
+    _kind = _lib.PBN_SCORE_BDE
 
     def __init__(self, df, iss=1.0, ctx=None):
         import pyarrow as pa
-
-        from .dataset import as_record_batch
-        from .independences import MutualInformation
 
         rb = as_record_batch(df)
         self._rb = rb
         self._iss = float(iss)
         self._names = [f.name for f in rb.schema]
         disc = [f.name for f in rb.schema if pa.types.is_dictionary(f.type)]
-        self._counts = MutualInformation(rb.select(disc), True, ctx) if disc else None
-        self._card = {d: len(rb.column(rb.schema.get_field_index(d)).dictionary) for d in disc}
+        columns = {d: rb.column(rb.schema.get_field_index(d)) for d in disc}
+        self._card = {d: len(columns[d].dictionary) for d in disc}
+        self._col = {d: i for i, d in enumerate(disc)}
+        self._handle, self._counts, self._comm = None, None, None
+        self._discrete_only = True
+        if not disc:
+            return
+        if any(columns[d].null_count for d in disc):
+            from .independences import MutualInformation
+
+            self._counts = MutualInformation(rb.select(disc), True, ctx)
+            return
+        self._ctx = ctx or default_context()
+        h = C.c_void_p()
+        _lib.check(_lib.load().pbn_scoredata_create_discrete(self._ctx.handle, int(rb.num_rows), _lib.PBN_SPLIT_NONE, 0, C.c_uint32(0), 0.0, C.byref(h)))
+        self._handle = h
+        codes = [np.ascontiguousarray(columns[d].indices.to_numpy(zero_copy_only=False), dtype=np.int32) for d in disc]
+        ptrs = (C.c_void_p * len(codes))(*[c.ctypes.data for c in codes])
+        _lib.check(_lib.load().pbn_scoredata_set_discrete(h, len(codes), ptrs, _lib.int_array([self._card[d] for d in disc])))
+        self._params = np.asarray([self._iss])
+        self._batch_raw = self._engine_batch_raw   # the batched engine protocol of the hill-climb (learning.py, _EngineBinding)
 
     def __str__(self):
         return "BDe"
@@ -562,8 +602,6 @@ class BDe(Score):
         return all(v in self._names for v in variables)
 
     def compatible_bn(self, model):
-        from .models import DiscreteFactorType
-
         t = model.type()
         nodes = model.joint_nodes() if model.interface_nodes() else model.nodes()
         return bool(t.is_homogeneous()) and t.default_node_type() == DiscreteFactorType() and self.has_variables(nodes)
@@ -571,10 +609,22 @@ class BDe(Score):
     def data(self):
         return self._rb
 
+    def is_discrete(self, variable):
+        return variable in self._card
+
+    def discrete_stats(self):
+        """(device units, host units, launches) of the family-count pass (pbn_scoredata_discrete_stats)."""
+        return _discrete_stats(self._handle)
+
+    def _engine_batch_raw(self, model, var, ntype, off, par, kind):
+        n = len(var)
+        out = np.zeros(n)
+        if n:
+            _lib.check(_lib.load().pbn_score_batch(self._handle, kind, n, _lib.int_array(var), _lib.int_array(ntype), _lib.int_array(off),
+                                                   _lib.int_array(par if par else [0]), _lib.dptr(self._params), 1, _lib.dptr(out)))
+        return out
+
     def _joint_counts(self, variables):
-        for v in variables:
-            if v not in self._card:
-                raise ValueError(f"Variable {v} is not categorical.")
         lib = _lib.load()
         h = self._counts._handle
         _lib.check(lib.pbn_mi_set_order(h, 0, None))
@@ -583,6 +633,12 @@ class BDe(Score):
         return out
 
     def _bde(self, variable, parents):
+        for v in [variable] + list(parents):
+            if v not in self._card:
+                raise ValueError(f"Variable {v} is not categorical.")
+        if self._handle is not None:
+            code = _lib.PBN_NODE_DISCRETE
+            return float(self._engine_batch_raw(None, [self._col[variable]], [code], [0, len(parents)], [self._col[p] for p in parents], self._kind)[0])
         from math import lgamma
 
         counts = self._joint_counts([variable] + list(parents))
@@ -597,19 +653,23 @@ class BDe(Score):
         return res + float(sum(lgamma(sum_alpha) - lgamma(sum_alpha + s) for s in sums))
 
     def local_score(self, model, variable, evidence=None):
-        from .models import DiscreteFactorType
-
         evidence = model.parents(variable) if evidence is None else list(evidence)
         if model.node_type(variable) != DiscreteFactorType():
             raise ValueError(f"Bayesian network type \"{model.type()}\" not valid for score BDe")
         return self._bde(variable, evidence)
 
     def local_score_node_type(self, model, variable_type, variable, evidence):
-        from .models import DiscreteFactorType
-
         if variable_type != DiscreteFactorType():
             raise ValueError(f"Node type \"{variable_type}\" not valid for score BDe")
         return self._bde(variable, list(evidence))
+
+    def __del__(self):
+        try:
+            if _lib.alive() and getattr(self, "_handle", None):
+                _lib.load().pbn_scoredata_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
 
 
 class CrossValidationView:
