@@ -290,6 +290,47 @@ int pbn_score_terms_missing(pbn_scoredata* sd, int kind, int n_terms, const int*
 int pbn_score_batch_parts(pbn_scoredata* sd, int kind, int n_cand, const int* var, const int* node_type, const int* par_off,
                           const int* parents, int part, int n_parts, double* out);
 
+/* ---- discrete networks: fit and evaluation in one device pass ----------------------------------------------------
+ * pbn_dtable replaces the dictionary columns of the DataFrame handed to BayesianNetwork::fit / logl / slogl
+ * (models/BayesianNetwork.hpp:960-994) when every node is a DiscreteFactor: n_cols arrays of n_rows HOST int32
+ * dictionary indices in source row order, -1 = null (arrow's validity bitmap), each code in [-1, cardinality).
+ * The table keeps a host copy and uploads int32 [n_cols][n_rows]; when every cardinality is <= 255 also a byte
+ * mirror in which a null is 0xFF.  n_rows = 0 is legal. */
+typedef struct pbn_dtable pbn_dtable;
+typedef struct pbn_dnet pbn_dnet;
+int pbn_dtable_create(pbn_ctx* ctx, int64_t n_rows, int n_cols, const int32_t* const* codes, const int* cardinality,
+                      pbn_dtable** out);
+void pbn_dtable_destroy(pbn_dtable* dt);
+/* joint_counts (factors/discrete/discrete_indices.cpp:134-150) as MLE<DiscreteFactor> (learning/parameters/
+ * mle_DiscreteFactor.cpp:5-41) takes them, for ALL families of the call in one device pass: family f = var[f] with
+ * parents[par_off[f] .. par_off[f + 1]) (column ids of the table).  out_off[f] .. out_off[f + 1] (n_fam + 1 entries)
+ * is family f's table in out_counts: the variable fastest, the parents in the order GIVEN.  A row with a null in any
+ * variable of a family is left out of that family's table (the reference's combined bitmap).  Families repeated in a
+ * call are counted once.  out_form[f]: 1 LDS on the byte mirror, 2 LDS on the int32 codes, 3 global atomics, 0 the
+ * host loop inside the call (more than 8 variables, more than 2^20 cells, or a table without rows).
+ * PBN_ERR_INVALID when the tables need more than `cap` entries. */
+int pbn_dtable_family_counts(pbn_dtable* dt, int n_fam, const int* var, const int* par_off, const int* parents,
+                             int64_t* out_off, int64_t* out_counts, int64_t cap, int* out_form);
+/* pbn_dnet: the fitted DiscreteFactors of a network (factors/discrete/DiscreteFactor.cpp:34-76): node n = var[n] with
+ * parents[par_off[n] .. par_off[n + 1]), its CPT logprob[cpt_off[n] .. cpt_off[n + 1]) with the variable fastest and
+ * the parents in the given order (cpt_off has n_nodes + 1 entries, cpt_off[0] = 0).  cardinality: of all n_cols
+ * columns of the tables it will be evaluated on.  PBN_ERR_INVALID for a node with more than 8 family variables, a
+ * family with more than 2^31 - 1 cells or offsets that do not match the families' cells. */
+int pbn_dnet_create(pbn_ctx* ctx, int n_cols, const int* cardinality, int n_nodes, const int* var, const int* par_off,
+                    const int* parents, const int64_t* cpt_off, const double* logprob, pbn_dnet** out);
+void pbn_dnet_destroy(pbn_dnet* dn);
+/* BayesianNetwork::logl (models/BayesianNetwork.hpp:960-994) over DiscreteFactor::logl (DiscreteFactor.cpp:91-131):
+ * out[r] (n_rows HOST doubles) = the nodes' log-probabilities of row r added one at a time in node order, starting
+ * from the first node's; a node with a null in any variable of its family contributes NaN.  One kernel launch for
+ * all nodes and rows.  The table's cardinalities must equal the network's. */
+int pbn_dnet_logl(pbn_dnet* dn, const pbn_dtable* dt, double* out);
+/* BayesianNetwork::slogl over DiscreteFactor::slogl (DiscreteFactor.cpp:133-171): per node the sum over the cells of
+ * its family's null-aware table, in cell order, of count x logprob (cells without rows skipped), then the nodes in
+ * node order.  out_per_node (n_nodes doubles) is nullable. */
+int pbn_dnet_slogl(pbn_dnet* dn, pbn_dtable* dt, double* out_total, double* out_per_node);
+/* cumulative pbn_dnet_logl launches and the rows they evaluated */
+int pbn_dnet_stats(const pbn_dnet* dn, int64_t* logl_launches, int64_t* rows_evaluated);
+
 /* ---- one process per GPU: the delta-score cache sharded BEHIND the boundary (shards the serial double
  * loops of learning/operators/operators.cpp:100-132,296-347 and the fold loop of learning/scores/cv_likelihood.cpp:5-25; the
  * reference is one process and has no counterpart).  The host supplies ONE collective - an all-gather of doubles - as a function

@@ -76,6 +76,14 @@ SIGNATURES = {
     "pbn_scoredata_set_discrete": (_int, [_vp, _int, C.POINTER(_vp), _ip]),
     "pbn_scoredata_create_discrete": (_int, [_vp, _i64, _int, _int, C.c_uint32, C.c_double, C.POINTER(_vp)]),
     "pbn_scoredata_discrete_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "pbn_dtable_create": (_int, [_vp, _i64, _int, C.POINTER(_vp), _ip, C.POINTER(_vp)]),
+    "pbn_dtable_destroy": (None, [_vp]),
+    "pbn_dtable_family_counts": (_int, [_vp, _int, _ip, _ip, _ip, C.POINTER(_i64), C.POINTER(_i64), _i64, _ip]),
+    "pbn_dnet_create": (_int, [_vp, _int, _ip, _int, _ip, _ip, _ip, C.POINTER(_i64), _dp, C.POINTER(_vp)]),
+    "pbn_dnet_destroy": (None, [_vp]),
+    "pbn_dnet_logl": (_int, [_vp, _vp, _dp]),
+    "pbn_dnet_slogl": (_int, [_vp, _vp, _dp, _dp]),
+    "pbn_dnet_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_set_validity": (_int, [_vp, C.POINTER(_vp)]),
     "pbn_split_layout": (_int, [_i64, _int, _int, C.c_uint32, C.c_double, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_layout": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),

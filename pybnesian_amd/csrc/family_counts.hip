@@ -34,7 +34,7 @@ constexpr int MAX_COPIES = 32;             // replicated sub-tables of one workg
 constexpr int ROWS_PER_LANE_U8 = 8;        // one 8-byte load per column and step
 constexpr int ROWS_PER_LANE_I32 = 4;       // four coalesced 4-byte loads per column and step
 constexpr int SLICE_ALIGN = BLOCK * ROWS_PER_LANE_U8;   // rows of a slice: a multiple of it
-constexpr int MIRROR_ALIGN = 16;           // the byte mirror's leading dimension is a multiple of it (rows past the last hold 0xFF)
+constexpr int MIRROR_ALIGN = FAMILY_MIRROR_ALIGN;   // the byte mirror's leading dimension is a multiple of it (rows past the last hold 0xFF)
 constexpr int64_t CHUNK_CELLS = 1ll << 24; // cells of one launch chunk's count buffer: 64 MB of uint32 (PBN_DISCRETE_CHUNK_CELLS)
 
 struct Desc {
@@ -58,7 +58,9 @@ void copies_for(int G, int* copies, int* copy_stride) {
 }
 
 // grid = (units, slices).  LDS = true: cells[] holds the workgroup's copies; false: the lanes add into the unit's table in global memory.
-template <typename CodeT, bool LDS>
+// NULLS = true (the tables of a pbn_dtable, discrete_model.hip): a row with a null - byte 0xFF, int32 code < 0 - in ANY column of the
+// unit is left out of the unit's table (the combined bitmap of discrete_indices.cpp:134-150); false compiles to the text it was before.
+template <typename CodeT, bool LDS, bool NULLS>
 __global__ __launch_bounds__(BLOCK) void family_count_kernel(const Desc* __restrict__ descs, const CodeT* __restrict__ codes, int64_t ld,
                                                               uint32_t* __restrict__ counts) {
     extern __shared__ uint32_t cells[];   // [copies][copy_stride]
@@ -82,22 +84,28 @@ __global__ __launch_bounds__(BLOCK) void family_count_kernel(const Desc* __restr
         constexpr int V = ROWS_PER_LANE_U8;
         for (int64_t r = s0 + (int64_t)tid * V; r < s1; r += (int64_t)BLOCK * V) {   // r is a multiple of 8 below ld: r + 7 < ld
             uint32_t key[V];
+            uint32_t null_rows = 0u;   // NULLS: bit i = row r + i has a null in one of the unit's columns
 #pragma unroll
             for (int i = 0; i < V; ++i) key[i] = 0u;
             for (int j = 0; j < m; ++j) {
                 const uint2 v = *reinterpret_cast<const uint2*>(codes + (int64_t)d.col[j] * ld + r);
                 const uint32_t stride = (uint32_t)d.stride[j];
 #pragma unroll
-                for (int i = 0; i < V; ++i) key[i] += (((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 0xFFu) * stride;
+                for (int i = 0; i < V; ++i) {
+                    const uint32_t code = ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 0xFFu;
+                    key[i] += code * stride;
+                    if constexpr (NULLS) null_rows |= (code == 0xFFu ? 1u : 0u) << i;
+                }
             }
 #pragma unroll
             for (int i = 0; i < V; ++i)
-                if (r + i >= row0 && r + i < s1 && key[i] < G) atomicAdd(mine + key[i], 1u);
+                if (r + i >= row0 && r + i < s1 && key[i] < G && !(NULLS && ((null_rows >> i) & 1u))) atomicAdd(mine + key[i], 1u);
         }
     } else {
         constexpr int V = ROWS_PER_LANE_I32;
         for (int64_t r = (s0 < row0 ? row0 : s0) + tid; r < s1; r += (int64_t)BLOCK * V) {
             uint32_t key[V];
+            uint32_t null_rows = 0u;
 #pragma unroll
             for (int i = 0; i < V; ++i) key[i] = 0u;
             for (int j = 0; j < m; ++j) {
@@ -105,11 +113,15 @@ __global__ __launch_bounds__(BLOCK) void family_count_kernel(const Desc* __restr
                 const uint32_t stride = (uint32_t)d.stride[j];
 #pragma unroll
                 for (int i = 0; i < V; ++i)
-                    if (r + (int64_t)i * BLOCK < s1) key[i] += (uint32_t)col[(int64_t)i * BLOCK] * stride;
+                    if (r + (int64_t)i * BLOCK < s1) {
+                        const CodeT code = col[(int64_t)i * BLOCK];
+                        key[i] += (uint32_t)code * stride;
+                        if constexpr (NULLS) null_rows |= (code < 0 ? 1u : 0u) << i;
+                    }
             }
 #pragma unroll
             for (int i = 0; i < V; ++i)
-                if (r + (int64_t)i * BLOCK < s1 && key[i] < G) atomicAdd(mine + key[i], 1u);
+                if (r + (int64_t)i * BLOCK < s1 && key[i] < G && !(NULLS && ((null_rows >> i) & 1u))) atomicAdd(mine + key[i], 1u);
         }
     }
     if constexpr (LDS) {
@@ -138,28 +150,35 @@ __global__ __launch_bounds__(BLOCK) void family_byte_mirror_kernel(const int32_t
     *reinterpret_cast<uint32_t*>(mirror + (int64_t)blockIdx.y * ld8 + r) = packed;
 }
 
-template <bool LDS>
-void launch_count(const Desc* descs, int n_units, int max_slices, int lds_words, bool bytes, const pbn_scoredata* sd, uint32_t* counts, hipStream_t st) {
+// the codes are the byte mirror (codes8, leading dimension ld8) when ld8 > 0, else the int32 codes (codes32, ld32)
+template <bool LDS, bool NULLS>
+void launch_count(const Desc* descs, int n_units, int max_slices, int lds_words, const uint8_t* codes8, int64_t ld8, const int32_t* codes32, int64_t ld32,
+                  uint32_t* counts, hipStream_t st) {
     if (n_units <= 0) return;
     if (lds_words < 0 || lds_words > LDS_WORDS || max_slices < 1 || max_slices > 65535) throw invalid_error("family counts: bad launch shape");
     const dim3 grid((unsigned)n_units, (unsigned)max_slices), block(BLOCK);
     const size_t lds = LDS ? (size_t)lds_words * sizeof(uint32_t) : 0;
-    if (bytes) hipLaunchKernelGGL((family_count_kernel<uint8_t, LDS>), grid, block, lds, st, descs, (const uint8_t*)sd->codes8.p, sd->ld8, counts);
-    else hipLaunchKernelGGL((family_count_kernel<int32_t, LDS>), grid, block, lds, st, descs, (const int32_t*)sd->codes_dev.p, (int64_t)sd->perm.size(), counts);
+    if (ld8 > 0) hipLaunchKernelGGL((family_count_kernel<uint8_t, LDS, NULLS>), grid, block, lds, st, descs, codes8, ld8, counts);
+    else hipLaunchKernelGGL((family_count_kernel<int32_t, LDS, NULLS>), grid, block, lds, st, descs, codes32, ld32, counts);
     HIP_CHECK(hipGetLastError());
 }
 
 bool on_device(const pbn_scoredata* sd, const Family& f) {
-    return sd->codes_dev.p && (int)f.cols.size() <= FAMILY_MAX_VARS && f.G <= FAMILY_MAX_CELLS;
+    return sd->codes_dev.p && family_fits_device(f);
 }
 
+}  // namespace
+
+bool family_fits_device(const Family& f) { return (int)f.cols.size() <= FAMILY_MAX_VARS && f.G <= FAMILY_MAX_CELLS; }
+
 // The families `which` (all on_device), chunk by chunk: descriptors up, one memset, one launch per form present, the chunk's tables down.
-void count_families_device(pbn_scoredata* sd, const std::vector<Region>& regions, const std::vector<Family>& fams, const std::vector<size_t>& which,
+void count_families_device(const FamilyCodes& src, const std::vector<Region>& regions, const std::vector<Family>& fams, const std::vector<size_t>& which,
                            const FamilySink& sink) {
-    pbn_ctx* ctx = sd->ctx;
+    pbn_ctx* ctx = src.ctx;
+    FamilyScratch* sd = src.scratch;
     HIP_CHECK(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const bool bytes = sd->ld8 > 0;
+    const bool bytes = src.ld8 > 0;
     const size_t R = regions.size();
     const int64_t budget = std::max<int64_t>(1, knob_ll("PBN_DISCRETE_CHUNK_CELLS", CHUNK_CELLS));   // (per call: the chunking test lowers it)
     std::vector<Desc> descs[2];   // LDS form, global form
@@ -184,7 +203,7 @@ void count_families_device(pbn_scoredata* sd, const std::vector<Region>& regions
                 Desc d{};
                 d.m = (int)f.cols.size(); d.G = (int)f.G;
                 int stride = 1;
-                for (int j = 0; j < d.m; ++j) { d.col[j] = f.cols[j]; d.stride[j] = stride; stride *= sd->card[f.cols[j]]; }
+                for (int j = 0; j < d.m; ++j) { d.col[j] = f.cols[j]; d.stride[j] = stride; stride *= src.card[f.cols[j]]; }
                 if (lds) copies_for(d.G, &d.copies, &d.copy_stride);
                 d.row0 = regions[ri].r0; d.row1 = regions[ri].r1;
                 d.base = bytes ? d.row0 / ROWS_PER_LANE_U8 * ROWS_PER_LANE_U8 : d.row0;
@@ -208,8 +227,13 @@ void count_families_device(pbn_scoredata* sd, const std::vector<Region>& regions
         if (n0) HIP_CHECK(hipMemcpyAsync(dd, descs[0].data(), n0 * sizeof(Desc), hipMemcpyHostToDevice, st));
         if (n1) HIP_CHECK(hipMemcpyAsync(dd + n0, descs[1].data(), n1 * sizeof(Desc), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemsetAsync(sd->fc_counts.p, 0, (size_t)cells * sizeof(uint32_t), st));
-        launch_count<true>(dd, (int)n0, max_slices[0], lds_words, bytes, sd, sd->fc_counts.p, st);
-        launch_count<false>(dd + n0, (int)n1, max_slices[1], 0, bytes, sd, sd->fc_counts.p, st);
+        if (src.nulls) {
+            launch_count<true, true>(dd, (int)n0, max_slices[0], lds_words, src.codes8, src.ld8, src.codes32, src.ld32, sd->fc_counts.p, st);
+            launch_count<false, true>(dd + n0, (int)n1, max_slices[1], 0, src.codes8, src.ld8, src.codes32, src.ld32, sd->fc_counts.p, st);
+        } else {
+            launch_count<true, false>(dd, (int)n0, max_slices[0], lds_words, src.codes8, src.ld8, src.codes32, src.ld32, sd->fc_counts.p, st);
+            launch_count<false, false>(dd + n0, (int)n1, max_slices[1], 0, src.codes8, src.ld8, src.codes32, src.ld32, sd->fc_counts.p, st);
+        }
         sd->fc_launches += (n0 ? 1 : 0) + (n1 ? 1 : 0);
         HIP_CHECK(hipMemcpyAsync(sd->fc_host.data(), sd->fc_counts.p, (size_t)cells * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));   // (the descriptors are read by then as well)
@@ -223,8 +247,6 @@ void count_families_device(pbn_scoredata* sd, const std::vector<Region>& regions
         base = end;
     }
 }
-
-}  // namespace
 
 // sd->codes (permuted row order) -> the device: int32 [n_disc][rows], and the byte mirror when every cardinality is <= 255
 void family_codes_upload(pbn_scoredata* sd) {
@@ -242,11 +264,15 @@ void family_codes_upload(pbn_scoredata* sd) {
     if (max_card <= 255 && sd->n_disc <= 65535) {
         sd->ld8 = ceil_div(rows, MIRROR_ALIGN) * MIRROR_ALIGN;
         sd->codes8.alloc((size_t)sd->ld8 * sd->n_disc);
-        hipLaunchKernelGGL(family_byte_mirror_kernel, dim3((unsigned)ceil_div(sd->ld8 / 4, BLOCK), (unsigned)sd->n_disc), dim3(BLOCK), 0, ctx->stream,
-                           sd->codes_dev.p, rows, sd->codes8.p, sd->ld8);
-        HIP_CHECK(hipGetLastError());
+        family_byte_mirror(ctx, sd->codes_dev.p, rows, sd->n_disc, sd->codes8.p, sd->ld8);
     }
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
+void family_byte_mirror(pbn_ctx* ctx, const int32_t* codes_dev, int64_t rows, int n_cols, uint8_t* mirror, int64_t ld8) {
+    hipLaunchKernelGGL(family_byte_mirror_kernel, dim3((unsigned)ceil_div(ld8 / 4, BLOCK), (unsigned)n_cols), dim3(BLOCK), 0, ctx->stream, codes_dev, rows,
+                       mirror, ld8);
+    HIP_CHECK(hipGetLastError());
 }
 
 void count_families(pbn_scoredata* sd, const std::vector<Region>& regions, const std::vector<Family>& fams, bool device, const FamilySink& sink) {
@@ -254,7 +280,14 @@ void count_families(pbn_scoredata* sd, const std::vector<Region>& regions, const
     if (device)
         for (size_t f = 0; f < fams.size(); ++f)
             if (on_device(sd, fams[f])) dev.push_back(f);
-    if (!dev.empty()) count_families_device(sd, regions, fams, dev, sink);
+    if (!dev.empty()) {
+        FamilyCodes src;
+        src.ctx = sd->ctx; src.scratch = sd; src.card = sd->card.data();
+        src.codes32 = sd->codes_dev.p; src.ld32 = (int64_t)sd->perm.size();
+        src.codes8 = sd->codes8.p; src.ld8 = sd->ld8;
+        src.nulls = false;   // the codes of score data hold no nulls (pbn_scoredata_set_discrete)
+        count_families_device(src, regions, fams, dev, sink);
+    }
     std::vector<std::vector<int64_t>> tables;
     for (size_t f = 0; f < fams.size(); ++f) {
         if (device && on_device(sd, fams[f])) continue;

@@ -30,6 +30,15 @@ struct Stats {  // pilot-shifted moments of a row set over all n columns (or a c
     }
 };
 
+// What a family-count pass (family_counts.hip) keeps between calls: a launch chunk's descriptors, count buffer and its host copy
+// (grow-only), and the counters behind pbn_scoredata_discrete_stats.  Score data and a pbn_dtable (discrete_model.hip) each own one.
+struct FamilyScratch {
+    pbn::dev_buf<char> fc_descs;
+    pbn::dev_buf<uint32_t> fc_counts;
+    std::vector<uint32_t> fc_host;
+    int64_t fc_device_units = 0, fc_host_units = 0, fc_launches = 0;
+};
+
 }  // namespace score
 }  // namespace pbn
 
@@ -47,7 +56,7 @@ struct HybridGrouping {
     mutable int full_state = 0;        // 0 not tried, 1 ready, -1 not applicable (more than 64 continuous columns / too many cells)
 };
 
-struct pbn_scoredata {
+struct pbn_scoredata : pbn::score::FamilyScratch {
     pbn::ctx_ptr ctx;
     int dtype = PBN_F64;
     int n = 0;  // continuous columns
@@ -105,10 +114,7 @@ struct pbn_scoredata {
     pbn::dev_buf<int32_t> codes_dev;
     pbn::dev_buf<uint8_t> codes8;
     int64_t ld8 = 0;                 // 0: no byte mirror
-    pbn::dev_buf<char> fc_descs;     // grow-only: a launch chunk's descriptors, count buffer and its host copy
-    pbn::dev_buf<uint32_t> fc_counts;
-    std::vector<uint32_t> fc_host;
-    int64_t fc_device_units = 0, fc_host_units = 0, fc_launches = 0;   // pbn_scoredata_discrete_stats
+    // (the pass's buffers and the counters of pbn_scoredata_discrete_stats: FamilyScratch)
     // pbn_scoredata_create_discrete: no table, n = 0, the discrete columns are ids 0 .. n_disc - 1
     bool discrete_only = false;
     // validity of the continuous columns (BIC / BGe on tables with nulls): byte masks, empty = no nulls
@@ -179,6 +185,26 @@ using FamilySink = std::function<void(size_t family, const std::vector<std::vect
 // counts every family in every region - on the device where `device` allows it and the family fits (family_counts.hip), else with the
 // host loop - and hands each family's tables to `sink`; the families are distinct
 void count_families(pbn_scoredata* sd, const std::vector<Region>& regions, const std::vector<Family>& fams, bool device, const FamilySink& sink);
+// The device pass by itself, over any table of codes: int32 [cols][ld32], and the byte mirror [cols][ld8] when ld8 > 0 (every cardinality
+// <= 255; 0xFF in the rows past the last).  nulls: a code < 0 (0xFF in the mirror) is a null, and a row with a null in any column of a
+// family is left out of that family's tables; without it no code may be negative.  `which` indexes the families to count - each must
+// pass family_fits_device - and the regions are row ranges of the table.
+struct FamilyCodes {
+    pbn_ctx* ctx = nullptr;
+    FamilyScratch* scratch = nullptr;
+    const int* card = nullptr;       // per column
+    const int32_t* codes32 = nullptr;
+    int64_t ld32 = 0;
+    const uint8_t* codes8 = nullptr;
+    int64_t ld8 = 0;
+    bool nulls = false;
+};
+bool family_fits_device(const Family& f);
+void count_families_device(const FamilyCodes& src, const std::vector<Region>& regions, const std::vector<Family>& fams, const std::vector<size_t>& which,
+                           const FamilySink& sink);
+// int32 codes [n_cols][rows] on the device -> the byte mirror [n_cols][ld8] (enqueued on the context's stream)
+void family_byte_mirror(pbn_ctx* ctx, const int32_t* codes_dev, int64_t rows, int n_cols, uint8_t* mirror, int64_t ld8);
+constexpr int FAMILY_MIRROR_ALIGN = 16;   // ld8 is a multiple of it
 void family_counts_host(const pbn_scoredata* sd, const std::vector<Region>& regions, const Family& f, std::vector<std::vector<int64_t>>& tables);
 void family_codes_upload(pbn_scoredata* sd);   // after pbn_scoredata_set_discrete filled sd->codes
 Family make_family(const pbn_scoredata* sd, int var, const int* parents, int p);   // column ids of the score data; sorts the parents

@@ -513,10 +513,21 @@ def _dictionary_column(rb, name):
     return col
 
 
+def _logprob_from_counts(counts, card):
+    """mle_DiscreteFactor.cpp:14-38: integer joint counts (the variable fastest, `card` its categories) -> the flat CPT,
+    logP = log(count) - log(sum over the parent configuration), uniform for unseen configurations.  The ONE expression behind
+    DiscreteFactor.fit and the network-level fit (discrete_model.py): both give the same bits."""
+    counts = np.asarray(counts).astype(np.float64).reshape(-1, card)
+    sums = counts.sum(axis=1, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lp = np.where(sums > 0, np.log(counts) - np.log(np.where(sums > 0, sums, 1.0)), np.log(1.0 / card))
+    return lp.reshape(-1)
+
+
 class DiscreteFactor(Factor):
     """Multinomial CPT (factors/discrete/DiscreteFactor.cpp:34-171, learning/parameters/mle_DiscreteFactor.cpp:5-41).
-    Integer counting on the host: logP = log(count) - log(sum over the parent
-    configuration), uniform for unseen configurations."""
+    Called directly, a factor counts on the host; the factors of a network whose nodes are all
+    DiscreteFactor are fitted and evaluated together on the device (discrete_model.py)."""
 
     def __init__(self, variable, evidence):
         super().__init__(variable, evidence)
@@ -554,11 +565,7 @@ class DiscreteFactor(Factor):
         cols, idx, valid, cards = self._indices(rb)
         self._categories = [c.dictionary.to_pylist() for c in cols]
         self._cards = cards
-        counts = np.bincount(idx[valid], minlength=int(np.prod(cards))).astype(np.float64).reshape(-1, cards[0])
-        sums = counts.sum(axis=1, keepdims=True)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            lp = np.where(sums > 0, np.log(counts) - np.log(np.where(sums > 0, sums, 1.0)), np.log(1.0 / cards[0]))
-        self._logprob = lp.reshape(-1)
+        self._logprob = _logprob_from_counts(np.bincount(idx[valid], minlength=int(np.prod(cards))), cards[0])
         self._fitted = True
 
     def logl(self, df):

@@ -866,12 +866,43 @@ class BayesianNetwork(BayesianNetworkBase):
             self.set_unknown_node_types(df)
         from .dataset import default_context, shared_upload
 
+        if self._fit_discrete(df):
+            return
         with shared_upload(default_context(), df, self._upload_columns()):   # one PCIe pass over the model's columns for all factors
             for n in self._nodes:
                 if not self._cpd_valid(n):
                     self._cpds[n] = self._new_factor(df, n)
                 if not self._cpds[n].fitted():
                     self._cpds[n].fit(df)
+
+    def _fit_discrete(self, df):
+        """The device path of `fit` (discrete_model.py): taken when every node's factor is, or will be built as, exactly
+        DiscreteFactor - all unfitted factors then come from ONE family-count pass.  Decided before anything is built, so a
+        network with another kind of node goes through the per-factor loop untouched.  False: the loop must run."""
+        import pyarrow as pa
+
+        from . import discrete_model as dm
+        from .factors import DiscreteFactor
+
+        if not dm.enabled() or not self._nodes:
+            return False
+        for n in self._nodes:
+            if self._cpd_valid(n):
+                if type(self._cpds[n]) is not DiscreteFactor:
+                    return False
+                continue
+            nt = self._types[n]
+            idx = df.schema.get_field_index(n)
+            disc = idx >= 0 and pa.types.is_dictionary(df.schema.field(idx).type)
+            if not (type(nt) is DiscreteFactorType or (disc and type(nt) in (LinearGaussianCPDType, CKDEType))):
+                return False
+        for n in self._nodes:
+            if not self._cpd_valid(n):
+                self._cpds[n] = self._new_factor(df, n)
+        if not dm.all_discrete_factors(self):
+            return False
+        todo = [n for n in self._nodes if not self._cpds[n].fitted()]
+        return not todo or dm.fit_network(self, df, todo)
 
     def _upload_columns(self):
         """The columns the factors of this model read: its nodes and, for a conditional network, its interface nodes."""
@@ -896,7 +927,13 @@ class BayesianNetwork(BayesianNetworkBase):
 
         from .dataset import as_record_batch, default_context, shared_upload
 
+        from . import discrete_model as dm
+
         df = as_record_batch(df)
+        if dm.enabled() and dm.all_discrete_factors(self):   # one launch for all nodes; the same adds in the same order
+            out = dm.network_logl(self, df)
+            if out is not None:
+                return out
         out = None
         with shared_upload(default_context(), df, self._upload_columns()):
             for n in self._nodes:
@@ -907,9 +944,14 @@ class BayesianNetwork(BayesianNetworkBase):
     def slogl(self, df):
         if not self.fitted():
             raise ValueError("Model not fitted.")
+        from . import discrete_model as dm
         from .dataset import as_record_batch, default_context, shared_upload
 
         df = as_record_batch(df)
+        if dm.enabled() and dm.all_discrete_factors(self):
+            total = dm.network_slogl(self, df)
+            if total is not None:
+                return float(total)
         with shared_upload(default_context(), df, self._upload_columns()):
             return float(sum(self._cpds[n].slogl(df) for n in self._nodes))
 
