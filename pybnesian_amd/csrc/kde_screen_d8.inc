@@ -27,9 +27,10 @@
 // tests/test_prune_d8_screen_cpu.py restates s~ and E in numpy and holds |s~ - s| <= E on adversarial rows.  Typical rows of the bench table
 // (N = 67, R = 11.6 by the bandwidth rule) carry E = 0.14 exponent units.
 // Rows that the f16 operands cannot hold - a NaN or infinite coordinate, |z_k| > 65504, N > 60000 - are FLAGGED: coordinates 0 and +inf in the
-// norm's hi slot, so every exponent of theirs is +inf (no slot of the other side is negative or non-finite but a flagged row's own +inf) and
-// v_max3_f32 cannot lose it as it would a NaN: the block is kept.  The comparison keeps on a NaN threshold too.  Padding rows (beyond the
-// table) carry nt = -60000: they have no term.
+// norm's hi slot, so every exponent of theirs is +inf (no slot of the other side is negative or non-finite but a flagged row's own +inf):
+// never a NaN, and the block is kept.  That matters to the serial kernel alone, whose fmaxf (v_max3_f32) would lose a NaN; the block maximum
+// of kde_screen_d8_kernel (v_maximum3_f32) hands a NaN on, and `!(max < thr)` then keeps the block as well.  The comparison keeps on a NaN
+// threshold too.  Padding rows (beyond the table) carry nt = -60000: they have no term.
 #define PBN_SCREEN_KAPPA (0x1p-10 + 0x1p-20 + 35.0 * 0x1p-23)
 #define PBN_SCREEN_LAMBDA 0x1p-12
 #define PBN_SCREEN_MU 0x1p-13
@@ -94,7 +95,9 @@ __global__ __launch_bounds__(256) void kde_screen_pack_kernel(const double* __re
 #ifndef PBN_SCREEN_WAVES
 #define PBN_SCREEN_WAVES 4   // waves per SIMD the screen is compiled for (128 VGPRs: the joint box test of two groups over eight dimensions spills at 5 and more)
 #endif
-__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(SweepArgs a) {
+// Round 11's kernel, kept for one release as the A/B leg and the yardstick of mask equality (PBN_D8_SCREEN_STREAM=0): box tests and MFMAs
+// interleaved batch by batch, one fragment load in flight per wave.  kde_screen_d8_kernel, below, writes the same words.
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_kernel(SweepArgs a) {
     constexpr int QG = PBN_QG_PRUNE, PD = PBN_PRUNE_PD;
     static_assert(QG == 2, "two groups = the 32 columns of the MFMA");
     const int lane = threadIdx.x & 63;
@@ -218,6 +221,189 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
     }
 }
 
+// The screen in two phases per wave (round 12).  The serial kernel's listing shows every MFMA behind `s_waitcnt vmcnt(0)` on a load issued a few
+// scalar instructions earlier (the compiler rotated the source's prefetch away): one memory round trip per MFMA, one load in flight per wave.
+// Phase 1 walks the super-batch's boxes exactly as before - batch_in_reach, prune_group_masks_joint, prune_group_mask on the same words - and
+// parks the box words in LDS, issuing no MFMA.  Phase 2 walks the flat list of tile pairs those words define (batch order, pairs inside a batch
+// as before: an odd count takes its last tile twice, no pair straddles batches) with PBN_SCREEN_RING fragments in flight: a prologue of R loads,
+// then turns of R slots - MFMA, block maximum, two compares and ballots, the result ORed into the batch's live words in LDS, the load of the
+// pair R ahead into the register the MFMA just read.  The loads are unconditional (a conditional load costs a vmcnt(0): run_batch in
+// kde_kernels.hip): past the end of the list the last pair is loaded and screened again, which ORs the same bits.  Nothing else in the loop
+// counts on vmcnt - the mask words leave through LDS and are stored after it - so each slot waits with vmcnt(R - 1)
+// (tests/test_isa_screen_cpu.py).  A tile's bit depends on its own 16 rows alone: the words are the serial kernel's, bit for bit.
+// The block maximum is __builtin_elementwise_maximum: 8 v_maximum3_f32 for the two tiles where fmaxf quiets every input first (19 v_max_f32 +
+// 4 v_max3_f32).  On accumulators without a NaN - all of them, by the operands' design - the two maxima are equal; a NaN it PROPAGATES,
+// and `!(max < thr)` then keeps the block instead of losing it.
+#ifndef PBN_SCREEN_RING
+#define PBN_SCREEN_RING 4   // fragments in flight per wave (4 VGPRs each)
+#endif
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(SweepArgs a) {
+    constexpr int QG = PBN_QG_PRUNE, PD = PBN_PRUNE_PD, R = PBN_SCREEN_RING;
+    static_assert(QG == 2, "two groups = the 32 columns of the MFMA");
+    static_assert(R >= 1 && R <= 16, "ring depth");
+    const int lane = threadIdx.x & 63;
+    int qx, split;
+    pruned_block(a, QG, blockIdx.x, qx, split);
+    const int64_t qt0 = (int64_t)qx * QG;
+    if (qt0 >= a.nqtiles) return;
+    const int64_t t0 = (int64_t)split * a.tiles_per_split;
+    const int64_t t1 = (t0 + a.tiles_per_split < a.ntiles) ? t0 + a.tiles_per_split : a.ntiles;
+    const PBN_GLOBAL double* __restrict__ TBp = (const PBN_GLOBAL double*)a.tile_box;
+    const PBN_GLOBAL double* __restrict__ QBp = (const PBN_GLOBAL double*)a.qtile_box;
+    const PBN_GLOBAL double* __restrict__ QTp = (const PBN_GLOBAL double*)a.qtile_thr;
+    const PBN_GLOBAL char* __restrict__ SAc = (const PBN_GLOBAL char*)a.scr_train;
+    const PBN_GLOBAL hf8* __restrict__ SQ = (const PBN_GLOBAL hf8*)a.scr_query;
+    __shared__ double qbs[QG * (2 * PD + 1)];            // the groups' boxes and thresholds, as in the serial kernel
+    __shared__ unsigned long long msk[64 * 2 * QG];      // per batch of the super-batch: the box words of its groups, then the live words
+    if (lane < QG * 2 * PD) {
+        const int g = lane / (2 * PD);
+        const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+        qbs[lane] = QBp[qt * 2 * PD + (lane - g * 2 * PD)];
+    } else if (lane < QG * 2 * PD + QG) {
+        const int g = lane - QG * 2 * PD;
+        const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+        qbs[lane] = QTp[qt] - a.prune_margin;
+    }
+    asm volatile("" ::: "memory");   // (one wave per workgroup, LDS in order: no barrier)
+    const bool count = a.count_redo != 0;
+    if (count && lane == 0) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
+    PBN_GLOBAL unsigned long long* LM = (PBN_GLOBAL unsigned long long*)a.live_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG;
+    PBN_GLOBAL unsigned long long* BM = a.box_mask ? (PBN_GLOBAL unsigned long long*)a.box_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG : nullptr;
+    for (int64_t sb = t0; sb < t1; sb += 4096) {
+        // ---- phase 1: the box words of the super-batch's batches (lane = batch)
+        const int64_t bt = sb + 64 * lane;   // my batch's first tile
+        const PBN_GLOBAL double* bb = (const PBN_GLOBAL double*)a.batch_box + ((int64_t)split * a.batches_per_split + ((bt - t0) >> 6)) * 2 * PD;
+        unsigned long long bmg[QG], bm = 0;
+#pragma unroll
+        for (int g = 0; g < QG; ++g) {
+            bmg[g] = __ballot(bt < t1 && batch_in_reach<PD>(bb, (const double*)&qbs[g * 2 * PD], PD, qbs[QG * 2 * PD + g]));
+            bm |= bmg[g];
+        }
+        unsigned long long my_box[QG] = {0, 0};
+        while (bm) {
+            const int j = __builtin_ctzll(bm);
+            bm &= bm - 1;
+            const int64_t tb = sb + 64 * (int64_t)j;
+            const unsigned gsel = (unsigned)((bmg[0] >> j) & 1ull) | ((unsigned)((bmg[1] >> j) & 1ull) << 1);
+            unsigned long long gm[QG];
+            if (gsel == 3u) {
+                const double* qb[QG] = {(const double*)&qbs[0], (const double*)&qbs[2 * PD]};
+                const double thr[QG] = {qbs[QG * 2 * PD], qbs[QG * 2 * PD + 1]};
+                prune_group_masks_joint<PD, QG>(TBp, qb, PD, tb, t1, thr, lane, gm);
+            } else {
+#pragma unroll
+                for (int g = 0; g < QG; ++g)
+                    gm[g] = ((gsel >> g) & 1u) ? prune_group_mask<PD>(TBp, (const double*)&qbs[g * 2 * PD], PD, tb, t1, qbs[QG * 2 * PD + g], lane) : 0ull;
+            }
+            if (count && lane == 0 && (gm[0] | gm[1])) {
+                atomicAdd(&g_sweep_visit, (unsigned long long)(__builtin_popcountll(gm[0]) + __builtin_popcountll(gm[1])));
+                atomicAdd(&g_screen_tested, (unsigned long long)(__builtin_popcountll(gm[0]) + __builtin_popcountll(gm[1])));
+            }
+            if (lane == j) { my_box[0] = gm[0]; my_box[1] = gm[1]; }
+        }
+        msk[lane * 4] = my_box[0];
+        msk[lane * 4 + 1] = my_box[1];
+        msk[lane * 4 + 2] = 0;
+        msk[lane * 4 + 3] = 0;
+        asm volatile("" ::: "memory");
+        // ---- phase 2: the pairs of the parked words through the ring.  Everything that names a pair is scalar.
+        const unsigned long long tiles = my_box[0] | my_box[1];
+        unsigned long long todo = __ballot(tiles != 0);   // batches whose pairs are still to be listed
+        if (todo) {
+            // what only the MFMAs need is set up here, from a lane number the compiler cannot hoist it by: the joint box test of phase 1 fills
+            // the 128 registers on its own (the queries' operands alone are four)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int r = ln & 31, h = ln >> 5, gl = r >> 4;   // my column's group
+            const int64_t qtl = qt0 + gl < a.nqtiles ? qt0 + gl : a.nqtiles - 1;
+            const hf8 bq = SQ[(qtl * 16 + (r & 15)) * 2 + h];
+            // the group's threshold as a float not above it (a NaN stays a NaN: nothing compares below it)
+            const double thrd = qbs[QG * 2 * PD + gl];
+            float thrf = (float)thrd;
+            if ((double)thrf > thrd) thrf = __builtin_fmaf(-__builtin_fabsf(thrf), 0x1p-23f, thrf) - 0x1p-126f;   // at least one ulp down
+            // my 16 bytes of a training row's operands: rows 0..15 of the product come from the pair's first tile, 16..31 from its second
+            const unsigned loff = (unsigned)((r & 15) * 32 + h * 16), second = r < 16 ? 0u : 1u;
+            const int tiles_lo = (int)(unsigned)tiles, tiles_hi = (int)(unsigned)(tiles >> 32);
+            const PBN_GLOBAL char* sbp = SAc + sb * 512;   // 512 B of operands per tile
+            struct Pair { unsigned j, a, b; };   // batch of the super-batch, first and second tile of the batch
+            Pair cur = {0u, 0u, 0u};       // the pair last listed
+            unsigned long long left = 0;   // tiles of batch cur.j not yet in a pair
+            auto next = [&]() -> bool {    // lists the next pair; false past the end (cur stays: that pair is loaded again)
+                if (left == 0 && todo != 0) {
+                    cur.j = (unsigned)__builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    left = (unsigned long long)(unsigned)__builtin_amdgcn_readlane(tiles_lo, (int)cur.j) |
+                           ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(tiles_hi, (int)cur.j) << 32);
+                }
+                if (left == 0) return false;
+                cur.a = (unsigned)__builtin_ctzll(left);
+                left &= left - 1;
+                cur.b = left ? (unsigned)__builtin_ctzll(left) : cur.a;   // an odd number of tiles: the last MFMA takes its tile twice
+                left &= left - 1;
+                return true;
+            };
+            // A scalar base per pair and a 32-bit lane offset.  The base goes through an empty asm: where the compiler can see that a slot past the
+            // end reloads the previous slot's pair it makes the load conditional - a copy of that slot's registers behind a vmcnt(0) - and the
+            // ring drains in every slot.
+            auto frag = [&](const Pair& d) -> hf8 {
+                unsigned base = (d.j * 64u + d.a) * 512u;
+                asm volatile("" : "+s"(base));
+                const PBN_GLOBAL char* p = sbp + (uint64_t)base;
+                return *(const PBN_GLOBAL hf8*)(p + (uint64_t)(loff + second * ((d.b - d.a) * 512u)));
+            };
+            auto slot = [&](const Pair& d, const hf8& af) {
+                f16acc acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bq, acc, 0, 0, 0);
+                // rows 0..15 of the product (tile A) sit in registers 0..7, rows 16..31 (tile B) in 8..15; the column - the query - is the lane
+                auto mx = [](float x, float y) { return __builtin_elementwise_maximum(x, y); };
+                const float mA = mx(mx(mx(mx(acc[0], acc[1]), acc[2]), mx(mx(acc[3], acc[4]), acc[5])), mx(acc[6], acc[7]));
+                const float mB = mx(mx(mx(mx(acc[8], acc[9]), acc[10]), mx(mx(acc[11], acc[12]), acc[13])), mx(acc[14], acc[15]));
+                const unsigned long long kA = __ballot(!(mA < thrf)), kB = __ballot(!(mB < thrf));
+                // group 0's columns are lanes 0..15 and 32..47: the halves of a ballot folded, its low 16 bits; group 1's the high 16
+                const unsigned fA = (unsigned)kA | (unsigned)(kA >> 32), fB = (unsigned)kB | (unsigned)(kB >> 32);
+                const unsigned long long l0 = ((fA & 0xffffu) ? 1ull << d.a : 0ull) | ((fB & 0xffffu) ? 1ull << d.b : 0ull);
+                const unsigned long long l1 = ((fA >> 16) ? 1ull << d.a : 0ull) | ((fB >> 16) ? 1ull << d.b : 0ull);
+                if (lane < QG) __hip_atomic_fetch_or(&msk[d.j * 4u + 2u + (unsigned)lane], lane ? l1 : l0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            };
+            Pair dq[R];
+            hf8 fq[R];
+            bool go = true;
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                next();
+                dq[i] = cur;
+                fq[i] = frag(cur);
+            }
+            do {
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    slot(dq[i], fq[i]);
+                    const bool more = next();
+                    if (i == 0) go = more;   // the next turn's first pair exists
+                    dq[i] = cur;
+                    fq[i] = frag(cur);
+                }
+            } while (go);
+        }
+        asm volatile("" ::: "memory");
+        if (bt < t1) {
+            const int64_t jb = (bt - t0) >> 6;
+            const unsigned long long lv0 = msk[lane * 4 + 2] & my_box[0], lv1 = msk[lane * 4 + 3] & my_box[1];
+            LM[jb * QG] = lv0;
+            LM[jb * QG + 1] = lv1;
+            if (BM) { BM[jb * QG] = msk[lane * 4]; BM[jb * QG + 1] = msk[lane * 4 + 1]; }
+            if (count && (lv0 | lv1)) atomicAdd(&g_screen_kept, (unsigned long long)(__builtin_popcountll(lv0) + __builtin_popcountll(lv1)));
+        }
+        asm volatile("" ::: "memory");   // (the next super-batch parks its words where these were read)
+    }
+    // the batch slots past the table's end in a short last split hold nothing: written too (see the serial kernel)
+    for (int64_t jb = ((t1 - t0 + 63) >> 6) + lane; jb < a.batches_per_split; jb += 64) {
+        LM[jb * QG] = 0;
+        LM[jb * QG + 1] = 0;
+        if (BM) { BM[jb * QG] = 0; BM[jb * QG + 1] = 0; }
+    }
+}
+
 void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t ntiles, bool is_query, void* out, hipStream_t st) {
     const int64_t npad = ntiles * 16;
     if (npad == 0) return;
@@ -225,11 +411,12 @@ void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t
     HIP_CHECK(hipGetLastError());
 }
 
-void launch_screen_d8(const SweepArgs& a_in, int nsplit, hipStream_t st) {
+void launch_screen_d8(const SweepArgs& a_in, int nsplit, bool stream, hipStream_t st) {
     SweepArgs a = a_in;
     a.nsplit_grid = nsplit;
     if (!a.scr_train || !a.scr_query || !a.live_mask || !a.batch_box || a.pdims != PBN_PRUNE_PD) throw invalid_error("KDE: the d = 8 screen needs its operands, masks and batch boxes");
     const dim3 grid((unsigned)(ceil_div(a.nqtiles, PBN_QG_PRUNE) * nsplit)), block(64);
-    hipLaunchKernelGGL(kde_screen_d8_kernel, grid, block, 0, st, a);
+    if (stream) hipLaunchKernelGGL(kde_screen_d8_kernel, grid, block, 0, st, a);
+    else hipLaunchKernelGGL(kde_screen_d8_serial_kernel, grid, block, 0, st, a);
     HIP_CHECK(hipGetLastError());
 }

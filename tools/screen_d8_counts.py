@@ -1,0 +1,98 @@
+"""Counts of the d = 8 f16 screen on the GPU: blocks kept / tested (PBN_SWEEP_COUNT_REDO=1, pbn_debug_d8_screen) and, from the dumped box
+masks (pbn_debug_d8_masks), the MFMA iterations the screen issues: sum over (wave, batch) of ceil(popcount(box0 | box1) / 2).
+    python tools/screen_d8_counts.py bench      bench.py's 1e6 x 1e5 table
+    python tools/screen_d8_counts.py test       the 100 000 x 2 000 table of tests/test_prune_d8_screen_gpu.py::test_no_dropped_block_holds_a_live_pair"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402  (before the library, as in tools/prune_d8_visits.py)
+import pybnesian_amd as pbn  # noqa: E402
+from pybnesian_amd import _lib  # noqa: E402
+
+which = sys.argv[1] if len(sys.argv) > 1 else "test"
+lib = _lib.load()
+lib.pbn_debug_d8_masks.restype = C.c_int64
+lib.pbn_debug_d8_masks.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_int]
+
+if which == "bench":
+    import bench
+
+    ctx = pbn.Context(0)
+    dev = torch.device("cuda", 0)
+    n_train, n_test = 1_000_000, 100_000
+    train_t, test_t = bench.make_tables(torch, dev, n_train, n_test, 0, 1, torch.float64)
+    torch.cuda.synchronize()
+    names = [f"v{i}" for i in range(bench.D)]
+    train = pbn.DeviceTable.from_device_pointer(ctx, train_t.data_ptr(), n_train, names, n_train, _lib.PBN_F64, keepalive=train_t)
+    test = pbn.DeviceTable.from_device_pointer(ctx, test_t.data_ptr(), n_test, names, n_test, _lib.PBN_F64, keepalive=test_t)
+    kde = pbn.ProductKDE(names)
+    kde.fit_table(train)
+    out = torch.zeros(1, dtype=torch.float64, device=dev)
+
+    def run():
+        kde.slogl_table_async(test, out.data_ptr())
+        ctx.sync()
+        return out.item()
+else:
+    import pandas as pd
+
+    d = 8
+    rng = np.random.default_rng(940 + d)
+    names = [f"v{i}" for i in range(d)]
+    mix = np.tril(np.full((d, d), 0.3), -1) + np.eye(d)
+    train = pd.DataFrame(rng.normal(size=(100_000, d)) @ mix.T, columns=names)
+    test = pd.DataFrame(rng.normal(size=(2_000, d)) @ mix.T, columns=names)
+    kde = pbn.ProductKDE(names)
+    kde.fit(train)
+
+    def run():
+        return kde.slogl(test)
+
+os.environ["PBN_SWEEP_COUNT_REDO"] = "1"
+lib.pbn_debug_d8_screen(None, None, 1)
+lib.pbn_debug_sweep_visits(None, None, 1)
+s = run()
+kept, tested, v, t = (C.c_ulonglong(0) for _ in range(4))
+lib.pbn_debug_d8_screen(C.byref(kept), C.byref(tested), 1)
+lib.pbn_debug_sweep_visits(C.byref(v), C.byref(t), 1)
+os.environ["PBN_SWEEP_COUNT_REDO"] = "0"
+print(f"{which}: slogl {s!r}; box-visited {v.value} of {t.value} offered ({v.value / max(t.value, 1):.4f}); "
+      f"screen kept {kept.value} of {tested.value} tested ({kept.value / max(tested.value, 1):.4f})")
+
+
+def fetch(what, dtype):
+    n = lib.pbn_debug_d8_masks(what, None, 0, 1)
+    a = np.zeros(n, dtype=dtype)
+    lib.pbn_debug_d8_masks(what, a.ctypes.data_as(C.c_void_p), n, 1)
+    return a
+
+
+lib.pbn_debug_d8_masks(0, None, 0, 1)
+try:
+    run()
+    nw, nsplit, bps, tps, ntiles, nq = (int(x) for x in fetch(0, np.int64))
+    box = fetch(1, np.uint64).reshape(nw, nsplit, bps, 2)
+    live = fetch(2, np.uint64).reshape(nw, nsplit, bps, 2)
+finally:
+    lib.pbn_debug_d8_masks(0, None, 0, 0)
+
+
+def popcount(a):
+    return np.unpackbits(np.ascontiguousarray(a).view(np.uint8).reshape(a.shape + (8,)), axis=-1).sum(axis=-1, dtype=np.int64)
+
+
+tiles = popcount(box[..., 0] | box[..., 1])          # per (wave, split, batch)
+iters = (tiles + 1) // 2
+blocks = int(popcount(box).sum())
+per_split = iters.sum(axis=2)
+print(f"  launch: {nw} waves x {nsplit} splits x {bps} batches of a split ({tps} tiles per split, {ntiles} tiles, {nq} queries)")
+print(f"  blocks in the box masks {blocks} (live {int(popcount(live).sum())}); batches in reach {int((tiles > 0).sum())} of {tiles.size}")
+print(f"  MFMA iterations {int(iters.sum())}: {blocks / max(int(iters.sum()), 1):.3f} blocks per iteration; tiles per batch in reach: "
+      f"mean {tiles[tiles > 0].mean():.2f}, odd {float((tiles[tiles > 0] & 1).mean()):.3f}")
+print(f"  iterations per (wave, split): mean {per_split.mean():.1f}, median {np.median(per_split):.0f}, max {per_split.max()}, "
+      f"zero {float((per_split == 0).mean()):.3f}")
