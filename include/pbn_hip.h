@@ -211,7 +211,11 @@ void pbn_scoredata_destroy(pbn_scoredata* sd);
 /* Dictionary-encoded columns (arrow::DictionaryArray indices, factors/discrete/discrete_indices.cpp): n_disc int32
  * arrays in SOURCE row order + cardinalities.  They get column ids n_cols .. n_cols+n_disc-1 in pbn_score_batch;
  * a continuous column with discrete parents is scored as CLinearGaussianCPD / HCKDE (DiscreteAdaptator.hpp:201-348),
- * a discrete column (node type PBN_NODE_DISCRETE, discrete parents only) as DiscreteFactor. */
+ * a discrete column (node type PBN_NODE_DISCRETE, discrete parents only) as DiscreteFactor.
+ * Code -1 is a null, accepted on PBN_SPLIT_NONE score data (BIC, BDe): a family's counts leave out the rows that are null in one of
+ * the family's own columns (discrete_indices.cpp:134-150), the grouping of a CLG candidate the rows that are null in a discrete parent
+ * (discrete_indices.cpp:169-204).  The tables of the likelihood scores are filtered before they are split and hold none: there -1 is
+ * PBN_ERR_INVALID like any other code out of range.  Call it after pbn_scoredata_set_validity. */
 int pbn_scoredata_set_discrete(pbn_scoredata* sd, int n_disc, const int32_t* const* codes, const int* cardinality);
 /* Score data of a table WITHOUT continuous columns (the DataFrame of a DiscreteBN under BIC / CVLikelihood / HoldoutLikelihood /
  * ValidatedLikelihood / BDe: learning/scores/bic.cpp:66-96, cv_likelihood.cpp:5-25 with learning/parameters/
@@ -225,7 +229,11 @@ int pbn_scoredata_create_discrete(pbn_ctx* ctx, int64_t n_rows, int split, int k
  * on the device and by the host loop (tables above 2^20 cells, more than 7 parents, PBN_DISCRETE_COUNTS=0), and kernel launches. */
 int pbn_scoredata_discrete_stats(const pbn_scoredata* sd, int64_t* device_units, int64_t* host_units, int64_t* launches);
 /* BIC / BGe on tables with nulls: masks[c] = byte array (1 = valid) of continuous column c in source row order, or
- * NULL when the column has no nulls (valid_rows / combined_bitmap semantics of bic.cpp:12-27, bge.hpp:184-234). */
+ * NULL when the column has no nulls (valid_rows / combined_bitmap semantics of bic.cpp:12-27, bge.hpp:184-234).  The values under
+ * null slots are never used as data, whatever the table holds there.  The masks also go to the device once, as ceil(n_cols / 64) 64-bit
+ * words per row (bit c = column c valid): the BIC / BGe candidates of a pbn_score_batch call that involve a column with nulls, and the
+ * cells of a CLG candidate under BIC, take their moments over the valid rows from one masked pass per batch (up to 8 columns per
+ * candidate).  PBN_NULL_MOMENTS=0 (read per call) keeps the per-candidate gather lists. */
 int pbn_scoredata_set_validity(pbn_scoredata* sd, const uint8_t* const* masks);
 /* perm: n_rows ints (source row of every permuted row); limits: k+1 fold limits; all nullable. */
 /* The split layout alone, host only (dataset::CrossValidation / HoldOut as stand-alone objects,

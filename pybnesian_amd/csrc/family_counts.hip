@@ -248,7 +248,8 @@ void count_families_device(const FamilyCodes& src, const std::vector<Region>& re
     }
 }
 
-// sd->codes (permuted row order) -> the device: int32 [n_disc][rows], and the byte mirror when every cardinality is <= 255
+// sd->codes (permuted row order) -> the device: int32 [n_disc][rows], and the byte mirror when every cardinality is <= 255 (a null code -1 is
+// 0xFF there, the rule of a pbn_dtable's mirror: family_byte_mirror_kernel keeps the low byte)
 void family_codes_upload(pbn_scoredata* sd) {
     pbn_ctx* ctx = sd->ctx;
     const int64_t rows = (int64_t)sd->perm.size();
@@ -285,7 +286,11 @@ void count_families(pbn_scoredata* sd, const std::vector<Region>& regions, const
         src.ctx = sd->ctx; src.scratch = sd; src.card = sd->card.data();
         src.codes32 = sd->codes_dev.p; src.ld32 = (int64_t)sd->perm.size();
         src.codes8 = sd->codes8.p; src.ld8 = sd->ld8;
-        src.nulls = false;   // the codes of score data hold no nulls (pbn_scoredata_set_discrete)
+        // null codes (BIC / BDe score data, pbn_scoredata_set_discrete): the null-aware instantiations, when a column of the call's families holds one
+        src.nulls = false;
+        if (sd->has_disc_nulls)
+            for (size_t f : dev)
+                for (int c : fams[f].cols) src.nulls = src.nulls || sd->disc_null[c];
         count_families_device(src, regions, fams, dev, sink);
     }
     std::vector<std::vector<int64_t>> tables;

@@ -73,6 +73,20 @@ void family_counts_host(const pbn_scoredata* sd, const std::vector<Region>& regi
         return c;
     };
     counts.assign(regions.size(), std::vector<int64_t>((size_t)joint, 0));
+    bool nulls = false;
+    if (sd->has_disc_nulls)
+        for (int c : f.cols) nulls = nulls || sd->disc_null[c];
+    if (nulls) {   // a row with a null (-1) in any column of the family is left out (discrete_indices.cpp:134-150)
+        auto is_null = [&](int64_t r) {
+            for (int i = 0; i < m; ++i)
+                if (sd->codes[f.cols[i]][r] < 0) return true;
+            return false;
+        };
+        for (size_t ri = 0; ri < regions.size(); ++ri)
+            for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r)
+                if (!is_null(r)) ++counts[ri][index(r)];
+        return;
+    }
     for (size_t ri = 0; ri < regions.size(); ++ri)
         for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r) ++counts[ri][index(r)];
 }
@@ -229,16 +243,37 @@ std::shared_ptr<const HybridGrouping> grouping_for(pbn_scoredata* sd, int kind, 
         for (size_t i = 0; i < dpar_sorted.size(); ++i) c += sd->codes[dpar_sorted[i] - sd->n][r] * strides[i];
         return c;
     };
+    bool nulls = false;   // null codes in a parent (BIC score data only): those rows belong to no configuration (discrete_indices.cpp:169-204)
+    if (sd->has_disc_nulls)
+        for (int dp : dpar_sorted) nulls = nulls || sd->disc_null[dp - sd->n];
+    auto is_null = [&](int64_t r) {
+        for (int dp : dpar_sorted)
+            if (sd->codes[dp - sd->n][r] < 0) return true;
+        return false;
+    };
     int64_t total = 0;
-    for (size_t ri = 0; ri < regions.size(); ++ri) {
-        for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r) ++g.off[(size_t)config(r) * regions.size() + ri + 1];
-        total += regions[ri].r1 - regions[ri].r0;
+    std::vector<int32_t> rows;
+    if (nulls) {
+        for (size_t ri = 0; ri < regions.size(); ++ri)
+            for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r)
+                if (!is_null(r)) { ++g.off[(size_t)config(r) * regions.size() + ri + 1]; ++total; }
+        for (size_t i = 0; i < cells; ++i) g.off[i + 1] += g.off[i];
+        rows.resize((size_t)total);
+        std::vector<int64_t> cur(g.off.begin(), g.off.end() - 1);
+        for (size_t ri = 0; ri < regions.size(); ++ri)
+            for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r)
+                if (!is_null(r)) rows[cur[(size_t)config(r) * regions.size() + ri]++] = (int32_t)r;
+    } else {
+        for (size_t ri = 0; ri < regions.size(); ++ri) {
+            for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r) ++g.off[(size_t)config(r) * regions.size() + ri + 1];
+            total += regions[ri].r1 - regions[ri].r0;
+        }
+        for (size_t i = 0; i < cells; ++i) g.off[i + 1] += g.off[i];
+        rows.resize((size_t)total);
+        std::vector<int64_t> cur(g.off.begin(), g.off.end() - 1);
+        for (size_t ri = 0; ri < regions.size(); ++ri)
+            for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r) rows[cur[(size_t)config(r) * regions.size() + ri]++] = (int32_t)r;
     }
-    for (size_t i = 0; i < cells; ++i) g.off[i + 1] += g.off[i];
-    std::vector<int32_t> rows((size_t)total);
-    std::vector<int64_t> cur(g.off.begin(), g.off.end() - 1);
-    for (size_t ri = 0; ri < regions.size(); ++ri)
-        for (int64_t r = regions[ri].r0; r < regions[ri].r1; ++r) rows[cur[(size_t)config(r) * regions.size() + ri]++] = (int32_t)r;
     // pieces of <= SEG_PIECE rows, cell by cell
     std::vector<int32_t> piece, piece_off(cells + 1, 0);
     for (size_t c = 0; c < cells; ++c) {
@@ -703,11 +738,91 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
     }
     auto cell = [&](int c, int r) { return (size_t)canon[c] * R + r; };
     std::vector<Stats> M;
-    group_moments(sd, g, cols.data(), d, M);
+    // BIC on a table with nulls in the candidate's continuous columns (bic.cpp:29-64: every configuration is fitted on the rows of its
+    // slice that are valid in the variable and the continuous parents): the cell moments and the cell N come from the masked pass over the
+    // grouping's row list (masked_moments.hip) - the grouping itself already leaves out the rows that are null in a discrete parent
+    bool null_clg = false;
+    if (kind == PBN_SCORE_BIC && sd->has_nulls)
+        for (int cc : cols) null_clg = null_clg || !sd->valid[cc].empty();
+    // ... and, for candidates wider than the masked pass takes (or with it switched off) and for the double-double refit, the grouped row
+    // list once more without the rows that are null in one of `cols`: one counting sort on the host, built when first asked for
+    struct Filtered { std::vector<int64_t> off; dev_buf<int32_t> rows; bool ready = false; } flt;
+    auto filtered = [&]() -> Filtered& {
+        if (flt.ready) return flt;
+        std::vector<int> cstride(dsorted.size(), 1);
+        int acc = 1;
+        for (size_t i = 0; i < dsorted.size(); ++i) { cstride[i] = acc; acc *= sd->card[dsorted[i] - n]; }
+        auto config = [&](int64_t r) {   // canonical configuration, or -1: null in a discrete parent or in one of the continuous columns
+            int c = 0;
+            for (size_t i = 0; i < dsorted.size(); ++i) {
+                const int32_t code = sd->codes[dsorted[i] - n][r];
+                if (code < 0) return -1;
+                c += code * cstride[i];
+            }
+            for (int cc : cols)
+                if (!sd->valid[cc].empty() && !sd->valid[cc][r]) return -1;
+            return c;
+        };
+        flt.off.assign((size_t)g.nc + 1, 0);
+        for (int64_t r = regions[0].r0; r < regions[0].r1; ++r) {
+            const int c = config(r);
+            if (c >= 0) ++flt.off[(size_t)c + 1];
+        }
+        for (int c = 0; c < g.nc; ++c) flt.off[(size_t)c + 1] += flt.off[(size_t)c];
+        std::vector<int32_t> rows((size_t)flt.off[(size_t)g.nc]);
+        std::vector<int64_t> cur(flt.off.begin(), flt.off.end() - 1);
+        for (int64_t r = regions[0].r0; r < regions[0].r1; ++r) {
+            const int c = config(r);
+            if (c >= 0) rows[(size_t)cur[(size_t)c]++] = (int32_t)r;
+        }
+        flt.rows.alloc(rows.size() + 16);
+        if (!rows.empty()) HIP_CHECK(hipMemcpyAsync(flt.rows.p, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the host vector goes out of scope
+        flt.ready = true;
+        return flt;
+    };
+    if (!null_clg) {
+        group_moments(sd, g, cols.data(), d, M);
+    } else if (d <= MASKED_MAX_COLS && masked_moments_on()) {
+        const size_t cells = (size_t)g.nc * R;   // (BIC: one region, cell = canonical configuration)
+        std::vector<MaskedUnit> unit(1);
+        unit[0].cols = cols;
+        unit[0].rows = g.rows.p;
+        unit[0].n_list = g.off[cells];
+        unit[0].seg_off = g.off;
+        std::vector<std::vector<MaskedMoments>> res;
+        masked_moments(sd, unit, res);
+        M.assign(cells, Stats());
+        for (size_t c = 0; c < cells; ++c) {
+            Stats& st = M[c];
+            st.zero(d);
+            st.N = res[0][c].N;
+            int pos = 0;
+            for (int i = 0; i < d; ++i) {
+                st.S[i] = res[0][c].S[i];
+                for (int j = i; j < d; ++j, ++pos) st.G[i + (size_t)j * d] = st.G[j + (size_t)i * d] = res[0][c].G[pos];
+            }
+        }
+    } else {
+        Filtered& f = filtered();
+        M.assign((size_t)g.nc, Stats());
+        for (int c = 0; c < g.nc; ++c) {
+            Stats& st = M[(size_t)c];
+            st.zero(d);
+            st.N = f.off[(size_t)c + 1] - f.off[(size_t)c];
+            if (st.N > 0) gram_raw(t, cols.data(), d, 0, st.N, f.rows.p + f.off[(size_t)c], sd->shift_dev.p, st.S.data(), st.G.data());
+        }
+    }
     std::vector<double> mu(d), sse((size_t)d * d), beta(d), H((size_t)d * d);
     // double-double refit of an ill-conditioned slice from its rows (lg_accurate.hip): the rows of configuration c are one
     // block of the grouped list, region u two ranges around its own rows
     auto refit = [&](int c, int u, int64_t ntrain, double* b) {
+        if (null_clg) {   // the same valid rows the moments were taken over
+            Filtered& f = filtered();
+            const int64_t base = f.off[(size_t)canon[c]];
+            if (f.off[(size_t)canon[c] + 1] - base != ntrain) throw device_error("masked moments: the pass and the validity masks disagree on the valid rows");
+            return lg_fit_accurate(t, cols.data(), d, base, ntrain, 0, ntrain, f.rows.p, b);
+        }
         const int64_t base = g.off[cell(c, 0)], end = g.off[cell(c, R - 1) + 1];
         if (u < 0) return lg_fit_accurate(t, cols.data(), d, base, ntrain, 0, ntrain, g.rows.p, b);   // one region: [base, base + ntrain)
         const int64_t f0 = g.off[cell(c, u)], f1 = g.off[cell(c, u) + 1];
@@ -722,6 +837,8 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
         for (int c = 0; c < g.nc; ++c) {
             const Stats& st = M[cell(c, 0)];
             valid += st.N;
+            // (tables with nulls: a configuration that has rows but none valid in the continuous columns is passed over like an empty one -
+            //  it adds nothing to the log-likelihood and nothing to `valid`, and stays in the penalty's configuration count)
             if (st.N == 0) continue;
             local_moments(sd, st, cols.data(), d, mu.data(), sse.data());
             bool suspect = false;

@@ -606,10 +606,16 @@ int pbn_scoredata_set_discrete(pbn_scoredata* sd, int n_disc, const int32_t* con
         sd->n_disc = n_disc;
         sd->codes.assign(n_disc, std::vector<int32_t>((size_t)rows));
         sd->card.assign(cardinality, cardinality + n_disc);
+        sd->disc_null.assign(n_disc, 0);
+        sd->has_disc_nulls = false;
+        // -1 = null, for BIC / BDe score data only (bic.cpp:66-96 and bde.cpp count over the rows valid in the family's columns,
+        // discrete_indices.cpp:134-150); the likelihood scores' tables were filtered before they were split and hold none
+        const bool nulls_ok = sd->split == PBN_SPLIT_NONE;
         for (int j = 0; j < n_disc; ++j)
             for (int64_t r = 0; r < rows; ++r) {
                 const int32_t v = codes[j][sd->perm[r]];
-                if (v < 0 || v >= cardinality[j]) throw invalid_error("pbn_scoredata_set_discrete: code out of range");
+                if (v == -1 && nulls_ok) { sd->disc_null[j] = 1; sd->has_disc_nulls = true; }
+                else if (v < 0 || v >= cardinality[j]) throw invalid_error("pbn_scoredata_set_discrete: code out of range");
                 sd->codes[j][r] = v;
             }
         family_codes_upload(sd);
@@ -626,6 +632,10 @@ int pbn_scoredata_set_validity(pbn_scoredata* sd, const uint8_t* const* masks) {
         if (sd->discrete_only) throw invalid_error("pbn_scoredata_set_validity: discrete-only score data has no continuous columns");
         if (sd->split != PBN_SPLIT_NONE) throw invalid_error("pbn_scoredata_set_validity: only for BIC / BGe score data");
         const int64_t rows = (int64_t)sd->perm.size();
+        // what was derived under the previous masks (cell moments of the groupings) is stale: let the work in flight finish, then drop it
+        HIP_CHECK(hipStreamSynchronize(sd->ctx->stream));
+        sd->ctx->sync_lanes(pbn_ctx::MAX_PARKED);
+        sd->groupings.clear();
         sd->valid.assign(sd->n, {});
         sd->has_nulls = false;
         for (int c = 0; c < sd->n; ++c)
@@ -633,6 +643,7 @@ int pbn_scoredata_set_validity(pbn_scoredata* sd, const uint8_t* const* masks) {
                 sd->valid[c].assign(masks[c], masks[c] + rows);
                 sd->has_nulls = true;
             }
+        masked_validity_upload(sd);   // the same bits as words on the device, for the masked pass (masked_moments.hip)
     });
 }
 
@@ -822,6 +833,47 @@ static int score_batch_impl(pbn_scoredata* sd, int kind, int n_cand, const int* 
         Stats train;
         std::vector<int> cols;
         std::vector<double> mu, sse, beta, H;
+        // Tables with nulls: the plain BIC / BGe candidates that involve a column with nulls, deduplicated by ordered column list, take their
+        // moments over the rows valid in all of their columns from ONE masked pass over the batch (masked_moments.hip) instead of a host
+        // loop over the rows, an upload and a gathered Gram each.  (More than 8 columns, or PBN_NULL_MOMENTS=0: the per-candidate path.)
+        std::map<std::vector<int>, size_t> masked_of;
+        std::vector<std::vector<MaskedMoments>> masked;
+        if (sd->has_nulls && (kind == PBN_SCORE_BIC || kind == PBN_SCORE_BGE) && masked_moments_on()) {
+            std::vector<MaskedUnit> units;
+            for (int c = 0; c < n_cand; ++c) {
+                const int p = par_off[c + 1] - par_off[c];
+                if (p + 1 > MASKED_MAX_COLS) continue;
+                cols.resize(p + 1);
+                cols[0] = var[c];
+                for (int i = 0; i < p; ++i) cols[i + 1] = parents[par_off[c] + i];
+                bool plain = true, involved = false;
+                for (int cc : cols) {
+                    plain = plain && cc >= 0 && cc < sd->n;   // (out of range: the loop below throws; discrete: hybrid.hip)
+                    involved = involved || (plain && !sd->valid[cc].empty());
+                }
+                if (!plain || !involved || masked_of.count(cols)) continue;
+                masked_of.emplace(cols, units.size());
+                units.push_back(MaskedUnit{cols, nullptr, 0, {}});
+            }
+            masked_moments(sd, units, masked);
+        }
+        // the gather list of a candidate's valid rows (DataFrame::combined_bitmap, dataset.cpp:208-235) -> sd->rows_dev
+        auto gather_rows = [&](const std::vector<int>& cs) {
+            const int64_t rows = (int64_t)sd->perm.size();
+            std::vector<int32_t> keep;
+            keep.reserve(rows);
+            for (int64_t r = 0; r < rows; ++r) {
+                bool ok = true;
+                for (int cc : cs) ok = ok && (sd->valid[cc].empty() || sd->valid[cc][r]);
+                if (ok) keep.push_back((int32_t)r);
+            }
+            sd->rows_dev.reserve(keep.size() + 16);
+            if (!keep.empty()) {
+                HIP_CHECK(hipMemcpyAsync(sd->rows_dev.p, keep.data(), keep.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+                HIP_CHECK(hipStreamSynchronize(ctx->stream));   // keep goes out of scope
+            }
+            return (int64_t)keep.size();
+        };
         for (int c = 0; c < n_cand; ++c) {
             const int p = par_off[c + 1] - par_off[c];
             const int d = p + 1;
@@ -870,10 +922,16 @@ static int score_batch_impl(pbn_scoredata* sd, int kind, int n_cand, const int* 
             mu.resize(d); sse.resize((size_t)d * d); beta.resize(d);
             const Stats* full = &sd->all;
             Stats gathered;
+            bool from_masked = false;   // `gathered` came from the masked pass: no gather list on the device yet
             if (sd->has_nulls && (kind == PBN_SCORE_BIC || kind == PBN_SCORE_BGE)) {
                 bool involved = false;
                 for (int cc : cols) involved = involved || !sd->valid[cc].empty();
-                if (involved) {
+                const auto mit = involved ? masked_of.find(cols) : masked_of.end();
+                if (mit != masked_of.end()) {
+                    masked_to_stats(sd, cols.data(), d, masked[mit->second][0], gathered);
+                    full = &gathered;
+                    from_masked = true;
+                } else if (involved) {
                     // rows valid in every involved column (DataFrame::combined_bitmap, dataset.cpp:208-235)
                     const int64_t rows = (int64_t)sd->perm.size();
                     std::vector<int32_t> keep;
@@ -905,6 +963,7 @@ static int score_batch_impl(pbn_scoredata* sd, int kind, int n_cand, const int* 
                 bool suspect = false;
                 double v = lg_fit(full->N, p, mu.data(), sse.data(), beta.data(), &suspect);
                 if (suspect && lg_guard_on() && d <= 16) {   // nearly collinear parents / nearly exact fit: double-double refit
+                    if (from_masked && gather_rows(cols) != full->N) throw device_error("masked moments: the pass and the validity masks disagree on the valid rows");
                     if (full == &gathered) v = lg_fit_accurate(t, cols.data(), d, 0, full->N, 0, full->N, sd->rows_dev.p, beta.data());
                     else v = lg_fit_accurate(t, cols.data(), d, 0, sd->n_cv, 0, sd->n_cv, nullptr, beta.data());
                 }

@@ -120,6 +120,17 @@ struct pbn_scoredata : pbn::score::FamilyScratch {
     // validity of the continuous columns (BIC / BGe on tables with nulls): byte masks, empty = no nulls
     std::vector<std::vector<uint8_t>> valid;
     bool has_nulls = false;
+    // the same validity once more on the device (masked_moments.hip): valid_nw = ceil(n / 64) 64-bit words per row, bit c of a row's words
+    // set when column c is valid there; empty without nulls.  mm_*: the masked pass's grow-only buffers and its counters.
+    pbn::dev_buf<uint64_t> valid_words;
+    int valid_nw = 0;
+    pbn::dev_buf<char> mm_descs;
+    pbn::dev_buf<int32_t> mm_owner;
+    pbn::dev_buf<double> mm_partial;
+    int64_t mm_launches = 0, mm_units = 0;
+    // null codes (-1) of the discrete columns (BIC / BDe score data only): per column, and whether any column holds one
+    std::vector<char> disc_null;
+    bool has_disc_nulls = false;
 };
 
 namespace pbn {
@@ -218,6 +229,26 @@ struct DiscreteCand {
 };
 void check_discrete_candidate(const pbn_scoredata* sd, int kind, int node_type, const int* parents, int p);
 void score_discrete_batch(pbn_scoredata* sd, int kind, double iss, std::vector<DiscreteCand>& cands);
+// masked_moments.hip: (N, S, upper triangle of G) of up to 8 continuous columns over the rows valid in all of them, for a batch of units in
+// one device pass.  rows == nullptr: the unit's rows are all rows of the table, one segment; else a device row list of n_list entries cut
+// into the segments [seg_off[s], seg_off[s + 1]).  G row by row: (0,0) (0,1) ... (0,d-1) (1,1) ...
+constexpr int MASKED_MAX_COLS = 8;
+struct MaskedUnit {
+    std::vector<int> cols;
+    const int32_t* rows = nullptr;
+    int64_t n_list = 0;
+    std::vector<int64_t> seg_off;
+};
+struct MaskedMoments {
+    int64_t N = 0;
+    double S[MASKED_MAX_COLS] = {};
+    double G[MASKED_MAX_COLS * (MASKED_MAX_COLS + 1) / 2] = {};
+};
+bool masked_moments_on();   // PBN_NULL_MOMENTS (default 1)
+void masked_validity_upload(pbn_scoredata* sd);   // after pbn_scoredata_set_validity filled sd->valid
+void masked_moments(pbn_scoredata* sd, const std::vector<MaskedUnit>& units, std::vector<std::vector<MaskedMoments>>& out);
+// a unit's moments as Stats over all n columns (the unit's entries filled in, the rest zero)
+void masked_to_stats(const pbn_scoredata* sd, const int* cols, int d, const MaskedMoments& m, Stats& st);
 struct HybridBatch;
 HybridBatch* hybrid_batch_begin(pbn_scoredata* sd);
 void hybrid_batch_flush(HybridBatch* hb);

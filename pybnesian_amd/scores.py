@@ -149,6 +149,21 @@ def _discrete_stats(handle):
     return d.value, h.value, l.value
 
 
+def _dictionary_codes(arr):
+    """int32 dictionary indices of a dictionary array, -1 under null slots: what pbn_scoredata_set_discrete takes (built the way
+    MutualInformation builds its codes)."""
+    import pyarrow as pa
+
+    if isinstance(arr, pa.ChunkedArray):
+        arr = arr.combine_chunks()
+    idx = arr.indices
+    if arr.null_count:
+        import pyarrow.compute as pc
+
+        idx = pc.if_else(arr.is_valid(), idx, pa.scalar(-1, type=idx.type))
+    return np.ascontiguousarray(idx.to_numpy(zero_copy_only=False), dtype=np.int32)
+
+
 class _DeviceScore(Score):
     """Score evaluated by the batched HIP engine (pbn_score_batch)."""
 
@@ -172,7 +187,7 @@ class _DeviceScore(Score):
                 if pa.types.is_dictionary(f.type):
                     arr = rb.column(rb.schema.get_field_index(f.name))
                     self._disc_names.append(f.name)
-                    self._disc_codes.append(np.ascontiguousarray(arr.indices.to_numpy(zero_copy_only=False), dtype=np.int32))
+                    self._disc_codes.append(_dictionary_codes(arr))
                     self._disc_card.append(len(arr.dictionary))
                     self._categories[f.name] = arr.dictionary.to_pylist()
                 else:
@@ -226,7 +241,8 @@ class _DeviceScore(Score):
     def _handle_nulls(self, rb):
         """Likelihood scores: CrossValidation / HoldOut keep only the rows that are valid in EVERY column
         (crossvalidation_adaptator.hpp:24-37).  BIC / BGe: per-candidate valid rows (bic.cpp:12-27) - the values
-        under null slots are zeroed for the upload and the validity masks go to the engine."""
+        under null slots are zeroed for the upload and the validity masks go to the engine; dictionary columns keep
+        their nulls and reach the engine as code -1 (_dictionary_codes)."""
         import pyarrow as pa
         import pyarrow.compute as pc
 
@@ -244,9 +260,7 @@ class _DeviceScore(Score):
         for i, f in enumerate(rb.schema):
             col = rb.column(i)
             m = validity_mask(col)
-            if m is not None:
-                if pa.types.is_dictionary(f.type):
-                    raise ValueError("Discrete columns with nulls are not supported by the device score engine.")
+            if m is not None and not pa.types.is_dictionary(f.type):
                 self._masks[f.name] = m
                 col = pc.fill_null(col, 0.0)
             arrays.append(col)
@@ -558,9 +572,8 @@ class _ScoreView:
 class BDe(Score):
     """learning/scores/bde.{hpp,cpp}: Bayesian Dirichlet equivalent score of discrete networks, BDe(df, iss=1).  A device score: the
     categorical columns become discrete-only score data (pbn_scoredata_create_discrete) and every local score is a PBN_SCORE_BDE candidate
-    of pbn_score_batch - the hill-climb hands it whole batches, whose family tables are counted in one device pass.  A table whose
-    categorical columns hold nulls keeps the counts of `MutualInformation` (`pbn_mi_counts`, one row grouping per family) and Python
-    arithmetic: the engine takes no null codes."""
+    of pbn_score_batch - the hill-climb hands it whole batches, whose family tables are counted in one device pass.  Nulls go in as code
+    -1: a family's table counts the rows valid in the family's own columns (discrete_indices.cpp:134-150)."""
 
     _kind = _lib.PBN_SCORE_BDE
 
@@ -575,20 +588,15 @@ class BDe(Score):
         columns = {d: rb.column(rb.schema.get_field_index(d)) for d in disc}
         self._card = {d: len(columns[d].dictionary) for d in disc}
         self._col = {d: i for i, d in enumerate(disc)}
-        self._handle, self._counts, self._comm = None, None, None
+        self._handle, self._comm = None, None
         self._discrete_only = True
         if not disc:
-            return
-        if any(columns[d].null_count for d in disc):
-            from .independences import MutualInformation
-
-            self._counts = MutualInformation(rb.select(disc), True, ctx)
             return
         self._ctx = ctx or default_context()
         h = C.c_void_p()
         _lib.check(_lib.load().pbn_scoredata_create_discrete(self._ctx.handle, int(rb.num_rows), _lib.PBN_SPLIT_NONE, 0, C.c_uint32(0), 0.0, C.byref(h)))
         self._handle = h
-        codes = [np.ascontiguousarray(columns[d].indices.to_numpy(zero_copy_only=False), dtype=np.int32) for d in disc]
+        codes = [_dictionary_codes(columns[d]) for d in disc]
         ptrs = (C.c_void_p * len(codes))(*[c.ctypes.data for c in codes])
         _lib.check(_lib.load().pbn_scoredata_set_discrete(h, len(codes), ptrs, _lib.int_array([self._card[d] for d in disc])))
         self._params = np.asarray([self._iss])
@@ -624,33 +632,12 @@ class BDe(Score):
                                                    _lib.int_array(par if par else [0]), _lib.dptr(self._params), 1, _lib.dptr(out)))
         return out
 
-    def _joint_counts(self, variables):
-        lib = _lib.load()
-        h = self._counts._handle
-        _lib.check(lib.pbn_mi_set_order(h, 0, None))
-        out = np.zeros(int(np.prod([self._card[v] for v in variables])))
-        _lib.check(lib.pbn_mi_counts(h, len(variables), _lib.int_array([self._counts._var(v) for v in variables]), _lib.dptr(out)))
-        return out
-
     def _bde(self, variable, parents):
         for v in [variable] + list(parents):
             if v not in self._card:
                 raise ValueError(f"Variable {v} is not categorical.")
-        if self._handle is not None:
-            code = _lib.PBN_NODE_DISCRETE
-            return float(self._engine_batch_raw(None, [self._col[variable]], [code], [0, len(parents)], [self._col[p] for p in parents], self._kind)[0])
-        from math import lgamma
-
-        counts = self._joint_counts([variable] + list(parents))
-        card0 = self._card[variable]
-        total = counts.size
-        alpha = self._iss / total
-        res = -total * lgamma(alpha) + float(sum(lgamma(m + alpha) for m in counts))
-        if not parents:   # bde.cpp:5-21
-            return res + lgamma(self._iss) - lgamma(self._iss + float(counts.sum()))
-        sums = counts.reshape(-1, card0).sum(axis=1)   # bde.cpp:23-50: one term per parent configuration
-        sum_alpha = alpha * card0
-        return res + float(sum(lgamma(sum_alpha) - lgamma(sum_alpha + s) for s in sums))
+        code = _lib.PBN_NODE_DISCRETE
+        return float(self._engine_batch_raw(None, [self._col[variable]], [code], [0, len(parents)], [self._col[p] for p in parents], self._kind)[0])
 
     def local_score(self, model, variable, evidence=None):
         evidence = model.parents(variable) if evidence is None else list(evidence)

@@ -4,7 +4,8 @@
                pbn_score_batch, rows 5e3 / 1e5 / 1e6, for BIC, CVLikelihood (k = 10) and BDe: the device count pass against
                PBN_DISCRETE_COUNTS=0 on the same build (the host loop, the code from before the pass), a fresh score object per repetition
                for the likelihood scores (they remember local scores).  BDe also against its class from before the engine path: one
-               `pbn_mi_counts` row grouping and a Python lgamma loop per candidate (what a table with null codes still takes).
+               `pbn_mi_counts` row grouping and a Python lgamma loop per candidate (ParentBDe below; what a table with null codes took as well
+               until the engine accepted them: tools/null_scores_timing.py).
   hc           GreedyHillClimbing to convergence over a 20-node DiscreteBN with BDe at 1e5 rows: the engine path (whole batches) against
                the same score behind a plain Score subclass (one trampoline call per candidate)
   large        the global form: a batch of 24 five-parent families of five-category columns (15 625 cells each) at 1e5 and 1e6 rows,
@@ -71,17 +72,44 @@ def encode(score, cands):
     return var, [_lib.PBN_NODE_DISCRETE] * len(var), off, par
 
 
-def parent_bde(pbn, df):
-    """BDe as it was before the engine path - today's path for tables with null codes: MutualInformation counts, Python arithmetic."""
-    from pybnesian_amd import _lib
-    from pybnesian_amd.independences import MutualInformation
+class ParentBDe:
+    """BDe as it was before the engine path (and, until null codes reached the engine, the path of tables with nulls): one
+    `pbn_mi_counts` row grouping per family through a MutualInformation handle, Python lgamma arithmetic (bde.cpp:5-47)."""
 
-    s = pbn.BDe(df)
-    _lib.load().pbn_scoredata_destroy(s._handle)
-    s._handle = None
-    del s._batch_raw
-    s._counts = MutualInformation(s._rb, True)
-    return s
+    def __init__(self, df, iss=1.0):
+        from pybnesian_amd.dataset import as_record_batch
+        from pybnesian_amd.independences import MutualInformation
+
+        rb = as_record_batch(df)
+        self._iss = float(iss)
+        self._card = {f.name: len(rb.column(i).dictionary) for i, f in enumerate(rb.schema)}
+        self._counts = MutualInformation(rb, True)
+
+    def _joint_counts(self, variables):
+        from pybnesian_amd import _lib
+
+        lib, h = _lib.load(), self._counts._handle
+        _lib.check(lib.pbn_mi_set_order(h, 0, None))
+        out = np.zeros(int(np.prod([self._card[v] for v in variables])))
+        _lib.check(lib.pbn_mi_counts(h, len(variables), _lib.int_array([self._counts._var(v) for v in variables]), _lib.dptr(out)))
+        return out
+
+    def local_score(self, model, variable, parents):
+        from math import lgamma
+
+        counts = self._joint_counts([variable] + list(parents))
+        card0, total = self._card[variable], counts.size
+        alpha = self._iss / total
+        res = -total * lgamma(alpha) + float(sum(lgamma(m + alpha) for m in counts))
+        if not parents:
+            return res + lgamma(self._iss) - lgamma(self._iss + float(counts.sum()))
+        sums = counts.reshape(-1, card0).sum(axis=1)
+        sum_alpha = alpha * card0
+        return res + float(sum(lgamma(sum_alpha) - lgamma(sum_alpha + s) for s in sums))
+
+
+def parent_bde(pbn, df):
+    return ParentBDe(df)
 
 
 def section_start(rows):
