@@ -341,8 +341,8 @@ void launch_sweep(const SweepArgs& a, int dtype, int KS, bool cond, int nsplit, 
 // the f16 screen of the pruned sum-only d = 8 sweep: operands from whitened rows z [n][8] (perm: sorted position -> row, null = sorted already)
 // into out [ntiles * 16][32 B], and the pass that fills SweepArgs::live_mask for the sweep launched with the same arguments and nsplit
 void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t ntiles, bool is_query, void* out, hipStream_t st);
-// (stream: the two-phase kernel with its ring of fragment loads; false = the serial kernel it replaces, PBN_D8_SCREEN_STREAM=0)
-void launch_screen_d8(const SweepArgs& a, int nsplit, bool stream, hipStream_t st);
+// (which = PBN_D8_SCREEN_STREAM: 0 the serial kernel, 1 the two-phase kernel with its ring of fragment loads over a pair list, else the dense kernel)
+void launch_screen_d8(const SweepArgs& a, int nsplit, int which, hipStream_t st);
 void launch_finish(const FinishArgs& a, bool cond, double* dev_sum_out, hipStream_t st, double* dev_sum_marg_out = nullptr);
 // out[0] = sum of in[0 .. n), fixed order (kde_finish.hip; launch_ucv in kde_cdf.hip ends with it too - a call between two units of the
 // library, not one of its exports)

@@ -685,7 +685,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         sa.box_mask = mdbg ? (unsigned long long*)(sp + scrq_b + mask_b) : nullptr;
         KernelTimer kt(ctx, PBN_K_PACK);
         launch_screen_pack(qs.zrow, qs.perm, n, nqtiles, true, sp, ctx->stream);
-        launch_screen_d8(sa, (int)nsplit, knob_int("PBN_D8_SCREEN_STREAM", 1) != 0, ctx->stream);   // (0: the serial kernel, the same masks; read per evaluation)
+        launch_screen_d8(sa, (int)nsplit, knob_int("PBN_D8_SCREEN_STREAM", 2), ctx->stream);   // (0: the serial kernel, 1: the ring, else the dense kernel: the same masks; read per evaluation)
     }
     { KernelTimer kt(ctx, PBN_K_SWEEP); launch_sweep(sa, fdt, m.KS, m.cond, (int)nsplit, ctx->stream); }
     if (screen && mdbg) {

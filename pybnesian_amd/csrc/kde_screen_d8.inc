@@ -404,6 +404,256 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
     }
 }
 
+// The screen without a pair list (round 13).  The ring's slot is 87 instructions, most of them scalar and in dependent chains - find-first-bit,
+// clear, readlane, the shifts that make a pair and its address, the masks of the LDS OR - and all of that walks a list that is not sparse: inside
+// a batch in reach 47 of the 64 tiles pass a box test (profiles/r13/step0.txt).  This kernel screens CONSECUTIVE tile pairs (2p, 2p + 1) instead,
+// in units of four pairs = 4 KiB of operands: from the unit of the first set bit of the batch's box words to the unit of the last.  A unit is one
+// scalar base, four loads at immediate offsets 0 .. 3 KiB, four MFMAs per served sweep wave, and the eight result bits of a wave land at
+// compile-time positions of a byte per lane, which one 64-bit shift by 8 x unit puts into the lane's word of the batch.  Behind a batch's last
+// unit the words are ORed over each group's 32 lanes (four DPP steps inside a row of 16, the rows by readlane: lanes 0-15 and 32-47 hold
+// group 0's columns) and kept by lane = batch.  A tile's bit depends on its own 16 rows and the group's 16 queries only - an MFMA output element
+// does not depend on what else shares the instruction - and live = screened AND box, so bits of tiles that fail the box test, which the list
+// never screened, change nothing: the words are the serial kernel's, bit for bit (tests/test_prune_d8_screen_dense_gpu.py).
+// Two units of loads (8 fragments) are in flight: the list of (batch, unit) runs two units ahead of the MFMAs, across batches, and past its end
+// the last unit is loaded again (unconditional loads, counted vmcnt waits) and its bits are shifted out.  A unit that would read beyond the
+// table's last tile is moved back by whole tiles and its byte shifted right by as many: no tile at or beyond ntiles is read (ntiles >= 8:
+// launch_screen_d8 hands smaller tables to the ring).
+// NW = sweep waves served by one screen wave (NW x 2 query groups against one stream of fragments): phase 1 runs per served wave in turn, a
+// batch's units run the MFMAs of the served waves in reach of it.
+template <int NW>
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kernel(SweepArgs a) {
+    constexpr int QG = PBN_QG_PRUNE, PD = PBN_PRUNE_PD, QW = QG * (2 * PD + 1);
+    static_assert(QG == 2, "two groups = the 32 columns of the MFMA");
+    static_assert(NW == 1 || NW == 2, "sweep waves per screen wave");
+    const int lane = threadIdx.x & 63;
+    int qxs, split;
+    pruned_block(a, QG * NW, blockIdx.x, qxs, split);
+    if ((int64_t)qxs * NW * QG >= a.nqtiles) return;
+    const int64_t t0 = (int64_t)split * a.tiles_per_split;
+    const int64_t t1 = (t0 + a.tiles_per_split < a.ntiles) ? t0 + a.tiles_per_split : a.ntiles;
+    const PBN_GLOBAL double* __restrict__ TBp = (const PBN_GLOBAL double*)a.tile_box;
+    const PBN_GLOBAL double* __restrict__ QBp = (const PBN_GLOBAL double*)a.qtile_box;
+    const PBN_GLOBAL double* __restrict__ QTp = (const PBN_GLOBAL double*)a.qtile_thr;
+    const PBN_GLOBAL char* __restrict__ SAc = (const PBN_GLOBAL char*)a.scr_train;
+    const PBN_GLOBAL hf8* __restrict__ SQ = (const PBN_GLOBAL hf8*)a.scr_query;
+    __shared__ double qbs[NW * QW];                       // per served wave: the groups' boxes and thresholds, as in the serial kernel
+    __shared__ unsigned long long msk[NW * 64 * QG];      // per served wave and batch of the super-batch: the box words of its groups
+    for (int w = 0; w < NW; ++w) {
+        const int64_t qt0 = ((int64_t)qxs * NW + w) * QG;
+        if (lane < QG * 2 * PD) {
+            const int g = lane / (2 * PD);
+            const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+            qbs[w * QW + lane] = QBp[qt * 2 * PD + (lane - g * 2 * PD)];
+        } else if (lane < QW) {
+            const int g = lane - QG * 2 * PD;
+            const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
+            qbs[w * QW + lane] = QTp[qt] - a.prune_margin;
+        }
+    }
+    asm volatile("" ::: "memory");   // (one wave per workgroup, LDS in order: no barrier)
+    const bool count = a.count_redo != 0;
+    const int64_t wave_words = (int64_t)a.nsplit_grid * a.batches_per_split * QG;   // of one sweep wave in live_mask / box_mask
+    const int64_t word0 = ((int64_t)qxs * NW * a.nsplit_grid + split) * a.batches_per_split * QG;
+    PBN_GLOBAL unsigned long long* LM = (PBN_GLOBAL unsigned long long*)a.live_mask + word0;
+    PBN_GLOBAL unsigned long long* BM = a.box_mask ? (PBN_GLOBAL unsigned long long*)a.box_mask + word0 : nullptr;
+    if (count && lane == 0)   // once per served sweep wave, as the ring and the serial kernel count
+        for (int w = 0; w < NW && ((int64_t)qxs * NW + w) * QG < a.nqtiles; ++w) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
+    for (int64_t sb = t0; sb < t1; sb += 4096) {
+        // ---- phase 1: the box words of the super-batch's batches (lane = batch), one served sweep wave after the other
+        const int64_t bt = sb + 64 * lane;   // my batch's first tile
+        const PBN_GLOBAL double* bb = (const PBN_GLOBAL double*)a.batch_box + ((int64_t)split * a.batches_per_split + ((bt - t0) >> 6)) * 2 * PD;
+        unsigned long long tiles = 0;        // of my batch: in reach of any served wave
+        unsigned served = 0;                 // of my batch: the served waves in reach
+#pragma unroll 1
+        for (int w = 0; w < NW; ++w) {
+            const double* qw = (const double*)&qbs[w * QW];
+            unsigned long long my_box[QG] = {0, 0};
+            if (((int64_t)qxs * NW + w) * QG < a.nqtiles) {
+                unsigned long long bmg[QG], bm = 0;
+#pragma unroll
+                for (int g = 0; g < QG; ++g) {
+                    bmg[g] = __ballot(bt < t1 && batch_in_reach<PD>(bb, qw + g * 2 * PD, PD, qw[QG * 2 * PD + g]));
+                    bm |= bmg[g];
+                }
+                while (bm) {
+                    const int j = __builtin_ctzll(bm);
+                    bm &= bm - 1;
+                    const int64_t tb = sb + 64 * (int64_t)j;
+                    const unsigned gsel = (unsigned)((bmg[0] >> j) & 1ull) | ((unsigned)((bmg[1] >> j) & 1ull) << 1);
+                    unsigned long long gm[QG];
+                    if (gsel == 3u) {
+                        const double* qb[QG] = {qw, qw + 2 * PD};
+                        const double thr[QG] = {qw[QG * 2 * PD], qw[QG * 2 * PD + 1]};
+                        prune_group_masks_joint<PD, QG>(TBp, qb, PD, tb, t1, thr, lane, gm);
+                    } else {
+#pragma unroll
+                        for (int g = 0; g < QG; ++g)
+                            gm[g] = ((gsel >> g) & 1u) ? prune_group_mask<PD>(TBp, qw + g * 2 * PD, PD, tb, t1, qw[QG * 2 * PD + g], lane) : 0ull;
+                    }
+                    if (count && lane == 0 && (gm[0] | gm[1])) {
+                        atomicAdd(&g_sweep_visit, (unsigned long long)(__builtin_popcountll(gm[0]) + __builtin_popcountll(gm[1])));
+                        atomicAdd(&g_screen_tested, (unsigned long long)(__builtin_popcountll(gm[0]) + __builtin_popcountll(gm[1])));
+                    }
+                    if (lane == j) { my_box[0] = gm[0]; my_box[1] = gm[1]; }
+                }
+            }
+            msk[(w * 64 + lane) * QG] = my_box[0];
+            msk[(w * 64 + lane) * QG + 1] = my_box[1];
+            tiles |= my_box[0] | my_box[1];
+            served |= (my_box[0] | my_box[1]) ? 1u << w : 0u;
+        }
+        asm volatile("" ::: "memory");
+        // ---- phase 2: the units of the batches in reach, two units of loads ahead of the MFMAs.  Everything that names a unit is scalar.
+        unsigned long long my_scr[NW][QG];   // of MY batch (lane = batch): the tiles the screen could not prove dead, per served wave and group
+#pragma unroll
+        for (int w = 0; w < NW; ++w) { my_scr[w][0] = 0; my_scr[w][1] = 0; }
+        unsigned long long todo = __ballot(tiles != 0);   // batches whose units are still to be listed
+        if (todo) {
+            // what only the MFMAs need is set up here, from a lane number the compiler cannot hoist it by (see kde_screen_d8_kernel)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const int r = ln & 31, h = ln >> 5, gl = r >> 4;   // my column's group
+            hf8 bq[NW];
+            float thrf[NW];
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                const int64_t qt0 = ((int64_t)qxs * NW + w) * QG;
+                const int64_t qtl = qt0 + gl < a.nqtiles ? qt0 + gl : a.nqtiles - 1;
+                bq[w] = SQ[(qtl * 16 + (r & 15)) * 2 + h];
+                // the group's threshold as a float not above it (a NaN stays a NaN: nothing compares below it)
+                const double thrd = qbs[w * QW + QG * 2 * PD + gl];
+                float tf = (float)thrd;
+                if ((double)tf > thrd) tf = __builtin_fmaf(-__builtin_fabsf(tf), 0x1p-23f, tf) - 0x1p-126f;   // at least one ulp down
+                thrf[w] = tf;
+            }
+            // my 16 bytes of a pair's KiB: rows 0..15 of the product come from tile 2p, 16..31 from tile 2p + 1
+            const unsigned loff = (unsigned)(r * 32 + h * 16);
+            const int tiles_lo = (int)(unsigned)tiles, tiles_hi = (int)(unsigned)(tiles >> 32);
+            const int served_v = (int)served;
+            const PBN_GLOBAL char* sbp = SAc + sb * 512;                                           // the super-batch's operands
+            const int left = (int)(a.ntiles - sb < 8192 ? a.ntiles - sb : 8192);                   // tiles of the table from the super-batch's first
+            // batch of the super-batch, unit of the batch, tiles the loads are moved back by, tiles the byte is shifted by (the same; 8 = not a
+            // unit, every bit shifted out), served waves in reach, the batch's last unit
+            struct Unit { unsigned j, u, back, sh, sel; bool last; };
+            unsigned cj = 0, cu = 0, ce = 0, csel = 0;   // the list's cursor: batch, unit, the batch's last unit, its served waves
+            bool started = false;
+            auto next = [&]() -> Unit {   // lists the next unit; past the end the last one again, as no unit
+                bool ok = true;
+                if (started && cu < ce) ++cu;
+                else if (todo != 0) {
+                    started = true;
+                    cj = (unsigned)__builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    const unsigned long long t = (unsigned long long)(unsigned)__builtin_amdgcn_readlane(tiles_lo, (int)cj) |
+                                                 ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(tiles_hi, (int)cj) << 32);
+                    cu = (unsigned)__builtin_ctzll(t) >> 3;
+                    ce = (63u - (unsigned)__builtin_clzll(t)) >> 3;
+                    csel = NW == 1 ? 1u : (unsigned)__builtin_amdgcn_readlane(served_v, (int)cj);
+                } else ok = false;
+                const int over = (int)(64u * cj + 8u * cu + 8u) - left;   // tiles of the unit beyond the table (< 8: its first tile is inside)
+                const unsigned back = over > 0 ? (unsigned)over : 0u;
+                Unit d = {cj, cu, back, back, csel, cu == ce};
+                if (!ok) { d.sh = 8u; d.last = false; }
+                return d;
+            };
+            // A scalar base per unit and a 32-bit lane offset; the base goes through an empty asm, so that the compiler cannot see a unit past the end
+            // reload the previous one's bytes (it would make the load conditional behind a vmcnt(0): kde_screen_d8_kernel)
+            auto load = [&](const Unit& d, hf8 (&f)[4]) {
+                // the unit's first tile, from the super-batch's: NEGATIVE where a split of fewer than 8 tiles ends the table and the unit is moved
+                // back in front of it
+                int tile = (int)(64u * d.j + 8u * d.u) - (int)d.back;
+                asm volatile("" : "+s"(tile));
+                const PBN_GLOBAL char* p = sbp + (int64_t)tile * 512;   // (512 B of operands per tile)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) f[i] = *(const PBN_GLOBAL hf8*)(p + (uint64_t)loff + i * 1024);
+            };
+            unsigned long long word[NW];   // per lane: the bits of my column's group in the batch being screened
+#pragma unroll
+            for (int w = 0; w < NW; ++w) word[w] = 0;
+            auto row_or = [](unsigned x) -> unsigned {   // OR over my row of 16 lanes, in every lane of it
+                x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, true);    // quad_perm [1, 0, 3, 2]
+                x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, true);    // quad_perm [2, 3, 0, 1]
+                x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x124, 0xf, 0xf, true);   // row_ror:4
+                x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x128, 0xf, 0xf, true);   // row_ror:8
+                return x;
+            };
+            auto unit = [&](const Unit& d, const hf8 (&f)[4]) {
+#pragma unroll
+                for (int w = 0; w < NW; ++w) {
+                    if (NW > 1 && !((d.sel >> w) & 1u)) continue;   // (uniform)
+                    unsigned b = 0;
+                    const f16acc zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    // the next pair's MFMA is issued before this pair's maxima, which then run beside it (two accumulators in turn)
+                    f16acc acc[4];
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[0], bq[w], zero, 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        if (i + 1 < 4) acc[i + 1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[i + 1], bq[w], zero, 0, 0, 0);
+                        // rows 0..15 of the product (tile 2p) sit in registers 0..7, rows 16..31 (tile 2p + 1) in 8..15; the column - the query - is the lane
+                        auto mx = [](float x, float y) { return __builtin_elementwise_maximum(x, y); };
+                        const f16acc& c = acc[i];
+                        const float mA = mx(mx(mx(mx(c[0], c[1]), c[2]), mx(mx(c[3], c[4]), c[5])), mx(c[6], c[7]));
+                        const float mB = mx(mx(mx(mx(c[8], c[9]), c[10]), mx(mx(c[11], c[12]), c[13])), mx(c[14], c[15]));
+                        b |= (!(mA < thrf[w]) ? 1u << (2 * i) : 0u) | (!(mB < thrf[w]) ? 2u << (2 * i) : 0u);
+                    }
+                    word[w] |= (unsigned long long)(b >> d.sh) << (8u * d.u);
+                }
+                if (d.last) {   // (uniform) the batch is through: its words over each group's lanes, kept by lane = batch
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) {
+                        const unsigned lo = row_or((unsigned)word[w]), hi = row_or((unsigned)(word[w] >> 32));
+                        unsigned long long g[QG];
+#pragma unroll
+                        for (int q = 0; q < QG; ++q)
+                            g[q] = (unsigned long long)((unsigned)__builtin_amdgcn_readlane((int)lo, 16 * q) | (unsigned)__builtin_amdgcn_readlane((int)lo, 32 + 16 * q)) |
+                                   ((unsigned long long)((unsigned)__builtin_amdgcn_readlane((int)hi, 16 * q) | (unsigned)__builtin_amdgcn_readlane((int)hi, 32 + 16 * q)) << 32);
+                        if (lane == (int)d.j) { my_scr[w][0] = g[0]; my_scr[w][1] = g[1]; }
+                        word[w] = 0;
+                    }
+                }
+            };
+            Unit dq[2];
+            hf8 fq[2][4];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                dq[k] = next();
+                load(dq[k], fq[k]);
+            }
+            do {
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    unit(dq[k], fq[k]);
+                    dq[k] = next();
+                    load(dq[k], fq[k]);
+                }
+            } while (dq[0].sh != 8u);   // the next turn's first unit exists
+        }
+        if (bt < t1) {
+            const int64_t jb = (bt - t0) >> 6;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) {
+                if (((int64_t)qxs * NW + w) * QG >= a.nqtiles) break;
+                const unsigned long long bx0 = msk[(w * 64 + lane) * QG], bx1 = msk[(w * 64 + lane) * QG + 1];
+                const unsigned long long lv0 = my_scr[w][0] & bx0, lv1 = my_scr[w][1] & bx1;
+                LM[w * wave_words + jb * QG] = lv0;
+                LM[w * wave_words + jb * QG + 1] = lv1;
+                if (BM) { BM[w * wave_words + jb * QG] = bx0; BM[w * wave_words + jb * QG + 1] = bx1; }
+                if (count && (lv0 | lv1)) atomicAdd(&g_screen_kept, (unsigned long long)(__builtin_popcountll(lv0) + __builtin_popcountll(lv1)));
+            }
+        }
+        asm volatile("" ::: "memory");   // (the next super-batch parks its words where these were read)
+    }
+    // the batch slots past the table's end in a short last split hold nothing: written too (see the serial kernel)
+    for (int w = 0; w < NW; ++w) {
+        if (((int64_t)qxs * NW + w) * QG >= a.nqtiles) break;
+        for (int64_t jb = ((t1 - t0 + 63) >> 6) + lane; jb < a.batches_per_split; jb += 64) {
+            LM[w * wave_words + jb * QG] = 0;
+            LM[w * wave_words + jb * QG + 1] = 0;
+            if (BM) { BM[w * wave_words + jb * QG] = 0; BM[w * wave_words + jb * QG + 1] = 0; }
+        }
+    }
+}
+
 void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t ntiles, bool is_query, void* out, hipStream_t st) {
     const int64_t npad = ntiles * 16;
     if (npad == 0) return;
@@ -411,12 +661,28 @@ void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t
     HIP_CHECK(hipGetLastError());
 }
 
-void launch_screen_d8(const SweepArgs& a_in, int nsplit, bool stream, hipStream_t st) {
+// which: PBN_D8_SCREEN_STREAM - 0 the serial kernel, 1 the ring, anything else the dense kernel (the default).  The three write the same words.
+#ifndef PBN_SCREEN_NW
+#define PBN_SCREEN_NW 2   // sweep waves served by one wave of the dense kernel (2: each fragment load feeds two MFMAs; profiles/r13/c2_bench.txt)
+#endif
+void launch_screen_d8(const SweepArgs& a_in, int nsplit, int which, hipStream_t st) {
     SweepArgs a = a_in;
     a.nsplit_grid = nsplit;
     if (!a.scr_train || !a.scr_query || !a.live_mask || !a.batch_box || a.pdims != PBN_PRUNE_PD) throw invalid_error("KDE: the d = 8 screen needs its operands, masks and batch boxes");
-    const dim3 grid((unsigned)(ceil_div(a.nqtiles, PBN_QG_PRUNE) * nsplit)), block(64);
-    if (stream) hipLaunchKernelGGL(kde_screen_d8_kernel, grid, block, 0, st, a);
-    else hipLaunchKernelGGL(kde_screen_d8_serial_kernel, grid, block, 0, st, a);
+    const int64_t nwaves = ceil_div(a.nqtiles, PBN_QG_PRUNE);
+    const dim3 grid((unsigned)(nwaves * nsplit)), block(64);
+    if (which == 0) hipLaunchKernelGGL(kde_screen_d8_serial_kernel, grid, block, 0, st, a);
+    else if (which == 1 || a.ntiles < 8) hipLaunchKernelGGL(kde_screen_d8_kernel, grid, block, 0, st, a);   // (a unit of the dense kernel is 8 tiles of operands)
+    else {
+        // the shipped NW alone is instantiated; an EXPERIMENTS build has both and PBN_SCREEN_NW (the environment) picks
+        const int nw = PBN_TUNE(SCREEN_NW, PBN_SCREEN_NW) == 2 ? 2 : 1;
+        const dim3 dgrid((unsigned)(ceil_div(nwaves, (int64_t)nw) * nsplit));
+#ifdef PBN_EXPERIMENTS
+        if (nw == 2) hipLaunchKernelGGL(kde_screen_d8_dense_kernel<2>, dgrid, block, 0, st, a);
+        else hipLaunchKernelGGL(kde_screen_d8_dense_kernel<1>, dgrid, block, 0, st, a);
+#else
+        hipLaunchKernelGGL(kde_screen_d8_dense_kernel<PBN_SCREEN_NW>, dgrid, block, 0, st, a);
+#endif
+    }
     HIP_CHECK(hipGetLastError());
 }

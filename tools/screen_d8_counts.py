@@ -1,5 +1,7 @@
 """Counts of the d = 8 f16 screen on the GPU: blocks kept / tested (PBN_SWEEP_COUNT_REDO=1, pbn_debug_d8_screen) and, from the dumped box
-masks (pbn_debug_d8_masks), the MFMA iterations the screen issues: sum over (wave, batch) of ceil(popcount(box0 | box1) / 2).
+masks (pbn_debug_d8_masks), the MFMA iterations the screen issues: sum over (wave, batch) of ceil(popcount(box0 | box1) / 2) - and what the
+forms of a screen without a pair list would issue instead (round 13): MFMAs and operand bytes (1 KiB per fragment load) with one screen wave
+serving NW = 1 or 2 sweep waves.
     python tools/screen_d8_counts.py bench      bench.py's 1e6 x 1e5 table
     python tools/screen_d8_counts.py test       the 100 000 x 2 000 table of tests/test_prune_d8_screen_gpu.py::test_no_dropped_block_holds_a_live_pair"""
 import ctypes as C
@@ -96,3 +98,59 @@ print(f"  MFMA iterations {int(iters.sum())}: {blocks / max(int(iters.sum()), 1)
       f"mean {tiles[tiles > 0].mean():.2f}, odd {float((tiles[tiles > 0] & 1).mean()):.3f}")
 print(f"  iterations per (wave, split): mean {per_split.mean():.1f}, median {np.median(per_split):.0f}, max {per_split.max()}, "
       f"zero {float((per_split == 0).mean()):.3f}")
+
+
+# ---- round 13: a screen that walks consecutive tile pairs (2p, 2p + 1) of a batch in reach instead of a list of the pairs that pass
+def smear(u):
+    for sh in (1, 2, 4, 8, 16, 32):
+        u = u | (u >> np.uint64(sh))
+    return u
+
+
+def first_pair(u):   # of the lowest set bit (u != 0)
+    return popcount((u & (~u + np.uint64(1))) - np.uint64(1)) >> 1
+
+
+def last_pair(u):    # of the highest set bit (u != 0)
+    return (popcount(smear(u)) - 1) >> 1
+
+
+u1 = box[..., 0] | box[..., 1]                                   # (wave, split, batch): tiles in reach of a sweep wave
+# pairs a batch holds at all: the last batch of a split (of the table) is partial
+split_tiles = np.minimum(tps, np.maximum(ntiles - tps * np.arange(nsplit), 0))
+batch_tiles = np.clip(split_tiles[:, None] - 64 * np.arange(bps)[None, :], 0, 64)      # (split, batch)
+batch_pairs = (batch_tiles + 1) // 2
+
+
+def forms(u, served):
+    """u: (screen wave, split, batch) the tiles whose fragments the wave loads; served: how many of its sweep waves reach the batch.
+    Returns {form: (MFMAs, loads)}."""
+    on = u != 0
+    uz = np.where(on, u, np.uint64(1))
+    cur = (popcount(u) + 1) // 2
+    full = np.where(on, np.broadcast_to(batch_pairs, u.shape), 0)
+    rng = np.where(on, last_pair(uz) - first_pair(uz) + 1, 0)
+    unit = np.where(on, 4 * ((last_pair(uz) >> 2) - (first_pair(uz) >> 2) + 1), 0)   # units of four pairs: what kde_screen_d8_dense_kernel walks
+    # (a non-empty quarter of a partial batch holds no more pairs than the batch has left)
+    quarters = sum(np.where(((u >> np.uint64(16 * k)) & np.uint64(0xFFFF)) != 0, np.clip(np.broadcast_to(batch_pairs, u.shape) - 8 * k, 0, 8), 0)
+                   for k in range(4))
+    return {name: (int((loads * served).sum()), int(loads.sum()))
+            for name, loads in (("listed pairs (the ring)", cur), ("all pairs of the batch", full), ("first to last set pair", rng), ("first to last set unit", unit), ("non-empty quarters", quarters))}
+
+
+print("  forms of the screen: MFMAs and operand bytes a step (1 KiB per fragment load); NW = sweep waves served by one screen wave")
+on1 = (u1 != 0).astype(np.int64)
+res = {1: forms(u1, on1)}
+pad = u1 if nw % 2 == 0 else np.concatenate([u1, np.zeros((1,) + u1.shape[1:], dtype=u1.dtype)])
+pad = pad.reshape(-1, 2, nsplit, bps)
+res[2] = forms(pad[:, 0] | pad[:, 1], (pad != 0).sum(axis=1).astype(np.int64))
+for NW, r in res.items():
+    for name, (mf, ld) in r.items():
+        note = "  (at NW = 2 the pairs of either wave's list, each MFMA'd once per wave in reach: an upper bound of a joint list)" if NW == 2 and name.startswith("listed") else ""
+        print(f"    NW = {NW}  {name:26s} {mf:12d} MFMAs  {ld:12d} loads  {ld * 1024 / 1e9:8.2f} GB{note}")
+both = int(((pad != 0).sum(axis=1) == 2).sum())
+print(f"    NW = 2: batches in reach of both served waves {both}, of one only {int(((pad != 0).sum(axis=1) == 1).sum())}")
+uz = u1[u1 != 0]
+print(f"    batches in reach whose first set bit is odd {float((popcount((uz & (~uz + np.uint64(1))) - np.uint64(1)) & 1).mean()):.3f}, "
+      f"whose last set bit is even {float(((popcount(smear(uz)) - 1) & 1 == 0).mean()):.3f}; with an empty 16-tile quarter "
+      f"{float((sum(((uz >> np.uint64(16 * k)) & np.uint64(0xFFFF)) == 0 for k in range(4)) > 0).mean()):.3f}")
