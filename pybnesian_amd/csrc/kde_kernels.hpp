@@ -198,6 +198,10 @@ struct SweepArgs {
     const void* scr_query;
     unsigned long long* live_mask;   // [ceil(nqtiles / PBN_QG_PRUNE)][nsplit][batches_per_split][PBN_QG_PRUNE]
     unsigned long long* box_mask;    // test aid (pbn_debug_d8_masks), nullable: the box masks alone, same layout
+    // Round 14: per (sorted) query the bound its OWN pairs are screened against - the query's window bound where that lies above the tile's
+    // (query_window_kernel), else the tile's.  The budget argument is per query: a dropped term lies below 2^-margin of its own query's sum bound.
+    // The screen kernels alone read it; null (no window pass, PBN_D8_SCREEN_ROWTHR=0) = every column against qtile_thr of its group.
+    const double* qrow_thr;          // [nqtiles * 16]
 };
 
 // Position along the Hilbert curve of a cell in n = 2 ... 4 dimensions, `bits` bits per axis (Skilling's transpose form: undo the excess rotations
@@ -292,9 +296,11 @@ void launch_query_prepass(const double* zq_row, const int32_t* qperm, int64_t nq
                           const double* subpart = nullptr, int P = 2, int which = 0, double log2_nsub = 0.0, const double* tile_box = nullptr,
                           int64_t* qtpos = nullptr);
 // sum-only pruned sweeps of the rotated (d = 7, 8) models, KS = 2: per query tile the exact terms over the `window` training tiles on either
-// side of qtpos[tile] (query_prepass_kernel) raise qthr (lower bound of log2 of the tile's sums) and qlb (of each query's largest exponent)
+// side of qtpos[tile] (query_prepass_kernel) raise qthr (lower bound of log2 of the tile's sums) and qlb (of each query's largest exponent);
+// qrow_thr (nullable, [nqtiles * 16]) takes every query's own sum bound where it lies above its tile's final one, else the tile's
 void launch_query_window(const double* Apack, const double* nxpack, const double* Bpack, const double* nypack, int64_t ntiles, int64_t n_train,
-                         int64_t nqtiles, int64_t nq, const int64_t* qtpos, int window, bool fold, double* qthr, double* qlb, double* dbg, hipStream_t st);
+                         int64_t nqtiles, int64_t nq, const int64_t* qtpos, int window, bool fold, double* qthr, double* qlb, double* qrow_thr,
+                         double* dbg, hipStream_t st);
 void sort_keys(pbn::dev_buf<char>& tmp, const uint32_t* keys_in, uint32_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int64_t n,
                int bits, hipStream_t st);
 // 52 (fp64) / 40 (fp32 on the f16 cores) at 10^6 training rows, + log2(n_train / 10^6): a constant bound (2.2e-10 / 9.1e-7 of a sum) on what

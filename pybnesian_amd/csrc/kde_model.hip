@@ -470,12 +470,17 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store) {
 }
 
 // pbn_debug_d8_masks (test aid, not part of the C ABI header): armed, the next screened d = 8 sweep also writes its box masks, and both mask
-// arrays are copied to the host behind it, with the launch's shape and the tables the masks were taken from
+// arrays are copied to the host behind it, with the launch's shape and the tables the masks were taken from.
+// Thresholds: qrow is what every column was compared against, its query's bound less the margin (the group's, sixteen times over, where the
+// launch had no per-query bounds: PBN_D8_SCREEN_ROWTHR=0, no window pass).  qthr, one number per query tile, is the LARGEST of the tile's
+// sixteen: a block all of whose columns lie below their own thresholds holds no pair at or above it - the only per-tile number of which
+// that is true - and where the launch compared against the group's bound it is that bound, as before.
 static std::atomic<bool> g_masks_capture{false};
 static std::mutex g_masks_mu;
 struct MaskDump {
     std::vector<unsigned long long> box, live;
-    std::vector<double> qthr, zq, zt;  // per query tile: sum bound less the margin; the sorted queries' / training rows' whitened rows [n][8]
+    std::vector<double> qthr, zq, zt;  // per query tile: see above; the sorted queries' / training rows' whitened rows [n][8]
+    std::vector<double> qrow;          // per sorted query, padding columns included [nqtiles * 16]
     long long dims[6] = {0, 0, 0, 0, 0, 0};   // sweep waves, splits, batches per split, tiles per split, training tiles, queries
 };
 static MaskDump g_masks;
@@ -566,12 +571,14 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     const bool wdbg = window > 0 && g_window_capture.load();
     int64_t* qtpos = nullptr;
     double* qdbg = nullptr;
+    double* qrow = nullptr;   // per query: its own sum bound where above its tile's (query_window_kernel), for the d = 8 screen's columns
     if (prune) {
         auto al = [](size_t x) { return (x + 255) / 256 * 256; };
         const size_t qbox_b = al((size_t)nqtiles * 2 * m.pdims * sizeof(double)), qthr_b = al((size_t)nqtiles * sizeof(double));
         const size_t qlb_b = al((size_t)nqtiles * 16 * sizeof(double));
         const size_t qtpos_b = window ? al((size_t)nqtiles * sizeof(int64_t)) : 0, qdbg_b = wdbg ? al((size_t)nqtiles * 16 * sizeof(double)) : 0;
-        qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.kdims, qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b);
+        const size_t qrow_b = window ? qlb_b : 0;
+        qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.kdims, qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b + qrow_b);
         pa.perm = qs.perm;
         qperm = qs.perm;
         qbox = (double*)qs.rest; qthr = (double*)(qs.rest + qbox_b);
@@ -579,6 +586,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         if (use_qlb) qlb = (double*)(qs.rest + qbox_b + qthr_b);
         if (window) qtpos = (int64_t*)(qs.rest + qbox_b + qthr_b + qlb_b);
         if (wdbg) qdbg = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b);
+        if (window) qrow = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b);
     }
     pa.pack = q; pa.npack = q + bpack_b; pa.xpack = m.cond ? q + bpack_b + ny_b : nullptr;
     pa.xnorm = xn_b ? q + bpack_b + ny_b + bx_b : nullptr;
@@ -605,7 +613,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
                              ctx->stream, subpart, P, m.cond ? 2 : 0, subpart ? std::log2((double)m.nsub) : 0.0, m.cond ? nullptr : m.tile_box, qtpos);
         if (window) {
             { KernelTimer kt(ctx, PBN_K_PACK); launch_query_window((const double*)m.Apack, (const double*)m.nxpack, (const double*)pa.pack, (const double*)pa.npack,
-                                                               m.ntiles, m.N, nqtiles, n, qtpos, window, fold, (double*)qthr, (double*)qlb, qdbg, ctx->stream); }
+                                                               m.ntiles, m.N, nqtiles, n, qtpos, window, fold, (double*)qthr, (double*)qlb, qrow, qdbg, ctx->stream); }
             if (wdbg) {   // pbn_debug_sum_window: the queries' bounds, in the table's row order
                 std::vector<double> lb((size_t)n);
                 std::vector<int32_t> perm((size_t)n);
@@ -683,6 +691,8 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         sa.scr_train = m.scr; sa.scr_query = sp;
         sa.live_mask = (unsigned long long*)(sp + scrq_b);
         sa.box_mask = mdbg ? (unsigned long long*)(sp + scrq_b + mask_b) : nullptr;
+        // every column against its own query's bound (round 14); 0: against its group's, the masks of round 13 bit for bit (read per evaluation)
+        sa.qrow_thr = knob_int("PBN_D8_SCREEN_ROWTHR", 1) != 0 ? qrow : nullptr;
         KernelTimer kt(ctx, PBN_K_PACK);
         launch_screen_pack(qs.zrow, qs.perm, n, nqtiles, true, sp, ctx->stream);
         launch_screen_d8(sa, (int)nsplit, knob_int("PBN_D8_SCREEN_STREAM", 2), ctx->stream);   // (0: the serial kernel, 1: the ring, else the dense kernel: the same masks; read per evaluation)
@@ -698,12 +708,28 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         HIP_CHECK(hipMemcpyAsync(g_masks.box.data(), sa.box_mask, mask_b, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(g_masks.live.data(), sa.live_mask, mask_b, hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(g_masks.qthr.data(), qthr, (size_t)nqtiles * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        g_masks.qrow.resize((size_t)nqtiles * 16);
+        if (sa.qrow_thr) HIP_CHECK(hipMemcpyAsync(g_masks.qrow.data(), sa.qrow_thr, (size_t)nqtiles * 16 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(zrow.data(), qs.zrow, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipMemcpyAsync(perm.data(), qs.perm, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         for (int64_t i = 0; i < n; ++i)
             for (int k = 0; k < 8; ++k) g_masks.zq[(size_t)i * 8 + k] = zrow[(size_t)perm[(size_t)i] * 8 + k];
         for (auto& v : g_masks.qthr) v -= sa.prune_margin;
+        if (sa.qrow_thr) {
+            for (int64_t t = 0; t < nqtiles; ++t) {
+                double top = g_masks.qrow[(size_t)t * 16] - sa.prune_margin;
+                for (int c = 0; c < 16; ++c) {
+                    double& v = g_masks.qrow[(size_t)t * 16 + c];
+                    v -= sa.prune_margin;
+                    if (v > top) top = v;   // (a NaN tile is NaN in all sixteen: top stays the first)
+                }
+                g_masks.qthr[(size_t)t] = top;
+            }
+        } else {
+            for (int64_t t = 0; t < nqtiles; ++t)
+                for (int c = 0; c < 16; ++c) g_masks.qrow[(size_t)t * 16 + c] = g_masks.qthr[(size_t)t];
+        }
         const long long dims[6] = {(long long)ceil_div(nqtiles, PBN_QG_PRUNE), (long long)nsplit, (long long)ceil_div(tps, 64), (long long)tps, (long long)m.ntiles, (long long)n};
         for (int i = 0; i < 6; ++i) g_masks.dims[i] = dims[i];
     }
@@ -722,8 +748,9 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
 
 }  // namespace pbn
 
-// capture != 0 arms the aid; what = 0 the shape (six values into dims), 1 / 2 the box / live masks, 3 the groups' thresholds, 4 / 5 the sorted
-// queries' / training rows' whitened rows: copies up to cap items into out and returns how many the last screened sweep left
+// capture != 0 arms the aid; what = 0 the shape (six values into dims), 1 / 2 the box / live masks, 3 per query tile the largest threshold of its
+// columns (the group's where the launch screened against that: MaskDump), 4 / 5 the sorted queries' / training rows' whitened rows, 6 the
+// columns' thresholds [query tiles * 16]: copies up to cap items into out and returns how many the last screened sweep left
 extern "C" int64_t pbn_debug_d8_masks(int what, void* out, int64_t cap, int capture) {
     pbn::g_masks_capture.store(capture != 0);
     std::lock_guard<std::mutex> lk(pbn::g_masks_mu);
@@ -739,6 +766,7 @@ extern "C" int64_t pbn_debug_d8_masks(int what, void* out, int64_t cap, int capt
         case 3: return copy(d.qthr.data(), d.qthr.size(), 8);
         case 4: return copy(d.zq.data(), d.zq.size(), 8);
         case 5: return copy(d.zt.data(), d.zt.size(), 8);
+        case 6: return copy(d.qrow.data(), d.qrow.size(), 8);
         default: return -1;
     }
 }

@@ -361,13 +361,16 @@ __global__ __launch_bounds__(256) void query_prepass_kernel(const double* __rest
 // left out, and queries that are NaN or beyond nq do not enter the tile's minimum.
 // Per query tile the smallest lb of its valid queries raises qthr where it is larger; per query the largest window exponent raises qlb
 // where it is larger (an exponent of a real term: a lower bound of the query's largest).  The window's terms are NOT added to any sum.
+// qrow_thr (nullable; round 14, the d = 8 screen's per-column thresholds): with T = the tile's bound as this kernel leaves it, a valid query
+// whose own lb lies above T gets lb - a lower bound of ITS whole sum, which is all the budget argument asks of it - and every other column
+// of the tile (padding, NaN queries, lb <= T) gets T.  A NaN T stays a NaN in all sixteen.
 // dbg (nullable, pbn_debug_sum_window): lb per query in the sorted order, -inf where there is none.
 #define PBN_WINDOW_SLACK 0x1p-8
 template <bool FOLD>
 __global__ __launch_bounds__(256) void query_window_kernel(const double* __restrict__ Ap, const double* __restrict__ Np, const double* __restrict__ Bp,
                                                            const double* __restrict__ NYp, int64_t ntiles, int64_t n_train, int64_t nqtiles, int64_t nq,
                                                            const int64_t* __restrict__ qtpos, int window, double* __restrict__ qthr,
-                                                           double* __restrict__ qlb, double* __restrict__ dbg) {
+                                                           double* __restrict__ qlb, double* __restrict__ qrow_thr, double* __restrict__ dbg) {
     constexpr int KS = 2;
     using V = Tr<double>::vec4;
     const int lane = threadIdx.x & 63, lg = lane >> 4, col = lane & 15;
@@ -434,7 +437,13 @@ __global__ __launch_bounds__(256) void query_window_kernel(const double* __restr
     if (qlb && lg == 0 && valid && top > qlb[q]) qlb[q] = top;
     double g = valid ? lb : INFINITY;
     for (int off = 1; off < 16; off <<= 1) { const double o = __shfl_xor(g, off); g = o < g ? o : g; }
-    if (lane == 0 && g < INFINITY && g > qthr[qt]) qthr[qt] = g;
+    const double told = qthr[qt];   // (every lane reads it before lane 0's store below: one wave, program order)
+    const bool raise = g < INFINITY && g > told;
+    if (qrow_thr && lg == 0) {
+        const double T = raise ? g : told;
+        qrow_thr[qt * 16 + col] = (valid && lb > T) ? lb : T;
+    }
+    if (lane == 0 && raise) qthr[qt] = g;
 }
 
 void launch_pack_classic(const PackArgs& a, int dtype, hipStream_t st) {
@@ -636,11 +645,12 @@ void launch_query_prepass(const double* zq_row, const int32_t* qperm, int64_t nq
 }
 
 void launch_query_window(const double* Apack, const double* nxpack, const double* Bpack, const double* nypack, int64_t ntiles, int64_t n_train,
-                         int64_t nqtiles, int64_t nq, const int64_t* qtpos, int window, bool fold, double* qthr, double* qlb, double* dbg, hipStream_t st) {
+                         int64_t nqtiles, int64_t nq, const int64_t* qtpos, int window, bool fold, double* qthr, double* qlb, double* qrow_thr, double* dbg,
+                         hipStream_t st) {
     if (nqtiles == 0 || window <= 0) return;
     const dim3 grid((unsigned)ceil_div(nqtiles, 4));
-    if (fold) hipLaunchKernelGGL(query_window_kernel<true>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, nq, qtpos, window, qthr, qlb, dbg);
-    else hipLaunchKernelGGL(query_window_kernel<false>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, nq, qtpos, window, qthr, qlb, dbg);
+    if (fold) hipLaunchKernelGGL(query_window_kernel<true>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, nq, qtpos, window, qthr, qlb, qrow_thr, dbg);
+    else hipLaunchKernelGGL(query_window_kernel<false>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, nq, qtpos, window, qthr, qlb, qrow_thr, dbg);
     HIP_CHECK(hipGetLastError());
 }
 

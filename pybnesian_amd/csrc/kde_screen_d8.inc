@@ -13,6 +13,9 @@
 // nt = -1/2|z_t|^2 as hi = f16(nt), lo = f16(nt - hi); et, eq = the row's share of the error bound, rounded UP to f16.  The accumulator is
 //   s~ + E,   s~ ~ s = z_t.z_q - 1/2|z_t|^2 - 1/2|z_q|^2 (the pair's exponent, base-2 units),   E = et + eq >= |s~ - s|:
 // a pair is dead when that is < thr = the group's sum bound less the margin - what the box test compares -1/2 dist^2 of the boxes against.
+// Round 14: with SweepArgs::qrow_thr a column is compared against ITS query's sum bound less the margin instead - at or above the group's, which
+// is the smallest of the sixteen - and a block is dropped when every column lies below its own.  The budget argument is per query (a dropped
+// term is below 2^-margin of its own query's sum); the box tests of phase 1 keep the group's number.
 //
 // The bound.  u = 2^-11 + 2^-24 (f16, round to nearest, a conversion by way of fp32 included), h = 2^-14 (the pack writes 0 for |x| < 2^-14:
 // no f16 subnormal reaches the matrix core, whatever it does with them), v = 2^-23 (one fp32 rounding, truncation included), R = |z|_2,
@@ -127,8 +130,10 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_ker
     const int r = lane & 31, h = lane >> 5, gl = r >> 4;   // my column's group
     const int64_t qtl = qt0 + gl < a.nqtiles ? qt0 + gl : a.nqtiles - 1;
     const hf8 bq = SQ[(qtl * 16 + (r & 15)) * 2 + h];
-    // the group's threshold as a float not above it (a NaN stays a NaN: nothing compares below it)
-    const double thrd = qbs[QG * 2 * PD + gl];
+    // my column's threshold - its own query's bound less the margin (SweepArgs::qrow_thr), the group's without one - as a float not above it
+    // (a NaN stays a NaN: nothing compares below it)
+    const PBN_GLOBAL double* __restrict__ QRp = (const PBN_GLOBAL double*)a.qrow_thr;
+    const double thrd = QRp ? QRp[qtl * 16 + (r & 15)] - a.prune_margin : qbs[QG * 2 * PD + gl];
     float thrf = (float)thrd;
     if ((double)thrf > thrd) thrf = __builtin_fmaf(-__builtin_fabsf(thrf), 0x1p-23f, thrf) - 0x1p-126f;   // at least one ulp down
     const unsigned long long G0 = 0x0000ffff0000ffffull;   // the lanes that hold group 0's columns
@@ -317,8 +322,10 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
             const int r = ln & 31, h = ln >> 5, gl = r >> 4;   // my column's group
             const int64_t qtl = qt0 + gl < a.nqtiles ? qt0 + gl : a.nqtiles - 1;
             const hf8 bq = SQ[(qtl * 16 + (r & 15)) * 2 + h];
-            // the group's threshold as a float not above it (a NaN stays a NaN: nothing compares below it)
-            const double thrd = qbs[QG * 2 * PD + gl];
+            // my column's threshold - its own query's bound less the margin (SweepArgs::qrow_thr), the group's without one - as a float not above
+            // it (a NaN stays a NaN: nothing compares below it)
+            const PBN_GLOBAL double* __restrict__ QRp = (const PBN_GLOBAL double*)a.qrow_thr;
+            const double thrd = QRp ? QRp[qtl * 16 + (r & 15)] - a.prune_margin : qbs[QG * 2 * PD + gl];
             float thrf = (float)thrd;
             if ((double)thrf > thrd) thrf = __builtin_fmaf(-__builtin_fabsf(thrf), 0x1p-23f, thrf) - 0x1p-126f;   // at least one ulp down
             // my 16 bytes of a training row's operands: rows 0..15 of the product come from the pair's first tile, 16..31 from its second
@@ -520,8 +527,10 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
                 const int64_t qt0 = ((int64_t)qxs * NW + w) * QG;
                 const int64_t qtl = qt0 + gl < a.nqtiles ? qt0 + gl : a.nqtiles - 1;
                 bq[w] = SQ[(qtl * 16 + (r & 15)) * 2 + h];
-                // the group's threshold as a float not above it (a NaN stays a NaN: nothing compares below it)
-                const double thrd = qbs[w * QW + QG * 2 * PD + gl];
+                // my column's threshold - its own query's bound less the margin (SweepArgs::qrow_thr), the group's without one - as a float not
+                // above it (a NaN stays a NaN: nothing compares below it)
+                const PBN_GLOBAL double* __restrict__ QRp = (const PBN_GLOBAL double*)a.qrow_thr;
+                const double thrd = QRp ? QRp[qtl * 16 + (r & 15)] - a.prune_margin : qbs[w * QW + QG * 2 * PD + gl];
                 float tf = (float)thrd;
                 if ((double)tf > thrd) tf = __builtin_fmaf(-__builtin_fabsf(tf), 0x1p-23f, tf) - 0x1p-126f;   // at least one ulp down
                 thrf[w] = tf;

@@ -1,4 +1,5 @@
-"""Counts of the d = 8 f16 screen on the GPU: blocks kept / tested (PBN_SWEEP_COUNT_REDO=1, pbn_debug_d8_screen) and, from the dumped box
+"""Counts of the d = 8 f16 screen on the GPU: blocks kept / tested (PBN_SWEEP_COUNT_REDO=1, pbn_debug_d8_screen), of the launch as shipped and of
+the same launch with the columns screened against their group's threshold (PBN_D8_SCREEN_ROWTHR=0), and, from the dumped box
 masks (pbn_debug_d8_masks), the MFMA iterations the screen issues: sum over (wave, batch) of ceil(popcount(box0 | box1) / 2) - and what the
 forms of a screen without a pair list would issue instead (round 13): MFMAs and operand bytes (1 KiB per fragment load) with one screen wave
 serving NW = 1 or 2 sweep waves.
@@ -55,16 +56,34 @@ else:
     def run():
         return kde.slogl(test)
 
-os.environ["PBN_SWEEP_COUNT_REDO"] = "1"
-lib.pbn_debug_d8_screen(None, None, 1)
-lib.pbn_debug_sweep_visits(None, None, 1)
-s = run()
-kept, tested, v, t = (C.c_ulonglong(0) for _ in range(4))
-lib.pbn_debug_d8_screen(C.byref(kept), C.byref(tested), 1)
-lib.pbn_debug_sweep_visits(C.byref(v), C.byref(t), 1)
-os.environ["PBN_SWEEP_COUNT_REDO"] = "0"
-print(f"{which}: slogl {s!r}; box-visited {v.value} of {t.value} offered ({v.value / max(t.value, 1):.4f}); "
-      f"screen kept {kept.value} of {tested.value} tested ({kept.value / max(tested.value, 1):.4f})")
+def counted():
+    """slogl and the counters of one step: blocks kept / tested by the screen, box-visited / offered."""
+    os.environ["PBN_SWEEP_COUNT_REDO"] = "1"
+    lib.pbn_debug_d8_screen(None, None, 1)
+    lib.pbn_debug_sweep_visits(None, None, 1)
+    s = run()
+    kept, tested, v, t = (C.c_ulonglong(0) for _ in range(4))
+    lib.pbn_debug_d8_screen(C.byref(kept), C.byref(tested), 1)
+    lib.pbn_debug_sweep_visits(C.byref(v), C.byref(t), 1)
+    os.environ["PBN_SWEEP_COUNT_REDO"] = "0"
+    return s, kept.value, tested.value, v.value, t.value
+
+
+s, kept, tested, v, t = counted()
+print(f"{which}: slogl {s!r}; box-visited {v} of {t} offered ({v / max(t, 1):.4f}); "
+      f"screen kept {kept} of {tested} tested ({kept / max(tested, 1):.4f})")
+# round 14: the same launch with every column against its GROUP's threshold (PBN_D8_SCREEN_ROWTHR=0, read per evaluation)
+before = os.environ.get("PBN_D8_SCREEN_ROWTHR")
+os.environ["PBN_D8_SCREEN_ROWTHR"] = "0"
+try:
+    s0, kept0, tested0, _, _ = counted()
+finally:
+    if before is None:
+        del os.environ["PBN_D8_SCREEN_ROWTHR"]
+    else:
+        os.environ["PBN_D8_SCREEN_ROWTHR"] = before
+print(f"  PBN_D8_SCREEN_ROWTHR=0: slogl {s0!r}; screen kept {kept0} of {tested0} tested ({kept0 / max(tested0, 1):.4f}); "
+      f"kept per-query / kept group {kept / max(kept0, 1):.4f}; slogl relative difference {abs(s - s0) / abs(s0):.3e}")
 
 
 def fetch(what, dtype):
