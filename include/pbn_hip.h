@@ -339,6 +339,29 @@ int pbn_dnet_slogl(pbn_dnet* dn, pbn_dtable* dt, double* out_total, double* out_
 /* cumulative pbn_dnet_logl launches and the rows they evaluated */
 int pbn_dnet_stats(const pbn_dnet* dn, int64_t* logl_launches, int64_t* rows_evaluated);
 
+/* ---- Gaussian networks: evaluation in one device pass -------------------------------------------------------------
+ * pbn_gnet replaces the loop over the factors of BNGeneric::logl / slogl (models/BayesianNetwork.hpp:997-1022) when
+ * every node is a LinearGaussianCPD (factors/continuous/LinearGaussianCPD.cpp:92-149 logl / slogl): node i is column
+ * var[i] given columns parents[par_off[i] .. par_off[i + 1]) (par_off has n_nodes + 1 entries, par_off[0] = 0); its
+ * p_i + 1 coefficients (intercept first, then the parents' in their order) start at beta[par_off[i] + i]; variance[i].
+ * Columns index a table of at least n_cols columns.  PBN_ERR_INVALID for a null argument, n_nodes < 1, a column
+ * outside [0, n_cols) or a family of more than 64 columns (the cap of pbn_lg_logl). */
+typedef struct pbn_gnet pbn_gnet;
+int pbn_gnet_create(pbn_ctx* ctx, int n_cols, int n_nodes, const int* var, const int* par_off, const int* parents,
+                    const double* beta, const double* variance, pbn_gnet** out);
+void pbn_gnet_destroy(pbn_gnet* g);
+/* BNGeneric::logl (models/BayesianNetwork.hpp:997-1008) over LinearGaussianCPD::logl (LinearGaussianCPD.cpp:92-120):
+ * out[r] (rows(t) HOST doubles) = the nodes' log-densities of row r added one at a time in node order, starting from
+ * the first node's - each the very value pbn_lg_logl gives.  One kernel launch for all nodes and rows, either dtype.
+ * PBN_ERR_INVALID for a table of fewer than n_cols columns or one on another context. */
+int pbn_gnet_logl(const pbn_gnet* g, const pbn_table* t, double* out);
+/* BNGeneric::slogl (models/BayesianNetwork.hpp:1010-1022) over LinearGaussianCPD::slogl (LinearGaussianCPD.cpp:122-149):
+ * node_slogl[i] (n_nodes HOST doubles) = pbn_lg_logl's out_slogl of node i over all rows of t, bit for bit (the same
+ * 256-row block trees, added in block order); all 0.0 for a table without rows.  One kernel launch. */
+int pbn_gnet_slogl(const pbn_gnet* g, const pbn_table* t, double* node_slogl);
+/* evaluation-kernel launches and the rows they covered since creation */
+int pbn_gnet_stats(const pbn_gnet* g, int64_t* launches, int64_t* rows);
+
 /* ---- one process per GPU: the delta-score cache sharded BEHIND the boundary (shards the serial double
  * loops of learning/operators/operators.cpp:100-132,296-347 and the fold loop of learning/scores/cv_likelihood.cpp:5-25; the
  * reference is one process and has no counterpart).  The host supplies ONE collective - an all-gather of doubles - as a function

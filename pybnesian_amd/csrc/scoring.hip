@@ -749,8 +749,7 @@ static int lg_eval(const pbn_table* t, const int* cols, int d, int64_t row0, int
         LgArgs a{};
         a.base = t->data; a.ld = t->ld; a.p = d - 1; a.row0 = row0; a.n = n;
         for (int i = 0; i < d; ++i) { a.gc.cols[i] = cols[i]; a.beta[i] = beta[i]; }
-        a.inv_std = 1.0 / std::sqrt(variance);
-        a.cte = -0.5 * std::log(variance) - 0.5 * LOG_2PI;
+        lg_constants(variance, &a.inv_std, &a.cte);
         a.logl = dlogl.p; a.block_sums = bs; a.want_cdf = want_cdf;
         launch_lg_logl(a, t->dtype, ctx->stream);
         if (out_logl) HIP_CHECK(hipMemcpyAsync(out_logl, dlogl.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

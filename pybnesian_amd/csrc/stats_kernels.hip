@@ -1301,12 +1301,11 @@ __global__ __launch_bounds__(256) void lg_logl_kernel(LgArgs a) {
     if (r < a.n) {
         const T* base = (const T*)a.base;
         const int64_t src = a.rows ? (int64_t)a.rows[a.row0 + r] : a.row0 + r;
-        double mean = a.beta[0];
-        for (int j = 1; j <= a.p; ++j) mean += a.beta[j] * (double)base[(int64_t)a.gc.cols[j] * a.ld + src];
-        const double y = (double)base[(int64_t)a.gc.cols[0] * a.ld + src];
-        const double z = a.inv_std * (y - mean);
-        val = -0.5 * z * z + a.cte;
-        if (a.logl) a.logl[r] = a.want_cdf ? 0.5 * erfc(-z * 0.70710678118654752440) : val;
+        const int64_t rows[1] = {src};
+        double z[1];
+        lg_rows_z<T, 1>(base, a.ld, a.gc.cols[0], a.gc.cols + 1, a.p, a.beta, rows, a.inv_std, z);
+        val = lg_value(z[0], a.cte);
+        if (a.logl) a.logl[r] = a.want_cdf ? 0.5 * erfc(-z[0] * 0.70710678118654752440) : val;
     }
     __shared__ double red[256];
     red[threadIdx.x] = val;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 
 namespace pbn {
@@ -46,6 +47,40 @@ struct LgArgs {
     double* block_sums;  // device, nullable: ceil(n/256) partial sums
 };
 void launch_lg_logl(const LgArgs& a, int dtype, hipStream_t st);
+
+// The two host constants of a LinearGaussianCPD evaluation (LgArgs::inv_std / ::cte), for every path that fills them.
+inline void lg_constants(double variance, double* inv_std, double* cte) {
+    *inv_std = 1.0 / std::sqrt(variance);
+    *cte = -0.5 * std::log(variance) - 0.5 * 1.8378770664093454835606594728112;   // log(2 pi)
+}
+
+#ifdef __HIPCC__
+// z = (y - mean) / sigma of V rows of a column-major table under one LinearGaussianCPD: `var` the variable's column, ev[0 .. p) the
+// evidence columns in the order of beta[1 .. p], src[i] the rows (all of them readable).  lg_logl_kernel (V = 1) and gnet_logl_kernel
+// (V = 4, gaussian_model.hip) both get their values from this text and lg_value below, so the compiler contracts the same products
+// into the same fmas in both: the network-level pass must give the per-factor bits.
+template <typename T, int V>
+__device__ __forceinline__ void lg_rows_z(const T* __restrict__ base, int64_t ld, int var, const int* __restrict__ ev, int p,
+                                          const double* __restrict__ beta, const int64_t (&src)[V], double inv_std, double (&z)[V]) {
+    double mean[V];
+    const double b0 = beta[0];
+#pragma unroll
+    for (int i = 0; i < V; ++i) mean[i] = b0;
+    for (int j = 1; j <= p; ++j) {
+        const double b = beta[j];
+        const T* col = base + (int64_t)ev[j - 1] * ld;
+#pragma unroll
+        for (int i = 0; i < V; ++i) mean[i] += b * (double)col[src[i]];
+    }
+    const T* ycol = base + (int64_t)var * ld;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const double y = (double)ycol[src[i]];
+        z[i] = inv_std * (y - mean[i]);
+    }
+}
+__device__ __forceinline__ double lg_value(double z, double cte) { return -0.5 * z * z + cte; }
+#endif
 
 int gram_ws(int nct);  // doubles per partial: nct(nct+1)/2 tiles of 256 + nct*16 column sums
 void launch_pilot(const void* base, int64_t ld, const GramCols& gc, int n_cols, int64_t row0, const int32_t* rows,

@@ -928,10 +928,15 @@ class BayesianNetwork(BayesianNetworkBase):
         from .dataset import as_record_batch, default_context, shared_upload
 
         from . import discrete_model as dm
+        from . import gaussian_model as gm
 
         df = as_record_batch(df)
         if dm.enabled() and dm.all_discrete_factors(self):   # one launch for all nodes; the same adds in the same order
             out = dm.network_logl(self, df)
+            if out is not None:
+                return out
+        if gm.enabled() and gm.all_lg_factors(self):   # likewise for LinearGaussianCPDs (gaussian_model.py)
+            out = gm.network_logl(self, df)
             if out is not None:
                 return out
         out = None
@@ -945,6 +950,7 @@ class BayesianNetwork(BayesianNetworkBase):
         if not self.fitted():
             raise ValueError("Model not fitted.")
         from . import discrete_model as dm
+        from . import gaussian_model as gm
         from .dataset import as_record_batch, default_context, shared_upload
 
         df = as_record_batch(df)
@@ -952,6 +958,10 @@ class BayesianNetwork(BayesianNetworkBase):
             total = dm.network_slogl(self, df)
             if total is not None:
                 return float(total)
+        if gm.enabled() and gm.all_lg_factors(self):
+            per_node = gm.network_node_slogl(self, df)
+            if per_node is not None:
+                return float(sum(float(v) for v in per_node))   # the loop's sum(...): from 0, in node order
         with shared_upload(default_context(), df, self._upload_columns()):
             return float(sum(self._cpds[n].slogl(df) for n in self._nodes))
 
