@@ -390,7 +390,11 @@ static void kde_fit_impl(pbn_ctx* ctx, const pbn_table* train, const int* cols, 
         const double sc = std::sqrt(2.0 * 1.4426950408889634073599246810019);
         k->wu.assign((size_t)m.d, 0.0);
         for (int j = 0; j < m.d; ++j) k->wu[j] = m.W[(size_t)(m.d - 1) * m.d + j] / sc;
-        if (m.d <= PBN_W_INLINE_D) {   // cdf / sample fragments: up to 16 evidence variables (logl / slogl go to 32 in fp64)
+        // an fp32 model that logl gave up on (kde_widen above: 2^-24 max|z|^2 past the fp32 tolerance) gives up here too: the weights are
+        // the same Gram form nx + ny + x.y and u = (x - b.e) / sigma_c is one more whitened coordinate, so its cdf / sample fragments are
+        // built in fp64 from the float columns through the generic pack, like those of more than 16 evidence variables
+        const bool widen_cdf = m.widen && m.d > 1;
+        if (m.d <= PBN_W_INLINE_D && !widen_cdf) {   // cdf / sample fragments: up to 16 evidence variables (logl / slogl go to 32 in fp64)
             k->cdf_KS = std::max(1, (m.d - 1 + 3) / 4);
             const size_t es = dtype_size(m.dtype);
             k->cA.alloc((size_t)m.ntiles * k->cdf_KS * 64 * es);
@@ -403,8 +407,9 @@ static void kde_fit_impl(pbn_ctx* ctx, const pbn_table* train, const int* cols, 
             KernelTimer kt(ctx, PBN_K_PACK);
             launch_pack_classic(pa, m.dtype, ctx->stream);
         } else {
-            // more than 16 evidence variables (the reference's cdf / sample loop over any number: CKDE.hpp:289-735): fp64 fragments in
-            // the classic order through the generic pack, runtime-sized kernels (kde_cdf_kernel<double, 0, ...>)
+            // more than 16 evidence variables (the reference's cdf / sample loop over any number: CKDE.hpp:289-735) or a widened fp32
+            // model: fp64 fragments in the classic order through the generic pack; runtime-sized kernels (kde_cdf_kernel<double, 0, ...>)
+            // beyond 16 variables, the templated double ones up to there
             k->cdf_wide = true;
             k->cdf_KS = (m.d - 1 + 3) / 4;
             k->cA.alloc((size_t)m.ntiles * k->cdf_KS * 64 * sizeof(double));

@@ -143,6 +143,16 @@ __global__ __launch_bounds__(256, 2) void kde_cdf_kernel(CdfArgs a) {
                 w0 = Tr<T>::ex2_hi(acc[0]); w1 = Tr<T>::ex2_hi(acc[1]); w2 = Tr<T>::ex2_hi(acc[2]); w3 = Tr<T>::ex2_hi(acc[3]);
                 ts = (w0 + w1) + (w2 + w3);
             }
+            if constexpr (MODE == 2 && sizeof(T) == 4) {
+                // UCV takes the N self pairs off the totals as N: a row against itself must weigh exactly 1.  The fp32 Gram form leaves
+                // 1 + O(2^-24 |z|^2) there, which the K_H term multiplies by 2^(d/2 + 1) against the K_2H(0) the score starts from.
+                if (t == qtg[g]) {
+                    const int col = lane & 15;
+                    w0 = Tr<T>::crow(lg, 0) == col ? (T)1 : w0; w1 = Tr<T>::crow(lg, 1) == col ? (T)1 : w1;
+                    w2 = Tr<T>::crow(lg, 2) == col ? (T)1 : w2; w3 = Tr<T>::crow(lg, 3) == col ? (T)1 : w3;
+                    ts = (w0 + w1) + (w2 + w3);
+                }
+            }
             // Phi((x_q - mu_t)/sigma_c) = 1/2 erfc((u_t - u_q)), u pre-divided by sqrt 2 (KDE.cl.src:448-456)
             sw[g] += (double)ts;
             if (MODE == 2) sc[g] += (double)((sqrt(w0) + sqrt(w1)) + (sqrt(w2) + sqrt(w3)));

@@ -17,7 +17,8 @@ struct pbn_kde {
     // CKDE::cdf state (pbn_ckde_fit only): classic fragments of the evidence dimensions + u = (x - b.e)/(sigma_c sqrt 2)
     bool ckde = false;
     int cdf_KS = 0;
-    bool cdf_wide = false;              // more than 16 evidence variables: fp64 fragments (whatever the table's type), runtime-sized kernels
+    bool cdf_wide = false;              // fp64 fragments whatever the table's type, through the generic pack: more than 16 evidence variables
+                                        // (runtime-sized kernels) or an fp32 model that kde_wants_widening() flagged (KdeModel::widen)
     std::vector<int> cols_fit;          // caller's column order (variable first)
     const pbn_table* train = nullptr;   // borrowed: CKDE::sample reads the sampled training rows from it
     int64_t train_row0 = 0;

@@ -130,7 +130,7 @@ void ckde_sample_t(pbn_kde* k, int64_t n, int64_t stream_n, const pbn_table* ev,
         for (int64_t i = n; i < stream_n; ++i) (void)uniform(rng);  // the reference draws all of them before the normals
     }
     // query fragments of the evidence rows: whitening order = caller's evidence order, W = leading p x p block
-    const bool wide = k->cdf_wide;               // more than 16 evidence variables: fp64 fragments, runtime-sized kernels
+    const bool wide = k->cdf_wide;               // more than 16 evidence variables or a widened fp32 model: fp64 fragments (kde_handle.hpp)
     const size_t es = wide ? sizeof(double) : sizeof(T);
     const int KS = k->cdf_KS;
     const int64_t tps = std::min<int64_t>(m.ntiles, 64);

@@ -43,7 +43,11 @@ struct UcvScorer {
         KdeModel m;
         kde_prepare(m, t->dtype, d, N, bw, kind, false, center.data());   // throws singular_error when H is not PD
         const int KS = (d + 3) / 4;
-        const bool wide = d > 16;                     // beyond the templated shapes: fp64 fragments through the generic pack, runtime-sized kernel
+        // fp64 fragments through the generic pack: beyond the templated shapes (runtime-sized kernel), and on a float table whose
+        // whitened rows reach too far from the centre for the fp32 Gram form - the rule of KDE.logl (kde_wants_widening); a simplex
+        // search visits such bandwidths.  The price is per evaluation: one small kernel, a memset and a stream synchronise on every score
+        // of a float table (the norm could be carried over between evaluations - it scales with a diagonal bandwidth - but is not)
+        const bool wide = d > 16 || (t->dtype == PBN_F32 && kde_wants_widening(kde_max_norm2(ctx, m, t, cols.data(), row0, N, 0, nullptr), d));
         const int fdt = wide ? PBN_F64 : t->dtype;
         const size_t es = dtype_size(fdt);
         const int64_t ntiles = ceil_div(N, 16);
