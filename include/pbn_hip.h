@@ -362,6 +362,52 @@ int pbn_gnet_slogl(const pbn_gnet* g, const pbn_table* t, double* node_slogl);
 /* evaluation-kernel launches and the rows they covered since creation */
 int pbn_gnet_stats(const pbn_gnet* g, int64_t* launches, int64_t* rows);
 
+/* ---- conditional linear Gaussian networks: evaluation in one device pass -------------------------------------------
+ * pbn_clgnet replaces the loop over the factors of BNGeneric::logl / slogl (models/BayesianNetwork.hpp:997-1022) when
+ * every node is a DiscreteFactor (factors/discrete/DiscreteFactor.cpp:91-171) or a LinearGaussianCPD behind a
+ * DiscreteAdaptator (factors/discrete/DiscreteAdaptator.hpp:327-348 over factors/continuous/LinearGaussianCPD.cpp:
+ * 92-149), i.e. a CLGNetwork.  It is evaluated on a PAIR of tables of the same rows: a pbn_dtable of n_dcols code
+ * columns with these cardinalities and a pbn_table of at least n_ccols continuous columns.  Node n:
+ *   kind[n] = 0  a discrete node: var[n] and dparents[dpar_off[n] .. dpar_off[n + 1]) are columns of the code table, at
+ *                most 8 together; its parameters are its CPT, the variable fastest and the parents in the given order
+ *                (pbn_dnet_create's layout); no continuous parents and no configuration marks.
+ *   kind[n] = 1  a CLG node: var[n] and cparents[cpar_off[n] .. cpar_off[n + 1]) are columns of the continuous table (p
+ *                parents, at most 64 columns together), dparents[...] its at most 7 discrete parents.  A configuration of
+ *                the discrete parents has the index sum code_j * stride_j, the FIRST parent fastest (DiscreteAdaptator.hpp:
+ *                201-260); there is one when there are none.  present[cfg_off[n] + c] != 0: configuration c has a
+ *                factor, and its record - p + 1 coefficients, intercept first, then the variance - lies at
+ *                params[param_off[n] + c (p + 2)]; == 0: it has none (the adaptator's null factor) and the record,
+ *                which must be there all the same, is not read.
+ * All four offset arrays have n_nodes + 1 entries and start at 0.  PBN_ERR_INVALID for a null argument, n_nodes < 1, no
+ * column of either kind, a column outside its table or twice in a discrete family, a family beyond the caps above,
+ * configuration or parameter offsets that do not match the cardinalities, a CLG node of more than
+ * PBN_CLGNET_MAX_CONFIGS configurations, or more than PBN_CLGNET_MAX_PARAMS doubles of parameters on the device (a
+ * CPT cell is one, a record p + 3).  A variance of 0 is not refused (pbn_gnet_create does not refuse it either). */
+#define PBN_CLGNET_MAX_CONFIGS 1048576   /* 2^20 */
+#define PBN_CLGNET_MAX_PARAMS 268435456  /* 2^28 doubles: 2 GiB */
+typedef struct pbn_clgnet pbn_clgnet;
+int pbn_clgnet_create(pbn_ctx* ctx, int n_dcols, const int* cardinality, int n_ccols, int n_nodes, const int* kind,
+                      const int* var, const int* dpar_off, const int* dparents, const int* cpar_off, const int* cparents,
+                      const int* cfg_off, const unsigned char* present, const int64_t* param_off, const double* params,
+                      pbn_clgnet** out);
+void pbn_clgnet_destroy(pbn_clgnet* g);
+/* BNGeneric::logl (models/BayesianNetwork.hpp:997-1008): out[r] (n_rows HOST doubles) = the nodes' values of row r added
+ * one at a time in node order, starting from the first node's.  A discrete node gives its CPT cell (DiscreteFactor.cpp:
+ * 91-131), NaN when a code of its family is -1.  A CLG node gives NaN when a discrete parent's code is -1 or the row's
+ * configuration has no factor (DiscreteAdaptator.hpp:327-337), and otherwise the very value pbn_lg_logl gives the row
+ * under that configuration's coefficients and variance (LinearGaussianCPD.cpp:92-120).  One kernel launch for all nodes
+ * and rows, either dtype; no rows, no launch.  PBN_ERR_INVALID when the tables differ in their row counts or contexts,
+ * the code table's cardinalities are not the network's, or the continuous table has fewer than n_ccols columns. */
+int pbn_clgnet_logl(const pbn_clgnet* g, const pbn_dtable* dt, const pbn_table* t, double* out);
+/* BNGeneric::slogl (models/BayesianNetwork.hpp:1010-1022) over DiscreteFactor::slogl (DiscreteFactor.cpp:133-171),
+ * DiscreteAdaptator::slogl (DiscreteAdaptator.hpp:339-348) and LinearGaussianCPD::slogl (LinearGaussianCPD.cpp:122-149):
+ * node_slogl[i] (n_nodes HOST doubles) = the sum over the rows of the values above, a NaN one counting +0.0: 256-row
+ * block trees on the device, added in block order from 0.0 on the host; all 0.0 for tables without rows.  One launch;
+ * no per-row vector.  Refusals as pbn_clgnet_logl's. */
+int pbn_clgnet_slogl(const pbn_clgnet* g, const pbn_dtable* dt, const pbn_table* t, double* node_slogl);
+/* evaluation-kernel launches and the rows they covered since creation */
+int pbn_clgnet_stats(const pbn_clgnet* g, int64_t* launches, int64_t* rows);
+
 /* ---- one process per GPU: the delta-score cache sharded BEHIND the boundary (shards the serial double
  * loops of learning/operators/operators.cpp:100-132,296-347 and the fold loop of learning/scores/cv_likelihood.cpp:5-25; the
  * reference is one process and has no counterpart).  The host supplies ONE collective - an all-gather of doubles - as a function

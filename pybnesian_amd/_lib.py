@@ -89,6 +89,11 @@ SIGNATURES = {
     "pbn_gnet_logl": (_int, [_vp, _vp, _dp]),
     "pbn_gnet_slogl": (_int, [_vp, _vp, _dp]),
     "pbn_gnet_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "pbn_clgnet_create": (_int, [_vp, _int, _ip, _int, _int, _ip, _ip, _ip, _ip, _ip, _ip, _ip, C.POINTER(C.c_ubyte), C.POINTER(_i64), _dp, C.POINTER(_vp)]),
+    "pbn_clgnet_destroy": (None, [_vp]),
+    "pbn_clgnet_logl": (_int, [_vp, _vp, _vp, _dp]),
+    "pbn_clgnet_slogl": (_int, [_vp, _vp, _vp, _dp]),
+    "pbn_clgnet_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_set_validity": (_int, [_vp, C.POINTER(_vp)]),
     "pbn_split_layout": (_int, [_i64, _int, _int, C.c_uint32, C.c_double, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_layout": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -21,21 +21,11 @@
 #include <vector>
 
 #include "common.hpp"
+#include "discrete_model.hpp"
 #include "scoring_internal.hpp"
 
 using namespace pbn;
 using namespace pbn::score;
-
-struct pbn_dtable : pbn::score::FamilyScratch {
-    pbn::ctx_ptr ctx;
-    int64_t n_rows = 0;
-    int n_cols = 0;
-    std::vector<int> card;
-    std::vector<std::vector<int32_t>> codes;   // host copy, source row order, -1 = null
-    pbn::dev_buf<int32_t> codes_dev;           // [n_cols][n_rows]
-    pbn::dev_buf<uint8_t> codes8;              // [n_cols][ld8], 0xFF = null and in the rows past the last
-    int64_t ld8 = 0;                           // 0: no byte mirror
-};
 
 namespace {
 

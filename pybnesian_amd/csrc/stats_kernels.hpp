@@ -79,6 +79,28 @@ __device__ __forceinline__ void lg_rows_z(const T* __restrict__ base, int64_t ld
         z[i] = inv_std * (y - mean[i]);
     }
 }
+// The same with coefficients of each row's own: row i takes beta[rec[i] + 2 .. rec[i] + 2 + p] (intercept first) and the inv_std at
+// beta[rec[i]] - a record of clgnet_logl_kernel (clg_model.hip), where the configuration of a row's discrete parents selects the
+// LinearGaussianCPD; src[i] of any integer type.  The same statements in the same order as lg_rows_z, so the same products are contracted into the same fmas: a
+// row's z carries the bits lg_rows_z gives it under its record's coefficients.
+template <typename T, int V, typename R>
+__device__ __forceinline__ void lg_rows_z_lanes(const T* __restrict__ base, int64_t ld, int var, const int* __restrict__ ev, int p,
+                                                const double* __restrict__ beta, const uint32_t (&rec)[V], const R (&src)[V], double (&z)[V]) {
+    double mean[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) mean[i] = beta[rec[i] + 2u];
+    for (int j = 1; j <= p; ++j) {
+        const T* col = base + (int64_t)ev[j - 1] * ld;
+#pragma unroll
+        for (int i = 0; i < V; ++i) mean[i] += beta[rec[i] + 2u + (uint32_t)j] * (double)col[src[i]];
+    }
+    const T* ycol = base + (int64_t)var * ld;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+        const double y = (double)ycol[src[i]];
+        z[i] = beta[rec[i]] * (y - mean[i]);
+    }
+}
 __device__ __forceinline__ double lg_value(double z, double cte) { return -0.5 * z * z + cte; }
 #endif
 

@@ -928,6 +928,7 @@ class BayesianNetwork(BayesianNetworkBase):
         from .dataset import as_record_batch, default_context, shared_upload
 
         from . import discrete_model as dm
+        from . import clg_model as cm
         from . import gaussian_model as gm
 
         df = as_record_batch(df)
@@ -937,6 +938,10 @@ class BayesianNetwork(BayesianNetworkBase):
                 return out
         if gm.enabled() and gm.all_lg_factors(self):   # likewise for LinearGaussianCPDs (gaussian_model.py)
             out = gm.network_logl(self, df)
+            if out is not None:
+                return out
+        if cm.enabled() and cm.clg_factors(self):   # likewise for networks of both kinds of node (clg_model.py)
+            out = cm.network_logl(self, df)
             if out is not None:
                 return out
         out = None
@@ -950,6 +955,7 @@ class BayesianNetwork(BayesianNetworkBase):
         if not self.fitted():
             raise ValueError("Model not fitted.")
         from . import discrete_model as dm
+        from . import clg_model as cm
         from . import gaussian_model as gm
         from .dataset import as_record_batch, default_context, shared_upload
 
@@ -962,6 +968,10 @@ class BayesianNetwork(BayesianNetworkBase):
             per_node = gm.network_node_slogl(self, df)
             if per_node is not None:
                 return float(sum(float(v) for v in per_node))   # the loop's sum(...): from 0, in node order
+        if cm.enabled() and cm.clg_factors(self):
+            per_node = cm.network_node_slogl(self, df)
+            if per_node is not None:
+                return float(sum(float(v) for v in per_node))
         with shared_upload(default_context(), df, self._upload_columns()):
             return float(sum(self._cpds[n].slogl(df) for n in self._nodes))
 
