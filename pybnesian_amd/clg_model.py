@@ -6,13 +6,16 @@ and, per configuration of a continuous node's discrete parents, LinearGaussianCP
 
 One upload of the continuous columns, one pbn_dtable of the discrete codes and one pbn_clgnet per call; no handle is kept on the
 model.  `PBN_CLG_MODEL=0` (read per call) restores the per-factor loop.  Networks whose factors are all DiscreteFactor or all
-LinearGaussianCPD are not served here: they keep discrete_model.py / gaussian_model.py and their switches."""
+LinearGaussianCPD are not served here: they keep discrete_model.py / gaussian_model.py and their switches.  The upload, the code
+table, the handle base and the numbering of the columns are network_pass.py's, shared with those two; here are the caps, the
+parameters' packing and the reasons to keep the loop."""
 import ctypes as C
 import os
 
 import numpy as np
 
 from . import _lib
+from .network_pass import FirstUse, Handle, Plan, evaluate_continuous, float_type  # noqa: F401 - Plan: this module's name too
 
 MAX_DISCRETE_FAMILY = 8        # pbn_clgnet_create: a discrete node's variable and 7 parents
 MAX_DISCRETE_PARENTS = 7       # ... a CLG node's discrete parents
@@ -30,19 +33,10 @@ def enabled():
     return os.environ.get("PBN_CLG_MODEL", "1").strip() != "0"
 
 
-class Plan:
-    """The arrays pbn_clgnet_create takes for a list of families over the code columns `dcolumns` and the continuous columns
-    `ccolumns`.  strides[i]: of node i's key columns (a discrete node: the variable, then its parents; a CLG node: its discrete
-    parents), configs[i]: their product.  Node i's parameters are param_off[i] .. param_off[i + 1]: configs[i] CPT cells, or
-    configs[i] records of p + 2 doubles; its configuration marks cfg_off[i] .. cfg_off[i + 1] (none for a discrete node)."""
-
-    def __init__(self, dcolumns, cardinality, ccolumns, kind, var, dpar_off, dparents, cpar_off, cparents, strides, configs, cfg_off, param_off,
-                 within_caps):
-        self.dcolumns, self.cardinality, self.ccolumns = dcolumns, cardinality, ccolumns
-        self.kind, self.var = kind, var
-        self.dpar_off, self.dparents, self.cpar_off, self.cparents = dpar_off, dparents, cpar_off, cparents
-        self.strides, self.configs, self.cfg_off, self.param_off = strides, configs, cfg_off, param_off
-        self.within_caps = within_caps
+# A plan's fields: the code columns `dcolumns` with their `cardinality` and the continuous columns `ccolumns`; per node its kind and
+# var; strides[i]: of node i's key columns (a discrete node: the variable, then its parents; a CLG node: its discrete parents),
+# configs[i]: their product.  Node i's parameters are param_off[i] .. param_off[i + 1]: configs[i] CPT cells, or configs[i] records
+# of p + 2 doubles; its configuration marks cfg_off[i] .. cfg_off[i + 1] (none for a discrete node).
 
 
 def build_plan(families, cards):
@@ -55,27 +49,18 @@ def build_plan(families, cards):
 
     within_caps is False when a family is beyond pbn_clgnet_create's caps (module constants above), names a column twice or has a
     column without categories: such a network keeps the per-factor loop."""
-    dcolumns, dindex, ccolumns, cindex = [], {}, [], {}
+    dindex, cindex = FirstUse(), FirstUse()
     kind, var, dpar_off, dparents, cpar_off, cparents = [], [], [0], [], [0], []
     strides, configs, cfg_off, param_off = [], [], [0], [0]
     within, device_params = True, 0
-
-    def number(name, columns, index):
-        if name not in index:
-            index[name] = len(columns)
-            columns.append(name)
-        return index[name]
-
     for variable, disc, cont in families:
         disc = list(disc)
         clg = cont is not None
         keys = disc if clg else [variable] + disc
-        for name in keys:
-            number(name, dcolumns, dindex)
+        key_ids = [dindex[name] for name in keys]
         if clg:
             cont = list(cont)
-            for name in [variable] + cont:
-                number(name, ccolumns, cindex)
+            cont_ids = [cindex[name] for name in [variable] + cont]
             if len(disc) > MAX_DISCRETE_PARENTS or 1 + len(cont) > MAX_CONTINUOUS_FAMILY:
                 within = False
         elif len(keys) > MAX_DISCRETE_FAMILY:
@@ -89,21 +74,23 @@ def build_plan(families, cards):
         if cells < 1 or (clg and cells > MAX_CONFIGS):
             within = False
         kind.append(CLG if clg else DISCRETE)
-        var.append(cindex[variable] if clg else dindex[variable])
-        dparents.extend(dindex[d] for d in disc)
+        var.append(cont_ids[0] if clg else key_ids[0])
+        dparents.extend(key_ids if clg else key_ids[1:])
         dpar_off.append(len(dparents))
         if clg:
-            cparents.extend(cindex[c] for c in cont)
+            cparents.extend(cont_ids[1:])
         cpar_off.append(len(cparents))
         strides.append(st)
         configs.append(cells)
         cfg_off.append(cfg_off[-1] + (cells if clg else 0))
         param_off.append(param_off[-1] + (cells * (len(cont) + 2) if clg else cells))
         device_params += cells * (len(cont) + 3) if clg else cells
+    dcolumns, ccolumns = list(dindex), list(cindex)
     if device_params > MAX_PARAMS or not dcolumns or not ccolumns:
         within = False
-    return Plan(dcolumns, [int(cards[c]) for c in dcolumns], ccolumns, kind, var, dpar_off, dparents, cpar_off, cparents, strides, configs, cfg_off,
-                param_off, within)
+    return Plan(dcolumns=dcolumns, cardinality=[int(cards[c]) for c in dcolumns], ccolumns=ccolumns, kind=kind, var=var, dpar_off=dpar_off,
+                dparents=dparents, cpar_off=cpar_off, cparents=cparents, strides=strides, configs=configs, cfg_off=cfg_off, param_off=param_off,
+                within_caps=within)
 
 
 def clg_factors(model):
@@ -163,18 +150,7 @@ def _evaluation(model, rb):
             if dcols[name][1] != list(want):
                 return None   # the loop raises "does not contain the same categories"
     plan = build_plan([(v, d, c) for v, d, c, _, _ in described], cards)
-    if not plan.within_caps:
-        return None
-    types = set()
-    for name in plan.ccolumns:
-        idx = rb.schema.get_field_index(name)
-        if idx < 0:
-            return None
-        types.add(rb.schema.field(idx).type)
-    if len(types) != 1:
-        return None
-    t = next(iter(types))
-    if not (pa.types.is_float64(t) or pa.types.is_float32(t)):
+    if not plan.within_caps or float_type(rb, plan.ccolumns) is None:
         return None
     params = np.zeros(plan.param_off[-1], dtype=np.float64)
     present = np.zeros(max(plan.cfg_off[-1], 1), dtype=np.uint8)
@@ -203,34 +179,19 @@ def _evaluation(model, rb):
     return plan, [dcols[c][0] for c in plan.dcolumns], params, present
 
 
-class _CodeTable:
-    """A pbn_dtable of int32 code arrays (-1 = null)."""
+class _CLGNet(Handle):
+    prefix, counters, stat_keys = "pbn_clgnet", counters, ("launches", "rows_evaluated")
 
-    def __init__(self, ctx, codes, cardinality, n_rows):
-        self._codes = codes
-        ptrs = (C.c_void_p * len(codes))(*[a.ctypes.data for a in codes])
-        h = C.c_void_p()
-        _lib.check(_lib.load().pbn_dtable_create(ctx.handle, int(n_rows), len(codes), ptrs, _lib.int_array(cardinality), C.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if self.handle:
-            _lib.load().pbn_dtable_destroy(self.handle)
-            self.handle = None
-
-
-class _CLGNet:
     def __init__(self, ctx, plan, params, present):
         self._keep = (np.ascontiguousarray(params, dtype=np.float64), np.ascontiguousarray(present, dtype=np.uint8),
                       np.ascontiguousarray(plan.param_off, dtype=np.int64))
         params, present, param_off = self._keep
-        h = C.c_void_p()
-        _lib.check(_lib.load().pbn_clgnet_create(
+        super().__init__(
             ctx.handle, len(plan.dcolumns), _lib.int_array(plan.cardinality), len(plan.ccolumns), len(plan.var), _lib.int_array(plan.kind),
             _lib.int_array(plan.var), _lib.int_array(plan.dpar_off), _lib.int_array(plan.dparents or [0]), _lib.int_array(plan.cpar_off),
             _lib.int_array(plan.cparents or [0]), _lib.int_array(plan.cfg_off), present.ctypes.data_as(C.POINTER(C.c_ubyte)),
-            param_off.ctypes.data_as(C.POINTER(C.c_int64)), _lib.dptr(params), C.byref(h)))
-        self.handle, self.n_nodes = h, len(plan.var)
+            param_off.ctypes.data_as(C.POINTER(C.c_int64)), _lib.dptr(params))
+        self.n_nodes = len(plan.var)
         counters["clgnet_created"] += 1
 
     def logl(self, codes, table):
@@ -243,65 +204,23 @@ class _CLGNet:
         _lib.check(_lib.load().pbn_clgnet_slogl(self.handle, codes.handle, table.handle, _lib.dptr(out)))
         return out
 
-    def close(self):
-        if self.handle:
-            launches, rows = C.c_int64(0), C.c_int64(0)
-            _lib.check(_lib.load().pbn_clgnet_stats(self.handle, C.byref(launches), C.byref(rows)))
-            counters["launches"] += launches.value
-            counters["rows_evaluated"] += rows.value
-            _lib.load().pbn_clgnet_destroy(self.handle)
-            self.handle = None
 
-
-def _has_nulls(rb, columns):
-    return any(rb.column(rb.schema.get_field_index(c)).null_count for c in columns)
-
-
-def _run(plan, dcols, params, present, rb, what):
-    from .dataset import DeviceTable, default_context
-    from .discrete_model import _codes
-
-    ctx = default_context()
-    table, mask = DeviceTable.from_dataframe(ctx, rb, plan.ccolumns)   # drops the rows null in any continuous column
-    if list(table.names) != list(plan.ccolumns):
-        return None   # a shared upload of other columns: the plan's numbering would not hold
-    codes = [_codes(c) for c in dcols]                                  # nulls in discrete columns travel as -1
-    if mask is not None:
-        codes = [np.ascontiguousarray(c[mask]) for c in codes]
-    ctable = _CodeTable(ctx, codes, plan.cardinality, table.num_rows)
-    try:
-        net = _CLGNet(ctx, plan, params, present)
-        try:
-            return getattr(net, what)(ctable, table), mask
-        finally:
-            net.close()
-    finally:
-        ctable.close()
+def _evaluate(model, rb, what):
+    ev = _evaluation(model, rb)
+    if ev is None:
+        return None
+    plan, dcols, params, present = ev
+    return evaluate_continuous(rb, plan.ccolumns, lambda ctx: _CLGNet(ctx, plan, params, present), what, dcols, plan.cardinality)
 
 
 def network_logl(model, rb):
     """Per-row log-likelihood: the nodes' values added in node order on the device, NaN where a row is null in any continuous
     column of the network (it is NaN in that factor's logl and so in the loop's sum); None when the per-factor loop must run."""
-    ev = _evaluation(model, rb)
-    if ev is None:
-        return None
-    res = _run(*ev, rb, "logl")
-    if res is None:
-        return None
-    vals, mask = res
-    if mask is None:
-        return vals
-    out = np.full(rb.num_rows, np.nan)
-    out[mask] = vals
-    return out
+    return _evaluate(model, rb, "logl")
 
 
 def network_node_slogl(model, rb):
     """The nodes' summed log-likelihoods in node order (float64 array), a NaN row counting 0 as in DiscreteFactor.slogl's nansum and
     the adaptator's skipped configurations; None when the loop must run: also when a continuous column of the network has nulls (each
     factor then sums over its own family's valid rows).  Nulls in discrete columns are served."""
-    ev = _evaluation(model, rb)
-    if ev is None or _has_nulls(rb, ev[0].ccolumns):
-        return None
-    res = _run(*ev, rb, "node_slogl")
-    return None if res is None else res[0]
+    return _evaluate(model, rb, "node_slogl")

@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 #include "discrete_model.hpp"
+#include "net_eval.hpp"
 #include "stats_kernels.hpp"
 
 using namespace pbn;
@@ -41,6 +42,8 @@ constexpr int CLG_MAX_DISCRETE_PARENTS = 7;
 constexpr int CLG_MAX_FAMILY = 64;            // a CLG node's continuous columns, the variable and 63 parents: the cap of pbn_lg_logl
 constexpr int64_t CLG_MAX_CONFIGS = PBN_CLGNET_MAX_CONFIGS;
 constexpr int64_t CLG_MAX_PARAMS = PBN_CLGNET_MAX_PARAMS;
+
+static_assert(BLOCK == NET_GROUP_ROWS, "a partial is one workgroup of rows");
 
 struct CNode {
     int kind;        // 0 discrete, 1 CLG
@@ -214,6 +217,7 @@ int pbn_clgnet_create(pbn_ctx* ctx, int n_dcols, const int* cardinality, int n_c
             if (c < 1) throw bad("a cardinality below 1");
         g->nodes.resize((size_t)n_nodes);
         int64_t total = 0;   // doubles of parameters on the device
+        std::vector<int> keys;
         for (int n = 0; n < n_nodes; ++n) {
             const int dp = dpar_off[n + 1] - dpar_off[n], p = cpar_off[n + 1] - cpar_off[n], n_cfg = cfg_off[n + 1] - cfg_off[n];
             if (dp < 0 || p < 0 || n_cfg < 0) throw bad("bad offsets");
@@ -223,6 +227,7 @@ int pbn_clgnet_create(pbn_ctx* ctx, int n_dcols, const int* cardinality, int n_c
             d = CNode{};
             d.kind = kind[n];
             d.var = var[n];
+            keys.clear();
             if (clg) {
                 if (dp > CLG_MAX_DISCRETE_PARENTS) throw bad("a CLG node with more than 7 discrete parents");
                 if (1 + p > CLG_MAX_FAMILY) throw bad("a CLG node with more than 64 continuous family columns");
@@ -232,22 +237,15 @@ int pbn_clgnet_create(pbn_ctx* ctx, int n_dcols, const int* cardinality, int n_c
             } else {
                 if (1 + dp > CLG_MAX_KEY_COLS) throw bad("a discrete node with more than 8 family variables");
                 if (p != 0 || n_cfg != 0) throw bad("a discrete node with continuous parents or configuration marks");
-                if (var[n] < 0 || var[n] >= n_dcols) throw bad("column out of range");
-                d.col[d.m++] = var[n];
+                keys.push_back(var[n]);
             }
-            for (int j = 0; j < dp; ++j) {
-                const int c = dparents[dpar_off[n] + j];
-                if (c < 0 || c >= n_dcols) throw bad("column out of range");
-                for (int k = 0; k < d.m; ++k)
-                    if (d.col[k] == c) throw bad("a column appears twice in a family");
-                d.col[d.m++] = c;
-            }
-            int64_t G = 1;
-            for (int j = 0; j < d.m; ++j) {
-                d.stride[j] = (uint32_t)G;
-                G *= g->card[(size_t)d.col[j]];
-                if (G > (clg ? CLG_MAX_CONFIGS : CLG_MAX_PARAMS)) throw bad(clg ? "a CLG node with more than 2^20 configurations" : "the parameters exceed 2^28 doubles");
-            }
+            keys.insert(keys.end(), dparents + dpar_off[n], dparents + dpar_off[n] + dp);
+            check_family_cols(n_dcols, keys, who);
+            d.m = (int)keys.size();
+            std::copy(keys.begin(), keys.end(), d.col);
+            const int64_t cap = clg ? CLG_MAX_CONFIGS : CLG_MAX_PARAMS;
+            const int64_t G = family_strides(g->card, keys, d.stride, cap);
+            if (G > cap) throw bad(clg ? "a CLG node with more than 2^20 configurations" : "the parameters exceed 2^28 doubles");
             d.G = (uint32_t)G;
             d.p = p;
             d.rec = (uint32_t)(p + 3);
@@ -293,12 +291,7 @@ int pbn_clgnet_create(pbn_ctx* ctx, int n_dcols, const int* cardinality, int n_c
     });
 }
 
-void pbn_clgnet_destroy(pbn_clgnet* g) {
-    if (!g) return;
-    ctx_pin pin(g->ctx);
-    std::lock_guard<std::recursive_mutex> lock(mu_of(g));
-    delete g;
-}
+void pbn_clgnet_destroy(pbn_clgnet* g) { destroy_handle(g); }
 
 int pbn_clgnet_logl(const pbn_clgnet* g, const pbn_dtable* dt, const pbn_table* t, double* out) {
     return guarded(mu_of(t), [&] {
@@ -306,12 +299,7 @@ int pbn_clgnet_logl(const pbn_clgnet* g, const pbn_dtable* dt, const pbn_table* 
         const int64_t n = t->n_rows;
         if (n == 0) return;
         if (!out) throw invalid_error("pbn_clgnet_logl: null output");
-        pbn_ctx* ctx = t->ctx;
-        HIP_CHECK(hipSetDevice(ctx->device));
-        dev_buf<double> dout((size_t)n);
-        launch_clgnet<false>(g, dt, t, dout.p);
-        HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        rows_to_host(t->ctx, n, out, [&](double* dev) { launch_clgnet<false>(g, dt, t, dev); });
     });
 }
 
@@ -319,32 +307,12 @@ int pbn_clgnet_slogl(const pbn_clgnet* g, const pbn_dtable* dt, const pbn_table*
     return guarded(mu_of(t), [&] {
         check_tables(g, dt, t, "pbn_clgnet_slogl");
         if (!node_slogl) throw invalid_error("pbn_clgnet_slogl: null output");
-        const size_t N = g->nodes.size();
-        const int64_t n = t->n_rows;
-        for (size_t i = 0; i < N; ++i) node_slogl[i] = 0.0;
-        if (n == 0) return;
-        pbn_ctx* ctx = t->ctx;
-        HIP_CHECK(hipSetDevice(ctx->device));
-        const size_t n_groups = (size_t)ceil_div(n, BLOCK);
-        dev_buf<double> dpart(N * n_groups);
-        launch_clgnet<true>(g, dt, t, dpart.p);
-        std::vector<double> part(N * n_groups);
-        HIP_CHECK(hipMemcpyAsync(part.data(), dpart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; i < N; ++i) {
-            double s = 0.0;
-            for (size_t b = 0; b < n_groups; ++b) s += part[i * n_groups + b];   // fixed order: lg_eval's
-            node_slogl[i] = s;
-        }
+        node_sums_to_host(t->ctx, g->nodes.size(), t->n_rows, node_slogl, [&](double* dev) { launch_clgnet<true>(g, dt, t, dev); });
     });
 }
 
 int pbn_clgnet_stats(const pbn_clgnet* g, int64_t* launches, int64_t* rows) {
-    return guarded(mu_of(g), [&] {
-        if (!g) throw invalid_error("pbn_clgnet_stats: null argument");
-        if (launches) *launches = g->launches;
-        if (rows) *rows = g->rows;
-    });
+    return handle_stats(g, "pbn_clgnet_stats", &pbn_clgnet::launches, &pbn_clgnet::rows, launches, rows);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 
 #include "common.hpp"
 #include "discrete_model.hpp"
+#include "net_eval.hpp"
 #include "scoring_internal.hpp"
 
 using namespace pbn;
@@ -121,23 +122,6 @@ struct AskedFamily {
     int64_t G = 1;
     size_t canon = 0;        // index into the distinct families (the variable, then the parents ascending)
 };
-
-int64_t cells_of(const std::vector<int>& card, const std::vector<int>& cols, const char* who) {
-    int64_t G = 1;
-    for (int c : cols) {
-        if (G > (std::numeric_limits<int64_t>::max() >> 1) / std::max(card[c], 1)) throw invalid_error(std::string(who) + ": a family's table has too many cells");
-        G *= card[c];
-    }
-    return G;
-}
-
-void check_family_cols(int n_cols, const std::vector<int>& cols, const char* who) {
-    for (size_t a = 0; a < cols.size(); ++a) {
-        if (cols[a] < 0 || cols[a] >= n_cols) throw invalid_error(std::string(who) + ": column out of range");
-        for (size_t b = 0; b < a; ++b)
-            if (cols[a] == cols[b]) throw invalid_error(std::string(who) + ": a column appears twice in a family");
-    }
-}
 
 // table in canonical order (the variable, then the parents ascending) -> the order of `cols`
 void permute_table(const std::vector<int>& card, const std::vector<int>& canon_cols, const std::vector<int>& cols, const int64_t* src, int64_t* dst) {
@@ -277,12 +261,7 @@ int pbn_dtable_create(pbn_ctx* ctx, int64_t n_rows, int n_cols, const int32_t* c
     });
 }
 
-void pbn_dtable_destroy(pbn_dtable* dt) {
-    if (!dt) return;
-    ctx_pin pin(dt->ctx);
-    std::lock_guard<std::recursive_mutex> lock(mu_of(dt));
-    delete dt;
-}
+void pbn_dtable_destroy(pbn_dtable* dt) { destroy_handle(dt); }
 
 int pbn_dtable_family_counts(pbn_dtable* dt, int n_fam, const int* var, const int* par_off, const int* parents, int64_t* out_off, int64_t* out_counts,
                              int64_t cap, int* out_form) {
@@ -332,8 +311,8 @@ int pbn_dnet_create(pbn_ctx* ctx, int n_cols, const int* cardinality, int n_node
             d.m = 1 + p;
             d.G = (uint32_t)G;
             d.cpt_off = cpt_off[n];
-            uint32_t stride = 1u;
-            for (int j = 0; j < d.m; ++j) { d.col[j] = cols[(size_t)j]; d.stride[j] = stride; stride *= (uint32_t)dn->card[cols[(size_t)j]]; }
+            std::copy(cols.begin(), cols.end(), d.col);
+            family_strides(dn->card, cols, d.stride, DNET_MAX_CELLS);   // (the strides alone: G, checked above, is within the cap)
         }
         dn->logprob.assign(logprob, logprob + cpt_off[n_nodes]);
         HIP_CHECK(hipSetDevice(ctx->device));
@@ -346,12 +325,7 @@ int pbn_dnet_create(pbn_ctx* ctx, int n_cols, const int* cardinality, int n_node
     });
 }
 
-void pbn_dnet_destroy(pbn_dnet* dn) {
-    if (!dn) return;
-    ctx_pin pin(dn->ctx);
-    std::lock_guard<std::recursive_mutex> lock(mu_of(dn));
-    delete dn;
-}
+void pbn_dnet_destroy(pbn_dnet* dn) { destroy_handle(dn); }
 
 static void check_same_columns(const pbn_dnet* dn, const pbn_dtable* dt, const char* who) {
     if (dn->ctx.p != dt->ctx.p) throw invalid_error(std::string(who) + ": the network and the table belong to different contexts");
@@ -417,11 +391,7 @@ int pbn_dnet_slogl(pbn_dnet* dn, pbn_dtable* dt, double* out_total, double* out_
 }
 
 int pbn_dnet_stats(const pbn_dnet* dn, int64_t* logl_launches, int64_t* rows_evaluated) {
-    return guarded(mu_of(dn), [&] {
-        if (!dn) throw invalid_error("pbn_dnet_stats: null argument");
-        if (logl_launches) *logl_launches = dn->logl_launches;
-        if (rows_evaluated) *rows_evaluated = dn->rows_evaluated;
-    });
+    return handle_stats(dn, "pbn_dnet_stats", &pbn_dnet::logl_launches, &pbn_dnet::rows_evaluated, logl_launches, rows_evaluated);
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "net_eval.hpp"
 #include "stats_kernels.hpp"
 
 using namespace pbn;
@@ -29,6 +30,8 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr int V = 4;                 // rows of a lane, BLOCK apart: the row tile of a workgroup is 1 024
 constexpr int GNET_MAX_FAMILY = 64;  // the variable and 63 parents: the cap of pbn_lg_logl / LgArgs
+
+static_assert(BLOCK == NET_GROUP_ROWS, "a partial is one workgroup of rows");
 
 struct GNode {
     int var;        // the variable's column
@@ -174,12 +177,7 @@ int pbn_gnet_create(pbn_ctx* ctx, int n_cols, int n_nodes, const int* var, const
     });
 }
 
-void pbn_gnet_destroy(pbn_gnet* g) {
-    if (!g) return;
-    ctx_pin pin(g->ctx);
-    std::lock_guard<std::recursive_mutex> lock(mu_of(g));
-    delete g;
-}
+void pbn_gnet_destroy(pbn_gnet* g) { destroy_handle(g); }
 
 int pbn_gnet_logl(const pbn_gnet* g, const pbn_table* t, double* out) {
     return guarded(mu_of(t), [&] {
@@ -187,12 +185,7 @@ int pbn_gnet_logl(const pbn_gnet* g, const pbn_table* t, double* out) {
         const int64_t n = t->n_rows;
         if (n == 0) return;
         if (!out) throw invalid_error("pbn_gnet_logl: null output");
-        pbn_ctx* ctx = t->ctx;
-        HIP_CHECK(hipSetDevice(ctx->device));
-        dev_buf<double> dout((size_t)n);
-        launch_gnet<false>(g, t, dout.p);
-        HIP_CHECK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        rows_to_host(t->ctx, n, out, [&](double* dev) { launch_gnet<false>(g, t, dev); });
     });
 }
 
@@ -200,32 +193,12 @@ int pbn_gnet_slogl(const pbn_gnet* g, const pbn_table* t, double* node_slogl) {
     return guarded(mu_of(t), [&] {
         check_table(g, t, "pbn_gnet_slogl");
         if (!node_slogl) throw invalid_error("pbn_gnet_slogl: null output");
-        const size_t N = g->nodes.size();
-        const int64_t n = t->n_rows;
-        for (size_t i = 0; i < N; ++i) node_slogl[i] = 0.0;
-        if (n == 0) return;
-        pbn_ctx* ctx = t->ctx;
-        HIP_CHECK(hipSetDevice(ctx->device));
-        const size_t n_groups = (size_t)ceil_div(n, BLOCK);
-        dev_buf<double> dpart(N * n_groups);
-        launch_gnet<true>(g, t, dpart.p);
-        std::vector<double> part(N * n_groups);
-        HIP_CHECK(hipMemcpyAsync(part.data(), dpart.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        for (size_t i = 0; i < N; ++i) {
-            double s = 0.0;
-            for (size_t b = 0; b < n_groups; ++b) s += part[i * n_groups + b];   // fixed order: lg_eval's
-            node_slogl[i] = s;
-        }
+        node_sums_to_host(t->ctx, g->nodes.size(), t->n_rows, node_slogl, [&](double* dev) { launch_gnet<true>(g, t, dev); });
     });
 }
 
 int pbn_gnet_stats(const pbn_gnet* g, int64_t* launches, int64_t* rows) {
-    return guarded(mu_of(g), [&] {
-        if (!g) throw invalid_error("pbn_gnet_stats: null argument");
-        if (launches) *launches = g->launches;
-        if (rows) *rows = g->rows;
-    });
+    return handle_stats(g, "pbn_gnet_stats", &pbn_gnet::launches, &pbn_gnet::rows, launches, rows);
 }
 
 }  // extern "C"

@@ -6,8 +6,7 @@ learning/independences/independence.hpp:42-77), DynamicBayesianNetwork (models/D
 "transition" table, with the scores, tests, MMPC and hill-climb of this package."""
 import numpy as np
 
-from . import clg_model as cm
-from . import gaussian_model as gm
+from .network_pass import CLG, GAUSSIAN, one_pass
 from .dataset import as_record_batch
 from .models import BayesianNetwork, GaussianNetworkType
 
@@ -300,8 +299,7 @@ class DynamicBayesianNetwork(DynamicBayesianNetworkBase):
                 ll[i] += self._static.cpd(temporal_name(v, self._order - i)).slogl(dstatic)
         if rb.num_rows > self._order:
             dtrans = transition_table(rb, self._order)
-            one_pass = self._transition_in_one_pass()
-            whole = one_pass.network_logl(self._transition, as_record_batch(dtrans)) if one_pass else None
+            whole = self._transition_in_one_pass(dtrans, "logl")
             if whole is not None:   # the same adds: 0 + (ll_0 + ll_1 + ...) carries the bits of ((0 + ll_0) + ll_1) + ...
                 ll[self._order:] += whole
             else:
@@ -309,18 +307,16 @@ class DynamicBayesianNetwork(DynamicBayesianNetworkBase):
                     ll[self._order:] += self._transition.cpd(temporal_name(v, 0)).logl(dtrans)
         return ll
 
-    def _transition_in_one_pass(self):
-        """The module the transition network goes through in one pass, or None: gaussian_model.py when all its factors are exactly
-        LinearGaussianCPD, clg_model.py when they are DiscreteFactors and (C)LinearGaussianCPDs of both kinds - and its node order is the
-        order this class adds the variables' values in."""
+    def _transition_in_one_pass(self, dtrans, what):
+        """The transition network's "logl" (per row) or "slogl" (per node) over `dtrans` in one pass, or None: gaussian_model.py when all
+        its factors are exactly LinearGaussianCPD, clg_model.py when they are DiscreteFactors and (C)LinearGaussianCPDs of both kinds -
+        and its node order is the order this class adds the variables' values in.  Known gap: the discrete pass is not asked, so an
+        all-DiscreteFactor transition network stays on the per-factor loop."""
         t = self._transition
         if list(t._nodes) != [temporal_name(v, 0) for v in self._variables]:
             return None
-        if gm.enabled() and gm.all_lg_factors(t):
-            return gm
-        if cm.enabled() and cm.clg_factors(t):
-            return cm
-        return None
+        served = one_pass(t, dtrans, what, only=(GAUSSIAN, CLG))
+        return None if served is None else served.value
 
     def slogl(self, df):
         rb = as_record_batch(df)
@@ -332,8 +328,7 @@ class DynamicBayesianNetwork(DynamicBayesianNetworkBase):
                 total += self._static.cpd(temporal_name(v, self._order - i)).slogl(dstatic)
         if rb.num_rows > self._order:
             dtrans = transition_table(rb, self._order)
-            one_pass = self._transition_in_one_pass()
-            per_node = one_pass.network_node_slogl(self._transition, as_record_batch(dtrans)) if one_pass else None
+            per_node = self._transition_in_one_pass(dtrans, "slogl")
             if per_node is not None:
                 for s in per_node:
                     total += float(s)

@@ -926,24 +926,12 @@ class BayesianNetwork(BayesianNetworkBase):
         import numpy as np
 
         from .dataset import as_record_batch, default_context, shared_upload
-
-        from . import discrete_model as dm
-        from . import clg_model as cm
-        from . import gaussian_model as gm
+        from .network_pass import one_pass
 
         df = as_record_batch(df)
-        if dm.enabled() and dm.all_discrete_factors(self):   # one launch for all nodes; the same adds in the same order
-            out = dm.network_logl(self, df)
-            if out is not None:
-                return out
-        if gm.enabled() and gm.all_lg_factors(self):   # likewise for LinearGaussianCPDs (gaussian_model.py)
-            out = gm.network_logl(self, df)
-            if out is not None:
-                return out
-        if cm.enabled() and cm.clg_factors(self):   # likewise for networks of both kinds of node (clg_model.py)
-            out = cm.network_logl(self, df)
-            if out is not None:
-                return out
+        served = one_pass(self, df, "logl")   # one launch for all nodes; the same adds in the same order
+        if served is not None:
+            return served.value
         out = None
         with shared_upload(default_context(), df, self._upload_columns()):
             for n in self._nodes:
@@ -954,24 +942,15 @@ class BayesianNetwork(BayesianNetworkBase):
     def slogl(self, df):
         if not self.fitted():
             raise ValueError("Model not fitted.")
-        from . import discrete_model as dm
-        from . import clg_model as cm
-        from . import gaussian_model as gm
         from .dataset import as_record_batch, default_context, shared_upload
+        from .network_pass import one_pass
 
         df = as_record_batch(df)
-        if dm.enabled() and dm.all_discrete_factors(self):
-            total = dm.network_slogl(self, df)
-            if total is not None:
-                return float(total)
-        if gm.enabled() and gm.all_lg_factors(self):
-            per_node = gm.network_node_slogl(self, df)
-            if per_node is not None:
-                return float(sum(float(v) for v in per_node))   # the loop's sum(...): from 0, in node order
-        if cm.enabled() and cm.clg_factors(self):
-            per_node = cm.network_node_slogl(self, df)
-            if per_node is not None:
-                return float(sum(float(v) for v in per_node))
+        served = one_pass(self, df, "slogl")
+        if served is not None:
+            if served.is_total:
+                return float(served.value)                       # the discrete pass: the total as the C side added it
+            return float(sum(float(v) for v in served.value))    # the nodes' sums as the loop's sum(...) adds them: from 0, in node order
         with shared_upload(default_context(), df, self._upload_columns()):
             return float(sum(self._cpds[n].slogl(df) for n in self._nodes))
 

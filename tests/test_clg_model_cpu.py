@@ -3,17 +3,13 @@ figures of clgnet_logl_kernel (csrc/clg_model.hip) read from the kernel descript
 
 The kernel is a streaming loop with next to no arithmetic: waves in flight hide its load latency.  Scratch memory or a fall in the
 waves per SIMD changes no result, so no numerical test would notice."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+from helpers import unit_asm
 
 from pybnesian_amd import clg_model as cm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pybnesian_amd", "csrc")
 
 
 def test_plan_numbers_both_column_kinds_by_first_use():
@@ -94,12 +90,8 @@ def test_enabled_follows_the_environment_per_call(monkeypatch):
 
 
 @pytest.fixture(scope="module")
-def clgnet_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "clg_model.s"
-    p = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                        "clg_model.hip", "-o", str(out)], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return out.read_text()
+def clgnet_asm():
+    return unit_asm("clg_model")
 
 
 def test_no_instantiation_uses_scratch_and_the_waves_per_simd_hold(clgnet_asm):

@@ -3,16 +3,12 @@ the resource figures of gnet_logl_kernel (csrc/gaussian_model.hip) read from the
 
 The kernel is a streaming loop with next to no arithmetic: what hides its load latency is eight waves per SIMD, which needs at most
 64 VGPRs and no scratch memory.  Losing that changes no result, so no numerical test would notice."""
-import os
 import re
-import subprocess
 
 import pytest
+from helpers import unit_asm
 
 from pybnesian_amd import gaussian_model as gm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "pybnesian_amd", "csrc")
 
 
 def test_plan_numbers_columns_by_first_use():
@@ -59,12 +55,8 @@ def test_enabled_follows_the_environment_per_call(monkeypatch):
 
 
 @pytest.fixture(scope="module")
-def gnet_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "gaussian_model.s"
-    p = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only",
-                        "gaussian_model.hip", "-o", str(out)], cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return out.read_text()
+def gnet_asm():
+    return unit_asm("gaussian_model")
 
 
 def test_every_instantiation_keeps_eight_waves_and_no_scratch(gnet_asm):
