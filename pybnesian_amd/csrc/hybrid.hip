@@ -537,7 +537,6 @@ double local_lg_slogl(const pbn_scoredata* sd, const Stats& test, const int* col
     return -0.5 * Nt * (std::log(variance) + LOG_2PI) - 0.5 * rss / variance;
 }
 
-struct Term { double value = 0; int slot = -1; };
 struct Slice { Term joint, marg; bool has_marg; int part; };
 // what a check-after redo needs, flat (one candidate makes ~100 terms, a search thousands of candidates: no per-term allocations): the
 // term's bandwidth and centre in `rstore`, its columns in `rcols`
@@ -609,7 +608,6 @@ struct HybridBatch {
 void HybridBatch::flush() {
     if (!active) return;
     const pbn_table* t = sd->table();
-    auto align = [](size_t x) { return (x + 255) / 256 * 256; };
     kick();
     const size_t ns = slot_key.size();
     std::vector<double> hs(std::max<size_t>(1, ns)), hmax(f32 ? ns : 0);
@@ -630,14 +628,8 @@ void HybridBatch::flush() {
             kde_prepare(m, sd->dtype, r.nv, r.N, rstore.data() + r.off, PBN_BW_FULL, false, rstore.data() + r.off + (size_t)r.nv * r.nv);
             if (f32) kde_widen(m);
             else ++sd->precise_redos;
-            const KdePackBytes pb = kde_pack_bytes(m.fdtype(), m.dm, false, m.N);
-            ctx->scratch_train.reserve(align(pb.apack) + align(pb.nxpack) + 256);
-            m.Apack = ctx->scratch_train.p;
-            m.nxpack = ctx->scratch_train.p + align(pb.apack);
-            m.Axpack = nullptr;
             HIP_CHECK(hipMemsetAsync(dsums + r.slot, 0, sizeof(double), ctx->stream));
-            kde_pack_train(ctx, m, t, v, r.r0, r.n0, r.r1, r.rows, /*prune=*/true);
-            kde_eval_enqueue(ctx, m, t, v, r.te0, r.nte, nullptr, dsums + r.slot, r.rows, nullptr, /*precise=*/f64);
+            enqueue_term_chain(ctx, m, t, v, TermRows{r.r0, r.n0, r.r1, r.te0, r.nte}, r.rows, dsums + r.slot, nullptr, /*precise=*/f64);
             ++sd->kde_sweeps;
             any = true;
         }
@@ -678,8 +670,7 @@ void HybridBatch::flush() {
 }
 
 HybridBatch* hybrid_batch_begin(pbn_scoredata* sd) {
-    static const bool check_after = PBN_TUNE(F32_CHECK, 1) != 0;   // 0: measurement only
-    return new HybridBatch(sd, sd->dtype == PBN_F32 && check_after);
+    return new HybridBatch(sd, sd->dtype == PBN_F32 && f32_check_after());
 }
 void hybrid_batch_flush(HybridBatch* hb) { if (hb) hb->flush(); }
 void hybrid_batch_end(HybridBatch* hb) noexcept { delete hb; }
@@ -905,12 +896,11 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
         k.push_back(canon[c]);
         return k;
     };
-    auto align = [](size_t x) { return (x + 255) / 256 * 256; };
     // Grouped evaluation (kde_group.hip): the slices of one configuration and one term (joint / marginal variable set) share a
     // POOL - the configuration's block of the grouped row list, its regions the folds (or hold-out train / test) - and are
     // evaluated by one launch chain for the whole candidate instead of one chain per (fold, configuration, term).  A pool takes
     // this path when every training slice of the configuration is large enough for the pruned sweeps.
-    GroupBatch gb;
+    std::vector<GPool> pools;
     std::vector<std::vector<GUnit>> pool_units;
     std::vector<int> pool_of((size_t)g.nc * 2, -1);   // (configuration, which) -> pool
     std::vector<char> elig((size_t)g.nc * 2, 0);
@@ -928,10 +918,10 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
         }
     }
     // v: the term's columns, colidx: their indices in `cols` (the joint in ascending order, the marginal = cols[1:])
-    auto group_unit = [&](int c, int u, int which, const KdeModel& m, const int* v, const int* colidx, int nv, int64_t ntrain, int64_t ntest, int slot) {
+    auto add_unit = [&](int c, int u, int which, const KdeModel& m, const int* v, const int* colidx, int nv, int64_t ntrain, int64_t ntest, int slot) {
         int& pi = pool_of[(size_t)c * 2 + which];
         if (pi < 0) {
-            pi = (int)gb.pools.size();
+            pi = (int)pools.size();
             GPool P{};
             const int64_t base = g.off[cell(c, 0)];
             P.rows = g.rows.p; P.row_base = base;
@@ -944,31 +934,19 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
             // pool-level standardisation for the Morton keys: the configuration's own covariance of the term's columns (training
             // part for the hold-out score); a singular one falls back to the diagonal - the keys only order the rows
             const Stats& all = cv ? allc[c] : M[cell(c, 0)];
-            std::vector<double> gm(d), gs((size_t)d * d), sub((size_t)nv * nv), L((size_t)nv * nv), Li((size_t)nv * nv);
+            std::vector<double> gm(d), gs((size_t)d * d), sub((size_t)nv * nv);
+            double mean[PBN_GROUP_MAX_D];
             local_moments(sd, all, cols.data(), d, gm.data(), gs.data());
-            for (int j = 0; j < nv; ++j)
+            for (int j = 0; j < nv; ++j) {
+                mean[j] = gm[colidx[j]];
                 for (int i = 0; i < nv; ++i) sub[i + (size_t)j * nv] = gs[colidx[i] + (size_t)colidx[j] * d] / (double)std::max<int64_t>(1, all.N - 1);
-            if (!hm::cholesky(sub.data(), nv, L.data())) {
-                std::fill(L.begin(), L.end(), 0.0);
-                for (int i = 0; i < nv; ++i) L[i + (size_t)i * nv] = std::sqrt(std::max(sub[i + (size_t)i * nv], 1e-300));
             }
-            hm::lower_inverse(L.data(), nv, Li.data());
-            for (int i = 0; i < nv; ++i) {
-                P.mug[i] = gm[colidx[i]];
-                for (int j = 0; j < nv; ++j) P.Wg[i * nv + j] = j <= i ? Li[i + (size_t)j * nv] : 0.0;
-            }
-            gb.pools.push_back(P);
+            pool_standardise(P, sub.data(), mean, nv);
+            pools.push_back(P);
             pool_units.emplace_back();
         }
-        GUnit U{};
-        U.test_region = cv ? u : 1;
-        U.train_mask = cv ? (((R >= 64) ? ~0ull : ((1ull << R) - 1ull)) & ~(1ull << u)) : 1ull;
-        U.N = (int32_t)ntrain; U.nq = (int32_t)ntest;
-        U.lognorm = m.lognorm;
-        for (int i = 0; i < nv * nv; ++i) U.W[i] = m.W[i];
-        for (int i = 0; i < nv; ++i) U.mu[i] = m.mu[i];
-        U.sum_slot = slot;
-        gb.pools[pi].test_unit[U.test_region] = (int32_t)pool_units[pi].size();
+        const GUnit U = group_unit(cv, R, u, m, nv, ntrain, ntest, slot);
+        pools[pi].test_unit[U.test_region] = (int32_t)pool_units[pi].size();
         pool_units[pi].push_back(U);
     };
     // the parts this call evaluates (scoring_internal.hpp): all of them, or those dealt to one rank of a job
@@ -1089,19 +1067,13 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
                     hb->rcols.insert(hb->rcols.end(), v, v + nv);
                 }
                 if (elig[(size_t)c * 2 + which]) {   // evaluated with the candidate's other grouped slices, after the loops
-                    group_unit(c, u, which, m, v, colidx, nv, tr->N, te->N, term.slot);
+                    add_unit(c, u, which, m, v, colidx, nv, tr->N, te->N, term.slot);
                     ++sd->kde_sweeps;
                     continue;
                 }
-                const KdePackBytes pb = kde_pack_bytes(m.fdtype(), m.dm, false, tr->N);
                 LaneSwitch lane(ctx, (int)(issued++ % (size_t)lanes));   // before the lane's scratch is touched
-                ctx->scratch_train.reserve(align(pb.apack) + align(pb.nxpack) + 256);
-                char* arena = ctx->scratch_train.p;
-                m.Apack = arena;
-                m.nxpack = arena + align(pb.apack);
-                m.Axpack = nullptr;
-                kde_pack_train(ctx, m, t, v, tr_row0, tr_n0, tr_row1, g.rows.p, /*prune=*/true, dmax ? dmax + term.slot : nullptr);
-                kde_eval_enqueue(ctx, m, t, v, te0, te->N, nullptr, dsums.p + term.slot, g.rows.p);
+                enqueue_term_chain(ctx, m, t, v, TermRows{tr_row0, tr_n0, tr_row1, te0, te->N}, g.rows.p, dsums.p + term.slot,
+                                   dmax ? dmax + term.slot : nullptr, /*precise=*/false);
                 ++sd->kde_sweeps;
             }
             if (sl.joint.slot == -2 || sl.marg.slot == -2) continue;
@@ -1109,13 +1081,7 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
         }
     }
     if (node_type != PBN_NODE_CKDE) return acc;
-    for (size_t pi = 0; pi < gb.pools.size(); ++pi) {   // the candidate's pools behind the batch's
-        gb.pools[pi].unit0 = (int32_t)hb->gb.units.size();
-        gb.pools[pi].nunits = (int32_t)pool_units[pi].size();
-        hb->gb.units.insert(hb->gb.units.end(), pool_units[pi].begin(), pool_units[pi].end());
-        hb->gb.pools.push_back(gb.pools[pi]);
-        hb->pool_bytes += kde_group_pool_bytes(hb->gb, hb->gb.pools.back());
-    }
+    append_pools(hb->gb, pools, pool_units, &hb->pool_bytes);   // the candidate's pools behind the batch's
     if (hb->pool_bytes >= kde_group_arena_budget()) hb->kick();   // an arena-full: one chain's worth
     HybridBatch::Job job{std::move(slices), parts != nullptr, parts ? *parts : HybridParts{0, 0, nullptr}, sink != nullptr, sink ? *sink : HybridSink{nullptr, {}}};
     hb->jobs.push_back(std::move(job));

@@ -28,7 +28,6 @@
 
 #include "common.hpp"
 #include "hostmath.hpp"
-#include "kde_group.hpp"
 #include "kde_model.hpp"
 #include "scoring_internal.hpp"
 #include "stats_kernels.hpp"
@@ -776,558 +775,270 @@ int pbn_lg_cdf(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t
     return lg_eval(t, cols, d, row0, n, beta, variance, out, nullptr, 1);
 }
 
-// `want` (nullable, per candidate): 0 = the local score; 1 / 2 = only the joint / only the marginal CKDE term of the candidate, summed
-// over the regions (pbn_score_terms)
-// `only_region` (nullable, per candidate; pbn_score_term_regions): >= 0 = that region's contribution alone (a CV fold; 0 for the hold-out score)
-// `parts_rank` / `parts_world` / `parts_out` (pbn_score_batch_parts): hybrid CKDE candidates evaluated on one rank's parts only, per-part sums to
-// parts_out[c * PBN_HYBRID_PARTS ...]
-static int score_batch_impl(pbn_scoredata* sd, int kind, int n_cand, const int* var, const int* node_type, const int* par_off,
-                            const int* parents, const double* params, int n_params, double* out, const int* want,
-                            int parts_rank = 0, int parts_world = 0, double* parts_out = nullptr, const int* only_region = nullptr) {
-    return guarded(mu_of(sd), [&] {
-        if (!sd || !var || !par_off || !out) throw invalid_error("pbn_score_batch: null argument");
-        pbn_ctx* ctx = sd->ctx;
-        if (sd->partial) throw invalid_error("pbn_score_batch: row-sharded score data needs pbn_scoredata_moments(set) first");
-        HIP_CHECK(hipSetDevice(ctx->device));
-        if ((kind == PBN_SCORE_CVLIK) && sd->k <= 0) throw invalid_error("pbn_score_batch: score data has no CV folds");
-        if ((kind == PBN_SCORE_HOLDOUT) && sd->n_hold <= 0) throw invalid_error("pbn_score_batch: score data has no hold-out split");
-        const pbn_table* t = sd->table();
-        // The set-function cache and the local-score memo grow by one entry per (region, configuration, term) and per hybrid
-        // candidate (~150 B a node): a long search over hybrid candidates would take gigabytes.  Both are pure accelerators -
-        // beyond PBN_SCORE_CACHE_ENTRIES entries (default 2^21, ~300 MB) they start over, at a batch boundary (no entry of
-        // the batch being assembled is lost).
-        static const size_t cache_budget = (size_t)std::max(1ll, knob_ll("PBN_SCORE_CACHE_ENTRIES", 1ll << 21));
-        if (sd->kde_cache.size() > cache_budget) { sd->kde_cache.clear(); ++sd->cache_resets; }
-        // (term_total is trimmed in pbn_score_terms_put only: every rank of a job reaches that call with the same state, whereas a rank
-        //  whose dealt list is empty skips the evaluation call - trimming here would let the ranks' "missing" lists drift apart)
-        if (sd->score_memo.size() > cache_budget) { sd->score_memo.clear(); ++sd->cache_resets; }
-        // BGe parameters
-        double iss_mu = 1, iss_w = sd->n + 2;
-        int total_nodes = sd->n;
-        const double* nu = nullptr;
-        if (kind < PBN_SCORE_BIC || kind > PBN_SCORE_BDE) throw invalid_error("pbn_score_batch: unknown score kind");
-        if (kind == PBN_SCORE_BGE && sd->discrete_only) throw invalid_error("BGe is not defined for networks with discrete variables.");
-        // BDe: the imaginary sample size; the discrete candidates of the call (variable a dictionary column) are collected here, counted
-        // together - all their families in one device pass - and finished after the loop (hybrid.hip, family_counts.hip)
-        const double bde_iss = (kind == PBN_SCORE_BDE && n_params >= 1 && params) ? params[0] : 1.0;
-        if (kind == PBN_SCORE_BDE && !(bde_iss > 0)) throw invalid_error("BDe: the imaginary sample size must be positive");
-        std::vector<DiscreteCand> discrete;
-        if (kind == PBN_SCORE_BGE) {
-            if (n_params >= 1) iss_mu = params[0];
-            if (n_params >= 2) iss_w = params[1];
-            if (n_params >= 3) total_nodes = (int)params[2];
-            if (n_params >= 3 + sd->n) nu = params + 3;
-        }
-        struct Pending { int cand; int unit0; int units; };
-        std::vector<Pending> pending;
-        // hybrid CKDE candidates of this call go into one HybridBatch (hybrid.hip): enqueued as they come, finished together after the loop
-        const bool hybrid_batched = knob_int("PBN_HYBRID_BATCH", 1) != 0;   // (per call: the tests switch it)
-        std::unique_ptr<HybridBatch, void (*)(HybridBatch*) noexcept> hbatch(nullptr, hybrid_batch_end);
-        auto hybrid_batch = [&]() -> HybridBatch* {
-            if (!hybrid_batched) return nullptr;
-            if (!hbatch) hbatch.reset(hybrid_batch_begin(sd));
-            return hbatch.get();
-        };
-        int n_units = 0;
-        Stats train;
-        std::vector<int> cols;
-        std::vector<double> mu, sse, beta, H;
-        // Tables with nulls: the plain BIC / BGe candidates that involve a column with nulls, deduplicated by ordered column list, take their
-        // moments over the rows valid in all of their columns from ONE masked pass over the batch (masked_moments.hip) instead of a host
-        // loop over the rows, an upload and a gathered Gram each.  (More than 8 columns, or PBN_NULL_MOMENTS=0: the per-candidate path.)
-        std::map<std::vector<int>, size_t> masked_of;
-        std::vector<std::vector<MaskedMoments>> masked;
-        if (sd->has_nulls && (kind == PBN_SCORE_BIC || kind == PBN_SCORE_BGE) && masked_moments_on()) {
-            std::vector<MaskedUnit> units;
-            for (int c = 0; c < n_cand; ++c) {
-                const int p = par_off[c + 1] - par_off[c];
-                if (p + 1 > MASKED_MAX_COLS) continue;
-                cols.resize(p + 1);
-                cols[0] = var[c];
-                for (int i = 0; i < p; ++i) cols[i + 1] = parents[par_off[c] + i];
-                bool plain = true, involved = false;
-                for (int cc : cols) {
-                    plain = plain && cc >= 0 && cc < sd->n;   // (out of range: the loop below throws; discrete: hybrid.hip)
-                    involved = involved || (plain && !sd->valid[cc].empty());
-                }
-                if (!plain || !involved || masked_of.count(cols)) continue;
-                masked_of.emplace(cols, units.size());
-                units.push_back(MaskedUnit{cols, nullptr, 0, {}});
-            }
-            masked_moments(sd, units, masked);
-        }
-        // the gather list of a candidate's valid rows (DataFrame::combined_bitmap, dataset.cpp:208-235) -> sd->rows_dev
-        auto gather_rows = [&](const std::vector<int>& cs) {
-            const int64_t rows = (int64_t)sd->perm.size();
-            std::vector<int32_t> keep;
-            keep.reserve(rows);
-            for (int64_t r = 0; r < rows; ++r) {
-                bool ok = true;
-                for (int cc : cs) ok = ok && (sd->valid[cc].empty() || sd->valid[cc][r]);
-                if (ok) keep.push_back((int32_t)r);
-            }
-            sd->rows_dev.reserve(keep.size() + 16);
-            if (!keep.empty()) {
-                HIP_CHECK(hipMemcpyAsync(sd->rows_dev.p, keep.data(), keep.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-                HIP_CHECK(hipStreamSynchronize(ctx->stream));   // keep goes out of scope
-            }
-            return (int64_t)keep.size();
-        };
-        for (int c = 0; c < n_cand; ++c) {
-            const int p = par_off[c + 1] - par_off[c];
-            const int d = p + 1;
-            cols.resize(d);
-            cols[0] = var[c];
-            for (int i = 0; i < p; ++i) cols[i + 1] = parents[par_off[c] + i];
-            bool hybrid = false;
-            for (int cc : cols) {
-                if (cc < 0 || cc >= sd->n + sd->n_disc) throw invalid_error("pbn_score_batch: column out of range");
-                if (cc >= sd->n) hybrid = true;
-            }
-            const int nt = node_type ? node_type[c] : PBN_NODE_LG;
-            if (hybrid) {
-                // Likelihood scores of DiscreteAdaptator factors cost k x configurations sweeps / Gram passes each, and a
-                // hill-climb asks for the same (variable, type, parent SET) again and again: every RemoveArc cell is the
-                // local score the node had before that arc was added, every FlipArc cell's source side likewise.  They
-                // are remembered by parent set (score_hybrid evaluates the continuous parents in ascending order and the discrete
-                // ones in canonical order: the value does not depend on the order they were given in).  BIC stays out: bic_clg ties.
-                if (parts_out) {   // a share of the candidate: never memoised
-                    HybridParts hp{parts_rank, parts_world, parts_out + (size_t)c * PBN_HYBRID_PARTS};
-                    HybridSink sink{out + c, {}};
-                    out[c] = score_hybrid(sd, kind, cols[0], nt, cols.data() + 1, p, &hp, hybrid_batch(), &sink);
-                    continue;
-                }
-                const bool memo = score_memo_on() && !sd->force_precise && (kind == PBN_SCORE_CVLIK || kind == PBN_SCORE_HOLDOUT);   // (discrete factors too)
-                std::vector<int> key;
-                if (memo) {
-                    key.assign(cols.begin() + 1, cols.end());
-                    std::sort(key.begin(), key.end());
-                    key.insert(key.begin(), {kind, nt, cols[0]});
-                    auto it = sd->score_memo.find(key);
-                    if (it != sd->score_memo.end()) { out[c] = it->second; ++sd->memo_hits; continue; }
-                }
-                if (cols[0] >= sd->n) {
-                    check_discrete_candidate(sd, kind, nt, cols.data() + 1, p);
-                    discrete.push_back(DiscreteCand{cols[0], std::vector<int>(cols.begin() + 1, cols.end()), out + c, key});
-                    continue;
-                }
-                HybridSink sink{out + c, key};   // (key empty without the memo)
-                bool deferred = false;
-                out[c] = score_hybrid(sd, kind, cols[0], nt, cols.data() + 1, p, nullptr, hybrid_batch(), &sink, &deferred);
-                if (memo && !deferred) sd->score_memo[key] = out[c];
-                continue;
-            }
-            if (kind == PBN_SCORE_BDE) throw invalid_error("BDe is defined for discrete variables with discrete parents only.");
-            mu.resize(d); sse.resize((size_t)d * d); beta.resize(d);
-            const Stats* full = &sd->all;
-            Stats gathered;
-            bool from_masked = false;   // `gathered` came from the masked pass: no gather list on the device yet
-            if (sd->has_nulls && (kind == PBN_SCORE_BIC || kind == PBN_SCORE_BGE)) {
-                bool involved = false;
-                for (int cc : cols) involved = involved || !sd->valid[cc].empty();
-                const auto mit = involved ? masked_of.find(cols) : masked_of.end();
-                if (mit != masked_of.end()) {
-                    masked_to_stats(sd, cols.data(), d, masked[mit->second][0], gathered);
-                    full = &gathered;
-                    from_masked = true;
-                } else if (involved) {
-                    // rows valid in every involved column (DataFrame::combined_bitmap, dataset.cpp:208-235)
-                    const int64_t rows = (int64_t)sd->perm.size();
-                    std::vector<int32_t> keep;
-                    keep.reserve(rows);
-                    for (int64_t r = 0; r < rows; ++r) {
-                        bool ok = true;
-                        for (int cc : cols) ok = ok && (sd->valid[cc].empty() || sd->valid[cc][r]);
-                        if (ok) keep.push_back((int32_t)r);
-                    }
-                    if (d > 64) throw invalid_error("pbn_score_batch: more than 64 columns in one candidate");
-                    sd->rows_dev.reserve(keep.size() + 16);
-                    if (!keep.empty())
-                        HIP_CHECK(hipMemcpyAsync(sd->rows_dev.p, keep.data(), keep.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-                    std::vector<double> S(d), G((size_t)d * d);
-                    if (!keep.empty())
-                        gram_raw(t, cols.data(), d, 0, (int64_t)keep.size(), sd->rows_dev.p, sd->shift_dev.p, S.data(), G.data());
-                    gathered.zero(sd->n);
-                    gathered.N = (int64_t)keep.size();
-                    for (int i = 0; i < d; ++i) {
-                        gathered.S[cols[i]] = S[i];
-                        for (int j = 0; j < d; ++j) gathered.G[cols[i] + (size_t)cols[j] * sd->n] = G[i + (size_t)j * d];
-                    }
-                    full = &gathered;
-                }
-            }
-            if (kind == PBN_SCORE_BIC) {
-                if (nt != PBN_NODE_LG) throw invalid_error("BIC: only LinearGaussianCPD node types are implemented on device");
-                subset_moments(sd, *full, cols.data(), d, mu.data(), sse.data());
-                bool suspect = false;
-                double v = lg_fit(full->N, p, mu.data(), sse.data(), beta.data(), &suspect);
-                if (suspect && lg_guard_on() && d <= 16) {   // nearly collinear parents / nearly exact fit: double-double refit
-                    if (from_masked && gather_rows(cols) != full->N) throw device_error("masked moments: the pass and the validity masks disagree on the valid rows");
-                    if (full == &gathered) v = lg_fit_accurate(t, cols.data(), d, 0, full->N, 0, full->N, sd->rows_dev.p, beta.data());
-                    else v = lg_fit_accurate(t, cols.data(), d, 0, sd->n_cv, 0, sd->n_cv, nullptr, beta.data());
-                }
-                out[c] = bic_lg(full->N, p, v);
-                continue;
-            }
-            if (kind == PBN_SCORE_BGE) {
-                out[c] = bge_score(sd, *full, cols.data(), p, iss_mu, iss_w, total_nodes, nu);
-                continue;
-            }
-            const bool cv = kind == PBN_SCORE_CVLIK;
-            const int units = cv ? sd->k : 1;
-            if (nt == PBN_NODE_LG) {
-                double acc = 0.0;
-                for (int f = 0; f < units; ++f) {
-                    const Stats* tr = &sd->all;
-                    const Stats* te = &sd->hold;
-                    if (cv) { stats_minus(sd->all, sd->fold[f], train); tr = &train; te = &sd->fold[f]; }
-                    subset_moments(sd, *tr, cols.data(), d, mu.data(), sse.data());
-                    bool suspect = false;
-                    double v = lg_fit(tr->N, p, mu.data(), sse.data(), beta.data(), &suspect);
-                    if (suspect && lg_guard_on() && d <= 16) {
-                        if (cv) v = lg_fit_accurate(t, cols.data(), d, 0, sd->limits[f], sd->limits[f + 1], tr->N, nullptr, beta.data());
-                        else v = lg_fit_accurate(t, cols.data(), d, 0, sd->n_cv, 0, sd->n_cv, nullptr, beta.data());
-                        // and the test fold's log-likelihood from its rows, as the reference evaluates it
-                        const int64_t te0 = cv ? sd->limits[f] : sd->n_cv;
-                        acc += lg_slogl_from_rows(t, cols.data(), d, te0, te->N, nullptr, beta.data(), v);
-                        continue;
-                    }
-                    acc += lg_slogl_from_moments(sd, *te, cols.data(), p, beta.data(), v);
-                }
-                out[c] = acc;
-                continue;
-            }
-            if (nt != PBN_NODE_CKDE) throw invalid_error("pbn_score_batch: unknown node type");
-            // CKDE: enqueue fit + slogl per unit from scratch arenas
-            ctx->scratch_misc.reserve(1);  // touched by kde_eval_enqueue
-            pending.push_back({c, n_units, units});
-            n_units += units;
-        }
-        hybrid_batch_flush(hbatch.get());   // (before the plain CKDE units below take the context's result slots)
-        hbatch.reset();
-        score_discrete_batch(sd, kind, bde_iss, discrete);
-        if (!pending.empty()) {
-            // ---- CKDE likelihood units through the set-function cache ------------------------------------------------
-            // slogl of a CKDE on a test region = A(vars, d) - A(parents, d), with A(S, m) = sum_q log KDE(S) under the
-            // bandwidth rule evaluated for m dimensions on the region's training rows: the marginal of the reference
-            // (CKDE.hpp:186-199) is the KDE of the parents with H[1:,1:], and H = k(N, d) cov, so both terms are
-            // functions of a variable SET (and m, and the region) only.  A({s,t}, 2) serves s -> t and t -> s,
-            // A({s}, 2) serves every child of s: each is swept once and remembered for the life of the score data.
-            // Neither term known: one fused sweep yields both; one known: a plain sweep of the other.
-            struct Term { double value = 0; int slot = -1; };           // cached value, or slot in the device sums
-            std::map<std::vector<int>, int> scheduled;                    // key -> slot (this batch)
-            std::vector<std::vector<int>> slot_key;
-            auto key_of = [&](int region, int m, const int* v, int nv) {
-                std::vector<int> k(v, v + nv);
-                std::sort(k.begin(), k.end());
-                k.insert(k.begin(), {region, m});
-                return k;
-            };
-            const bool precise_all = sd->force_precise && sd->dtype == PBN_F64;
-            auto lookup = [&](const std::vector<int>& key, Term& t) {
-                auto it = sd->kde_cache.find(key);
-                if (!precise_all && it != sd->kde_cache.end()) { t.value = it->second; return true; }
-                auto is = scheduled.find(key);
-                if (is != scheduled.end()) { t.slot = is->second; return true; }
-                return false;
-            };
-            auto new_slot = [&](const std::vector<int>& key) {
-                const int slot = (int)slot_key.size();
-                slot_key.push_back(key);
-                scheduled[key] = slot;
-                return slot;
-            };
-            struct Unit { int cand; Term joint, marg; bool has_marg; int want; };
-            // a term whose total over the regions was installed (pbn_score_terms_put): the total stands for region 0, the others add 0
-            auto lookup_total = [&](int m, const int* v, int nv, int region_index, Term& t) {
-                if (sd->term_total.empty() || only_region || precise_all) return false;   // (one region of a term: never its total)
-                std::vector<int> k(v, v + nv);
-                std::sort(k.begin(), k.end());
-                k.insert(k.begin(), {kind, m});   // a validated score asks one handle for both kinds
-                auto it = sd->term_total.find(k);
-                if (it == sd->term_total.end()) return false;
-                t.value = region_index == 0 ? it->second : 0.0;
-                return true;
-            };
-            std::vector<Unit> units_v;
-            struct Work { int cand, f, mode, slot_j, slot_m; };          // mode 1 joint term, 2 marginal term
-            std::vector<Work> work;
-            const bool cv = kind == PBN_SCORE_CVLIK;
-            // Neither term known: two plain sweeps (joint, marginal), each pruned on its own box.  (The fused joint + marginal sweep costs
-            // exactly two sweeps' worth of exponentials anyway - they, not the MFMAs, are the cost - and under tile pruning it can only
-            // prune on the marginal box: C3 16-21 ms fused against 2 x 7 ms plain per fold.  The engine dropped it in round 2; the
-            // stand-alone CKDE handles keep the fused kernel.)
-            for (const Pending& pd : pending) {
-                const int c = pd.cand;
-                const int p = par_off[c + 1] - par_off[c], d = p + 1;
-                cols.resize(d);
-                cols[0] = var[c];
-                for (int i = 0; i < p; ++i) cols[i + 1] = parents[par_off[c] + i];
-                for (int f = 0; f < pd.units; ++f) {
-                    if (only_region && only_region[c] >= 0 && f != only_region[c]) continue;
-                    const int region = cv ? f : sd->k;                    // fold index, or the hold-out region
-                    const int wnt = want ? want[c] : 0;
-                    Unit u{c, {}, {}, wnt == 3 || (p > 0 && wnt != 1), wnt};
-                    const std::vector<int> kj = key_of(region, d, cols.data(), d);
-                    const bool have_j = wnt >= 2 || lookup_total(d, cols.data(), d, f, u.joint) || lookup(kj, u.joint);
-                    bool have_m = true;
-                    std::vector<int> km;
-                    if (wnt == 3) {   // a marginal TERM (pbn_score_terms): all d columns of the pseudo-candidate under the rule for d + 1 dimensions, no child
-                        km = key_of(region, d + 1, cols.data(), d);
-                        have_m = lookup_total(d + 1, cols.data(), d, f, u.marg) || lookup(km, u.marg);
-                    } else if (u.has_marg) { km = key_of(region, d, cols.data() + 1, p); have_m = lookup_total(d, cols.data() + 1, p, f, u.marg) || lookup(km, u.marg); }
-                    if (!have_j && !have_m) {
-                        u.joint.slot = new_slot(kj); u.marg.slot = new_slot(km);
-                        work.push_back({c, f, 1, u.joint.slot, -1});
-                        work.push_back({c, f, 2, -1, u.marg.slot});
-                    } else if (!have_j) {
-                        u.joint.slot = new_slot(kj);
-                        work.push_back({c, f, 1, u.joint.slot, -1});
-                    } else if (!have_m) {
-                        u.marg.slot = new_slot(km);
-                        work.push_back({c, f, 2, -1, u.marg.slot});
-                    }
-                    units_v.push_back(u);
-                }
-            }
-            const size_t nslots = slot_key.size();
-            // fp32 tables: behind the sums, one slot per sum for |z|^2 of the evaluation's farthest whitened training row (the pack
-            // kernels report it): an evaluation that kde_wants_widening() flags is redone on fp64 fragments (KdeModel::widen) before its
-            // value is used.  The choice is a function of that evaluation alone - nothing is remembered per variable set, so the double
-            // a (term, region) gets does not depend on what this process evaluated before or on how a job dealt its terms
-            static const bool check_after = PBN_TUNE(F32_CHECK, 1) != 0;   // 0: measurement only
-            const bool f32 = sd->dtype == PBN_F32 && check_after;
-            ctx->scratch_sums.reserve(std::max<size_t>(1, 2 * nslots));   // (grow-only: no hipMalloc / hipFree per batch)
-            struct { double* p; } dsums{ctx->scratch_sums.p};
-            HIP_CHECK(hipMemsetAsync(dsums.p, 0, std::max<size_t>(1, 2 * nslots) * sizeof(double), ctx->stream));
-            double* const dmax = f32 ? dsums.p + nslots : nullptr;
-            auto align = [](size_t x) { return (x + 255) / 256 * 256; };
-            // host side of one evaluation: columns, training moments of the region, bandwidth, whitening (KdeModel without packs)
-            struct Prep { KdeModel m; std::vector<int> use; int64_t row0, n0, row1, te0, te_n, ntrain; };
-            auto prepare = [&](const Work& w, Prep& pr) {
-                const int c = w.cand;
-                const int p = par_off[c + 1] - par_off[c], d = p + 1;
-                cols.resize(d);
-                cols[0] = var[c];
-                for (int i = 0; i < p; ++i) cols[i + 1] = parents[par_off[c] + i];
-                mu.resize(d); sse.resize((size_t)d * d); H.resize((size_t)d * d);
-                const Stats* tr = &sd->all;
-                pr.row0 = 0; pr.n0 = sd->n_cv; pr.row1 = 0; pr.te0 = sd->n_cv; pr.te_n = sd->n_hold;
-                if (cv) {
-                    stats_minus(sd->all, sd->fold[w.f], train);
-                    tr = &train;
-                    pr.n0 = sd->limits[w.f]; pr.row1 = sd->limits[w.f + 1];
-                    pr.te0 = sd->limits[w.f]; pr.te_n = sd->limits[w.f + 1] - sd->limits[w.f];
-                }
-                pr.ntrain = tr->N;
-                // The plain terms are evaluated over their columns in ASCENDING order, whatever the candidate's orientation and the order
-                // of its parents: A(S, m) is then a function of the set alone down to the last bit - the value a term gets does not
-                // depend on which candidate asked for it first, and a job that evaluates the terms on other ranks (pbn_score_terms)
-                // computes the very same doubles.  (H = k(N, d) cov: the bandwidth of a subset is the sub-block of the set's.)
-                const int var0 = cols[0];
-                std::sort(cols.begin(), cols.end());
-                subset_moments(sd, *tr, cols.data(), d, mu.data(), sse.data());
-                const double inv = 1.0 / (double)(tr->N - 1);
-                for (auto& x : sse) x *= inv;  // covariance
-                if (w.mode == 2 && want && want[c] == 3) {
-                    // a marginal term evaluated for itself (a job that deals the terms to its ranks): KDE of these d columns with
-                    // H = k(N, d + 1) cov - the block the joint bandwidth of ANY child over them would have (H = k(N, dims) cov for the
-                    // library selectors), bit for bit, without a child whose own degeneracy (a constant column ...) has nothing to do
-                    // with the term.  The pre-checks of the selector stand on the term's own columns; the real candidate's set is
-                    // checked by its joint term.
-                    bandwidth_full_block(sd->selector, sse.data(), d, d + 1, tr->N, sd->dtype, H.data());
-                    kde_prepare(pr.m, sd->dtype, d, tr->N, H.data(), PBN_BW_FULL, false, mu.data());
-                    pr.use = cols;
-                    return;
-                }
-                bandwidth_from_cov(sd->selector, PBN_BW_FULL, sse.data(), d, tr->N, sd->dtype, H.data());
-                if (w.mode == 2) {            // KDE of the parents with the bandwidth block of the parents
-                    const int vp = (int)(std::find(cols.begin(), cols.end(), var0) - cols.begin());
-                    std::vector<double> Hm((size_t)p * p), mum((size_t)p);
-                    pr.use.clear();
-                    for (int j = 0, jj = 0; j < d; ++j) {
-                        if (j == vp) continue;
-                        for (int i = 0, ii = 0; i < d; ++i) {
-                            if (i == vp) continue;
-                            Hm[ii + (size_t)jj * p] = H[i + (size_t)j * d];
-                            ++ii;
-                        }
-                        mum[jj] = mu[j];
-                        pr.use.push_back(cols[j]);
-                        ++jj;
-                    }
-                    kde_prepare(pr.m, sd->dtype, p, tr->N, Hm.data(), PBN_BW_FULL, false, mum.data());
-                } else {
-                    kde_prepare(pr.m, sd->dtype, d, tr->N, H.data(), PBN_BW_FULL, false, mu.data());
-                    pr.use = cols;
-                }
-            };
-            // ---- grouped evaluation (kde_group.hip): the plain terms whose shape qualifies are collected into pools - one per
-            // variable set, its units the regions asked for - and evaluated by ONE launch chain per batch of pools ---------------
-            struct Batch { GroupBatch gb; std::vector<std::vector<GUnit>> pool_units; std::map<std::vector<int>, int> pool_of; };   // pool_of: [m, sorted columns...] -> pool
-            Batch bt[1];
-            std::vector<char> grouped(work.size(), 0);
-            const int R = cv ? sd->k : 2;
-            const int64_t min_train = cv ? sd->n_cv - (sd->limits[1] - sd->limits[0]) : sd->n_cv;
-            for (size_t wi = 0; wi < work.size(); ++wi) {
-                const Work& w = work[wi];
-                const int p = par_off[w.cand + 1] - par_off[w.cand];
-                const bool own_term = w.mode == 2 && want && want[w.cand] == 3;   // marginal term over all p + 1 columns, rule for p + 2
-                const int dims = own_term ? p + 1 : (w.mode == 2 ? p : p + 1);
-                if (precise_all || !kde_group_applies(sd->dtype, dims, min_train, R)) continue;   // (precise: one chain per term, per-row accuracy)
-                Prep pr;
-                prepare(w, pr);
-                std::vector<int> key(pr.use);
-                std::sort(key.begin(), key.end());
-                Batch& B = bt[0];
-                GroupBatch& gb = B.gb;
-                std::vector<std::vector<GUnit>>& pool_units = B.pool_units;
-                key.insert(key.begin(), own_term ? p + 2 : p + 1);
-                auto it = B.pool_of.find(key);
-                int pi;
-                if (it == B.pool_of.end()) {
-                    pi = (int)gb.pools.size();
-                    B.pool_of[key] = pi;
-                    GPool P{};
-                    P.rows = nullptr; P.row_base = 0;
-                    P.n = (int32_t)(cv ? sd->n_cv : sd->n_cv + sd->n_hold);
-                    P.R = R; P.d = dims; P.kd = std::min(dims, 4);
-                    if (cv) for (int f = 0; f <= sd->k; ++f) P.rb[f] = sd->limits[f];
-                    else { P.rb[0] = 0; P.rb[1] = (int32_t)sd->n_cv; P.rb[2] = (int32_t)(sd->n_cv + sd->n_hold); }
-                    for (int r = 0; r < PBN_GROUP_MAX_R; ++r) P.test_unit[r] = -1;
-                    for (int i = 0; i < dims; ++i) P.cols[i] = pr.use[i];
-                    // pool-level standardisation for the Morton keys: L^-1 of the covariance of the whole CV / training region
-                    std::vector<double> gm(dims), gs((size_t)dims * dims), L((size_t)dims * dims), Li((size_t)dims * dims);
-                    subset_moments(sd, sd->all, pr.use.data(), dims, gm.data(), gs.data());
-                    for (auto& x : gs) x /= (double)std::max<int64_t>(1, sd->all.N - 1);
-                    if (!hm::cholesky(gs.data(), dims, L.data())) {   // the keys only order the rows: fall back to the diagonal
-                        std::fill(L.begin(), L.end(), 0.0);
-                        for (int i = 0; i < dims; ++i) L[i + (size_t)i * dims] = std::sqrt(std::max(gs[i + (size_t)i * dims], 1e-300));
-                    }
-                    hm::lower_inverse(L.data(), dims, Li.data());
-                    for (int i = 0; i < dims; ++i) {
-                        P.mug[i] = gm[i];
-                        for (int j = 0; j < dims; ++j) P.Wg[i * dims + j] = j <= i ? Li[i + (size_t)j * dims] : 0.0;
-                    }
-                    gb.pools.push_back(P);
-                    pool_units.emplace_back();
-                } else {
-                    pi = it->second;
-                }
-                GUnit U{};
-                U.test_region = cv ? w.f : 1;
-                U.train_mask = cv ? (((R >= 64) ? ~0ull : ((1ull << R) - 1ull)) & ~(1ull << w.f)) : 1ull;
-                U.N = (int32_t)pr.ntrain; U.nq = (int32_t)pr.te_n;
-                U.lognorm = pr.m.lognorm;
-                for (int i = 0; i < dims * dims; ++i) U.W[i] = pr.m.W[i];
-                for (int i = 0; i < dims; ++i) U.mu[i] = pr.m.mu[i];
-                U.sum_slot = w.mode == 2 ? w.slot_m : w.slot_j;
-                gb.pools[pi].test_unit[U.test_region] = (int32_t)pool_units[pi].size();
-                pool_units[pi].push_back(U);
-                grouped[wi] = 1;
-            }
-            for (Batch& B : bt)
-                for (size_t pi = 0; pi < B.gb.pools.size(); ++pi) {
-                    B.gb.pools[pi].unit0 = (int32_t)B.gb.units.size();
-                    B.gb.pools[pi].nunits = (int32_t)B.pool_units[pi].size();
-                    B.gb.units.insert(B.gb.units.end(), B.pool_units[pi].begin(), B.pool_units[pi].end());
-                }
-            size_t n_legacy = 0;
-            for (char gflag : grouped) n_legacy += gflag ? 0 : 1;
-            // independent evaluations alternate between the context's two issue lanes (common.hpp)
-            const int lanes = (n_legacy > 1 && !ctx->profiling) ? score_lanes(t->n_rows) : 1;
-            if (lanes > 1) { ctx->ensure_lanes(lanes - 1); ctx->lanes_wait_for_stream(lanes - 1); }
-            if (!bt[0].gb.pools.empty()) kde_group_run(ctx, t, bt[0].gb, dsums.p, dmax, false);
-            // one evaluation through its own launch chain (shapes the grouped path does not take; the redo of a flagged evaluation)
-            auto run_single = [&](const Work& w, bool force64, bool precise = false) {
-                Prep pr;
-                prepare(w, pr);
-                KdeModel& m = pr.m;
-                const int* use_cols = pr.use.data();
-                const int slot = w.mode == 2 ? w.slot_m : w.slot_j;
-                if (f32 && force64) kde_widen(m);
-                const KdePackBytes pb = kde_pack_bytes(m.fdtype(), m.dm, m.cond, m.N);
-                ctx->scratch_train.reserve(pb.apack + pb.nxpack + pb.axpack + 768);
-                char* base = ctx->scratch_train.p;
-                m.Apack = base;
-                m.nxpack = base + align(pb.apack);
-                m.Axpack = m.cond ? base + align(pb.apack) + align(pb.nxpack) : nullptr;
-                kde_pack_train(ctx, m, t, use_cols, pr.row0, pr.n0, pr.row1, nullptr, /*prune=*/true, dmax ? dmax + slot : nullptr);
-                kde_eval_enqueue(ctx, m, t, use_cols, pr.te0, pr.te_n, nullptr, dsums.p + slot, nullptr, nullptr, precise);
-            };
-            size_t wi = 0, li = 0;
-            for (const Work& w : work) {
-                if (grouped[wi++]) continue;
-                LaneSwitch lane(ctx, (int)(li++ % (size_t)lanes));
-                run_single(w, false, precise_all);
-            }
-            std::vector<double> hs(std::max<size_t>(1, 2 * nslots));
-            if (lanes > 1) ctx->sync_lanes(lanes - 1);
-            if (nslots) HIP_CHECK(hipMemcpyAsync(hs.data(), dsums.p, (f32 ? 2 : 1) * nslots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            if (f32 && nslots) {
-                // check-after: evaluations whose training rows reach beyond what fp32 fragments hold (2^-24 max|z|^2 above the threshold of
-                // kde_wants_widening) are redone on fp64 fragments
-                std::vector<const Work*> redo;
-                for (const Work& w : work) {
-                    const int slot = w.mode == 2 ? w.slot_m : w.slot_j;
-                    // the criterion follows the fragments' layout, i.e. the number of variables of the term: p + 1 for a joint term, p or (a
-                    // marginal TERM of pbn_score_terms) p + 1 for a marginal one - the stricter of the two there
-                    const int pw = par_off[w.cand + 1] - par_off[w.cand];
-                    const double far2 = hs[nslots + (size_t)slot];
-                    if (kde_wants_widening(far2, pw + 1) || (w.mode == 2 && kde_wants_widening(far2, pw))) redo.push_back(&w);
-                }
-                if (!redo.empty()) {
-                    for (const Work* w : redo) {
-                        Prep pr;
-                        prepare(*w, pr);
-                        const int slot = w->mode == 2 ? w->slot_m : w->slot_j;
-                        HIP_CHECK(hipMemsetAsync(dsums.p + slot, 0, sizeof(double), ctx->stream));
-                        run_single(*w, true);
-                    }
-                    HIP_CHECK(hipMemcpyAsync(hs.data(), dsums.p, nslots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    sd->kde_sweeps += (int64_t)redo.size();
-                }
-            }
-            if (sd->dtype == PBN_F64 && nslots) {
-                // fp64 tables: a term whose sum over its test rows is a cancellation to ~0 (kde_sum_needs_precision: the sum-only sweeps'
-                // absolute error budget would exceed 5e-7 of it) is evaluated once more at the accuracy of the per-row path
-                std::vector<const Work*> redo;
-                for (const Work& w : work) {
-                    const int slot = w.mode == 2 ? w.slot_m : w.slot_j;
-                    const int64_t nq = cv ? sd->limits[w.f + 1] - sd->limits[w.f] : sd->n_hold;
-                    if (kde_sum_needs_precision(hs[(size_t)slot], nq)) redo.push_back(&w);
-                }
-                if (!redo.empty()) {
-                    for (const Work* w : redo) {
-                        const int slot = w->mode == 2 ? w->slot_m : w->slot_j;
-                        HIP_CHECK(hipMemsetAsync(dsums.p + slot, 0, sizeof(double), ctx->stream));
-                        run_single(*w, false, /*precise=*/true);
-                    }
-                    HIP_CHECK(hipMemcpyAsync(hs.data(), dsums.p, nslots * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    sd->kde_sweeps += (int64_t)redo.size();
-                    sd->precise_redos += (int64_t)redo.size();
-                }
-            }
-            ctx->drop_staged();
-            for (size_t i = 0; i < nslots; ++i) sd->kde_cache[slot_key[i]] = hs[i];
-            sd->kde_sweeps += (int64_t)work.size();
-            // a candidate = (its joint terms added in region order) - (its marginal terms added in region order): the two sums are
-            // what pbn_score_terms hands out, so a job that computes the terms on different ranks assembles the same doubles
-            std::vector<double> jsum((size_t)n_cand, 0.0), msum((size_t)n_cand, 0.0);
-            for (const Unit& u : units_v) {
-                if (u.want < 2) jsum[u.cand] += u.joint.slot >= 0 ? hs[u.joint.slot] : u.joint.value;
-                if (u.has_marg) msum[u.cand] += u.marg.slot >= 0 ? hs[u.marg.slot] : u.marg.value;
-            }
-            for (const Pending& pd : pending) {
-                const int wnt = want ? want[pd.cand] : 0;
-                out[pd.cand] = wnt >= 2 ? msum[pd.cand] : (wnt == 1 ? jsum[pd.cand] : jsum[pd.cand] - msum[pd.cand]);
-            }
-        }
-    });
+}  // extern "C"
+
+// ---- the batch engine: score_batch_body checks the call and sends every candidate to one of score_hybrid_candidate (a discrete column
+// involved), score_gaussian_candidate (BIC, BGe, LinearGaussian likelihood) or the list of plain CKDE candidates that score_ckde_terms
+// (score_terms.hip) evaluates together after the loop.  DESIGN.md 3.5 has the map. ----
+namespace pbn {
+namespace score {
+
+size_t score_cache_budget() {
+    static const size_t v = (size_t)std::max(1ll, knob_ll("PBN_SCORE_CACHE_ENTRIES", 1ll << 21));
+    return v;
 }
+
+void candidate_cols(const BatchArgs& a, int c, std::vector<int>& cols) {
+    const int p = a.n_parents(c);
+    cols.resize(p + 1);
+    cols[0] = a.var[c];
+    for (int i = 0; i < p; ++i) cols[i + 1] = a.parents[a.par_off[c] + i];
+}
+
+namespace {
+
+// the gather list of a candidate's valid rows (DataFrame::combined_bitmap, dataset.cpp:208-235) -> sd->rows_dev
+int64_t gather_rows(pbn_scoredata* sd, const std::vector<int>& cs) {
+    const int64_t rows = (int64_t)sd->perm.size();
+    std::vector<int32_t> keep;
+    keep.reserve(rows);
+    for (int64_t r = 0; r < rows; ++r) {
+        bool ok = true;
+        for (int cc : cs) ok = ok && (sd->valid[cc].empty() || sd->valid[cc][r]);
+        if (ok) keep.push_back((int32_t)r);
+    }
+    sd->rows_dev.reserve(keep.size() + 16);
+    if (!keep.empty()) {
+        HIP_CHECK(hipMemcpyAsync(sd->rows_dev.p, keep.data(), keep.size() * sizeof(int32_t), hipMemcpyHostToDevice, sd->ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(sd->ctx->stream));   // keep goes out of scope
+    }
+    return (int64_t)keep.size();
+}
+
+// Tables with nulls: the plain BIC / BGe candidates that involve a column with nulls, deduplicated by ordered column list, take their
+// moments over the rows valid in all of their columns from ONE masked pass over the batch (masked_moments.hip) instead of a host
+// loop over the rows, an upload and a gathered Gram each.  (More than 8 columns, or PBN_NULL_MOMENTS=0: the per-candidate path.)
+struct MaskedPlan {
+    std::map<std::vector<int>, size_t> unit_of;   // ordered column list -> unit of the pass
+    std::vector<std::vector<MaskedMoments>> moments;
+};
+MaskedPlan masked_prepass(pbn_scoredata* sd, const BatchArgs& a, std::vector<int>& cols) {
+    MaskedPlan plan;
+    if (!sd->has_nulls || (a.kind != PBN_SCORE_BIC && a.kind != PBN_SCORE_BGE) || !masked_moments_on()) return plan;
+    std::vector<MaskedUnit> units;
+    for (int c = 0; c < a.n_cand; ++c) {
+        if (a.n_parents(c) + 1 > MASKED_MAX_COLS) continue;
+        candidate_cols(a, c, cols);
+        bool plain = true, involved = false;
+        for (int cc : cols) {
+            plain = plain && cc >= 0 && cc < sd->n;   // (out of range: the candidate loop throws; discrete: hybrid.hip)
+            involved = involved || (plain && !sd->valid[cc].empty());
+        }
+        if (!plain || !involved || plan.unit_of.count(cols)) continue;
+        plan.unit_of.emplace(cols, units.size());
+        units.push_back(MaskedUnit{cols, nullptr, 0, {}});
+    }
+    masked_moments(sd, units, plan.moments);
+    return plan;
+}
+
+// Moments of a BIC / BGe candidate over the rows valid in all of its columns -> `gathered` (true), or false when none of its columns has
+// nulls and sd->all serves.  From the masked plan where it holds the candidate (*from_masked: no gather list on the device yet), else
+// from a gather list of the valid rows (left in sd->rows_dev) and a gathered Gram.
+bool valid_row_moments(pbn_scoredata* sd, const std::vector<int>& cols, const MaskedPlan& plan, Stats& gathered, bool* from_masked) {
+    const int d = (int)cols.size();
+    bool involved = false;
+    for (int cc : cols) involved = involved || !sd->valid[cc].empty();
+    if (!involved) return false;
+    const auto mit = plan.unit_of.find(cols);
+    if (mit != plan.unit_of.end()) {
+        masked_to_stats(sd, cols.data(), d, plan.moments[mit->second][0], gathered);
+        *from_masked = true;
+        return true;
+    }
+    if (d > 64) throw invalid_error("pbn_score_batch: more than 64 columns in one candidate");
+    const int64_t kept = gather_rows(sd, cols);
+    std::vector<double> S(d), G((size_t)d * d);
+    if (kept > 0) gram_raw(sd->table(), cols.data(), d, 0, kept, sd->rows_dev.p, sd->shift_dev.p, S.data(), G.data());
+    gathered.zero(sd->n);
+    gathered.N = kept;
+    for (int i = 0; i < d; ++i) {
+        gathered.S[cols[i]] = S[i];
+        for (int j = 0; j < d; ++j) gathered.G[cols[i] + (size_t)cols[j] * sd->n] = G[i + (size_t)j * d];
+    }
+    return true;
+}
+
+struct BgeParams {   // iss_mu, iss_w, total_nodes, then optionally nu[n] (per table column)
+    double iss_mu, iss_w;
+    int total_nodes;
+    const double* nu;
+};
+
+// BIC, BGe and the CV / hold-out likelihood of a LinearGaussianCPD over continuous columns (s.cols): host arithmetic on the regions' moments
+double score_gaussian_candidate(pbn_scoredata* sd, int kind, int nt, const BgeParams& bge, const MaskedPlan& plan, ScoreScratch& s) {
+    const pbn_table* t = sd->table();
+    const std::vector<int>& cols = s.cols;
+    const int d = (int)cols.size(), p = d - 1;
+    s.mu.resize(d); s.sse.resize((size_t)d * d); s.beta.resize(d);
+    if (kind == PBN_SCORE_BIC || kind == PBN_SCORE_BGE) {
+        const Stats* full = &sd->all;
+        Stats gathered;
+        bool from_masked = false;
+        if (sd->has_nulls && valid_row_moments(sd, cols, plan, gathered, &from_masked)) full = &gathered;
+        if (kind == PBN_SCORE_BGE) return bge_score(sd, *full, cols.data(), p, bge.iss_mu, bge.iss_w, bge.total_nodes, bge.nu);
+        if (nt != PBN_NODE_LG) throw invalid_error("BIC: only LinearGaussianCPD node types are implemented on device");
+        subset_moments(sd, *full, cols.data(), d, s.mu.data(), s.sse.data());
+        bool suspect = false;
+        double v = lg_fit(full->N, p, s.mu.data(), s.sse.data(), s.beta.data(), &suspect);
+        if (suspect && lg_guard_on() && d <= 16) {   // nearly collinear parents / nearly exact fit: double-double refit
+            if (from_masked && gather_rows(sd, cols) != full->N) throw device_error("masked moments: the pass and the validity masks disagree on the valid rows");
+            if (full == &gathered) v = lg_fit_accurate(t, cols.data(), d, 0, full->N, 0, full->N, sd->rows_dev.p, s.beta.data());
+            else v = lg_fit_accurate(t, cols.data(), d, 0, sd->n_cv, 0, sd->n_cv, nullptr, s.beta.data());
+        }
+        return bic_lg(full->N, p, v);
+    }
+    const bool cv = kind == PBN_SCORE_CVLIK;
+    double acc = 0.0;
+    for (int f = 0; f < (cv ? sd->k : 1); ++f) {
+        const Stats* tr = &sd->all;
+        const Stats* te = &sd->hold;
+        if (cv) { stats_minus(sd->all, sd->fold[f], s.train); tr = &s.train; te = &sd->fold[f]; }
+        subset_moments(sd, *tr, cols.data(), d, s.mu.data(), s.sse.data());
+        bool suspect = false;
+        double v = lg_fit(tr->N, p, s.mu.data(), s.sse.data(), s.beta.data(), &suspect);
+        if (suspect && lg_guard_on() && d <= 16) {
+            if (cv) v = lg_fit_accurate(t, cols.data(), d, 0, sd->limits[f], sd->limits[f + 1], tr->N, nullptr, s.beta.data());
+            else v = lg_fit_accurate(t, cols.data(), d, 0, sd->n_cv, 0, sd->n_cv, nullptr, s.beta.data());
+            // and the test fold's log-likelihood from its rows, as the reference evaluates it
+            const int64_t te0 = cv ? sd->limits[f] : sd->n_cv;
+            acc += lg_slogl_from_rows(t, cols.data(), d, te0, te->N, nullptr, s.beta.data(), v);
+            continue;
+        }
+        acc += lg_slogl_from_moments(sd, *te, cols.data(), p, s.beta.data(), v);
+    }
+    return acc;
+}
+
+// hybrid CKDE candidates of a call go into one HybridBatch (hybrid.hip): begun with the first of them, enqueued as they come, finished
+// together after the candidate loop
+struct LazyHybridBatch {
+    pbn_scoredata* sd;
+    const bool on = knob_int("PBN_HYBRID_BATCH", 1) != 0;   // (per call: the tests switch it)
+    std::unique_ptr<HybridBatch, void (*)(HybridBatch*) noexcept> hb{nullptr, hybrid_batch_end};
+    HybridBatch* get() {
+        if (!on) return nullptr;
+        if (!hb) hb.reset(hybrid_batch_begin(sd));
+        return hb.get();
+    }
+};
+
+// A candidate with a discrete column (cols = [variable, parents]): the memo, the hand-off of an all-discrete family to the call's
+// discrete batch, or score_hybrid - whose score may arrive only when the hybrid batch is flushed.
+// Likelihood scores of DiscreteAdaptator factors cost k x configurations sweeps / Gram passes each, and a hill-climb asks for the same
+// (variable, type, parent SET) again and again: every RemoveArc cell is the local score the node had before that arc was added, every
+// FlipArc cell's source side likewise.  They are remembered by parent set (score_hybrid evaluates the continuous parents in ascending
+// order and the discrete ones in canonical order: the value does not depend on the order they were given in).  BIC stays out: bic_clg ties.
+void score_hybrid_candidate(pbn_scoredata* sd, const BatchArgs& a, int c, int nt, const std::vector<int>& cols, LazyHybridBatch& batch,
+                            std::vector<DiscreteCand>& discrete) {
+    const int kind = a.kind, p = (int)cols.size() - 1;
+    double* out = a.out + c;
+    if (a.parts_out) {   // a share of the candidate: never memoised
+        HybridParts hp{a.parts_rank, a.parts_world, a.parts_out + (size_t)c * PBN_HYBRID_PARTS};
+        HybridSink sink{out, {}};
+        *out = score_hybrid(sd, kind, cols[0], nt, cols.data() + 1, p, &hp, batch.get(), &sink);
+        return;
+    }
+    const bool memo = score_memo_on() && !sd->force_precise && (kind == PBN_SCORE_CVLIK || kind == PBN_SCORE_HOLDOUT);   // (discrete factors too)
+    std::vector<int> key;
+    if (memo) {
+        key.assign(cols.begin() + 1, cols.end());
+        std::sort(key.begin(), key.end());
+        key.insert(key.begin(), {kind, nt, cols[0]});
+        auto it = sd->score_memo.find(key);
+        if (it != sd->score_memo.end()) { *out = it->second; ++sd->memo_hits; return; }
+    }
+    if (cols[0] >= sd->n) {
+        check_discrete_candidate(sd, kind, nt, cols.data() + 1, p);
+        discrete.push_back(DiscreteCand{cols[0], std::vector<int>(cols.begin() + 1, cols.end()), out, key});
+        return;
+    }
+    HybridSink sink{out, key};   // (key empty without the memo)
+    bool deferred = false;
+    *out = score_hybrid(sd, kind, cols[0], nt, cols.data() + 1, p, nullptr, batch.get(), &sink, &deferred);
+    if (memo && !deferred) sd->score_memo[key] = *out;
+}
+
+}  // namespace
+
+void score_batch_body(pbn_scoredata* sd, const BatchArgs& a) {
+    if (!sd || !a.var || !a.par_off || !a.out) throw invalid_error("pbn_score_batch: null argument");
+    pbn_ctx* ctx = sd->ctx;
+    const int kind = a.kind;
+    if (sd->partial) throw invalid_error("pbn_score_batch: row-sharded score data needs pbn_scoredata_moments(set) first");
+    HIP_CHECK(hipSetDevice(ctx->device));
+    if ((kind == PBN_SCORE_CVLIK) && sd->k <= 0) throw invalid_error("pbn_score_batch: score data has no CV folds");
+    if ((kind == PBN_SCORE_HOLDOUT) && sd->n_hold <= 0) throw invalid_error("pbn_score_batch: score data has no hold-out split");
+    // The set-function cache and the local-score memo grow by one entry per (region, configuration, term) and per hybrid
+    // candidate (~150 B a node): a long search over hybrid candidates would take gigabytes.  Both are pure accelerators -
+    // beyond PBN_SCORE_CACHE_ENTRIES entries (default 2^21, ~300 MB) they start over, at a batch boundary (no entry of
+    // the batch being assembled is lost).
+    if (sd->kde_cache.size() > score_cache_budget()) { sd->kde_cache.clear(); ++sd->cache_resets; }
+    // (term_total is trimmed in pbn_score_terms_put only: every rank of a job reaches that call with the same state, whereas a rank
+    //  whose dealt list is empty skips the evaluation call - trimming here would let the ranks' "missing" lists drift apart)
+    if (sd->score_memo.size() > score_cache_budget()) { sd->score_memo.clear(); ++sd->cache_resets; }
+    if (kind < PBN_SCORE_BIC || kind > PBN_SCORE_BDE) throw invalid_error("pbn_score_batch: unknown score kind");
+    if (kind == PBN_SCORE_BGE && sd->discrete_only) throw invalid_error("BGe is not defined for networks with discrete variables.");
+    // BDe: the imaginary sample size; the discrete candidates of the call (variable a dictionary column) are collected here, counted
+    // together - all their families in one device pass - and finished after the loop (hybrid.hip, family_counts.hip)
+    const double bde_iss = (kind == PBN_SCORE_BDE && a.n_params >= 1 && a.params) ? a.params[0] : 1.0;
+    if (kind == PBN_SCORE_BDE && !(bde_iss > 0)) throw invalid_error("BDe: the imaginary sample size must be positive");
+    BgeParams bge{1, (double)(sd->n + 2), sd->n, nullptr};
+    if (kind == PBN_SCORE_BGE) {
+        if (a.n_params >= 1) bge.iss_mu = a.params[0];
+        if (a.n_params >= 2) bge.iss_w = a.params[1];
+        if (a.n_params >= 3) bge.total_nodes = (int)a.params[2];
+        if (a.n_params >= 3 + sd->n) bge.nu = a.params + 3;
+    }
+    ScoreScratch s;
+    std::vector<DiscreteCand> discrete;
+    std::vector<int> pending;   // plain CKDE candidates
+    LazyHybridBatch hbatch{sd};
+    const MaskedPlan plan = masked_prepass(sd, a, s.cols);
+    const bool likelihood = kind == PBN_SCORE_CVLIK || kind == PBN_SCORE_HOLDOUT;
+    for (int c = 0; c < a.n_cand; ++c) {
+        candidate_cols(a, c, s.cols);
+        bool hybrid = false;
+        for (int cc : s.cols) {
+            if (cc < 0 || cc >= sd->n + sd->n_disc) throw invalid_error("pbn_score_batch: column out of range");
+            if (cc >= sd->n) hybrid = true;
+        }
+        const int nt = a.node_type ? a.node_type[c] : PBN_NODE_LG;
+        if (hybrid) { score_hybrid_candidate(sd, a, c, nt, s.cols, hbatch, discrete); continue; }
+        if (kind == PBN_SCORE_BDE) throw invalid_error("BDe is defined for discrete variables with discrete parents only.");
+        if (!likelihood || nt == PBN_NODE_LG) { a.out[c] = score_gaussian_candidate(sd, kind, nt, bge, plan, s); continue; }
+        if (nt != PBN_NODE_CKDE) throw invalid_error("pbn_score_batch: unknown node type");
+        ctx->scratch_misc.reserve(1);  // touched by kde_eval_enqueue
+        pending.push_back(c);
+    }
+    hybrid_batch_flush(hbatch.hb.get());   // (before the plain CKDE units take the context's result slots)
+    hbatch.hb.reset();
+    score_discrete_batch(sd, kind, bde_iss, discrete);
+    if (!pending.empty()) score_ckde_terms(sd, a, pending, s);
+}
+
+int score_batch_local(pbn_scoredata* sd, int kind, int n_cand, const int* var, const int* node_type, const int* par_off, const int* parents,
+                      const double* params, int n_params, double* out) {
+    BatchArgs a;
+    a.kind = kind; a.n_cand = n_cand; a.var = var; a.node_type = node_type; a.par_off = par_off; a.parents = parents;
+    a.params = params; a.n_params = n_params; a.out = out;
+    return guarded(mu_of(sd), [&] { score_batch_body(sd, a); });
+}
+
+}  // namespace score
+}  // namespace pbn
+
+extern "C" {
 
 int pbn_scoredata_set_precise(pbn_scoredata* sd, int on) {
     return guarded(mu_of(sd), [&] {
@@ -1347,133 +1058,8 @@ int pbn_score_batch(pbn_scoredata* sd, int kind, int n_cand, const int* var, con
         } catch (const singular_error& e) { set_last_error(e.what()); return PBN_ERR_SINGULAR;
         } catch (const std::exception& e) { set_last_error(e.what()); return PBN_ERR_DEVICE; }
     }
-    return score_batch_impl(sd, kind, n_cand, var, node_type, par_off, parents, params, n_params, out, nullptr);
-}
-
-extern "C++" {
-namespace pbn {
-namespace score {
-int score_batch_local(pbn_scoredata* sd, int kind, int n_cand, const int* var, const int* node_type, const int* par_off, const int* parents,
-                      const double* params, int n_params, double* out) {
-    return score_batch_impl(sd, kind, n_cand, var, node_type, par_off, parents, params, n_params, out, nullptr);
-}
-}  // namespace score
-}  // namespace pbn
-}  // extern "C++"
-
-extern "C++" {
-namespace {
-// term i = columns vars[off[i] .. off[i + 1]) under the bandwidth rule for m[i] dimensions: m = the number of columns for a joint term,
-// one more for the marginal term of a candidate with those parents
-void check_terms(const pbn_scoredata* sd, int kind, int n_terms, const int* off, const int* vars, const int* m, const char* who) {
-    if (!sd || (n_terms > 0 && (!off || !vars || !m))) throw invalid_error(std::string(who) + ": null argument");
-    if (kind != PBN_SCORE_CVLIK && kind != PBN_SCORE_HOLDOUT) throw invalid_error(std::string(who) + ": likelihood scores only");
-    for (int i = 0; i < n_terms; ++i) {
-        const int nv = off[i + 1] - off[i];
-        if (nv < 1 || (m[i] != nv && m[i] != nv + 1)) throw invalid_error(std::string(who) + ": a term has m = its columns (joint) or one more (marginal)");
-        for (int j = off[i]; j < off[i + 1]; ++j)
-            if (vars[j] < 0 || vars[j] >= sd->n) throw invalid_error(std::string(who) + ": continuous columns only");
-    }
-}
-std::vector<int> term_key(int kind, const int* v, int nv, int m) {
-    std::vector<int> k(v, v + nv);
-    std::sort(k.begin(), k.end());
-    k.insert(k.begin(), {kind, m});
-    return k;
-}
-}  // namespace
-}  // extern "C++"
-
-int pbn_score_terms(pbn_scoredata* sd, int kind, int n_terms, const int* off, const int* vars, const int* m, double* out) {
-    return guarded(mu_of(sd), [&] {
-        check_terms(sd, kind, n_terms, off, vars, m, "pbn_score_terms");
-        if (n_terms > 0 && !out) throw invalid_error("pbn_score_terms: null output");
-        // every term as a pseudo-candidate of the batch engine over the term's OWN columns (first column | the others): a joint term
-        // asks for the joint half only (want 1), a marginal term for "the KDE of all my columns under the rule for one more dimension"
-        // (want 3) - no pseudo-child: the bandwidth block of the parents does not depend on the child (H = k(N, d) cov for the library
-        // selectors), and a degenerate unrelated column must not fail a term no real candidate pairs with it
-        std::vector<int> var((size_t)n_terms), nt((size_t)n_terms, PBN_NODE_CKDE), po{0}, par, want((size_t)n_terms);
-        for (int i = 0; i < n_terms; ++i) {
-            const int nv = off[i + 1] - off[i];
-            const int* v = vars + off[i];
-            var[i] = v[0];
-            want[i] = m[i] == nv ? 1 : 3;
-            par.insert(par.end(), v + 1, v + nv);
-            po.push_back((int)par.size());
-        }
-        if (n_terms > 0) {
-            const int rc = score_batch_impl(sd, kind, n_terms, var.data(), nt.data(), po.data(), par.data(), nullptr, 0, out, want.data());
-            // the inner status class goes out unchanged: a SingularCovarianceData of a term is one on every rank, not a device error
-            if (rc == PBN_ERR_SINGULAR) throw singular_error(pbn_last_error());
-            if (rc == PBN_ERR_INVALID) throw invalid_error(pbn_last_error());
-            if (rc != PBN_OK) throw device_error(pbn_last_error());
-        }
-    });
-}
-
-int pbn_score_term_regions(pbn_scoredata* sd, int kind, int n_items, const int* off, const int* vars, const int* m, const int* region, double* out) {
-    return guarded(mu_of(sd), [&] {
-        check_terms(sd, kind, n_items, off, vars, m, "pbn_score_term_regions");
-        if (n_items > 0 && (!out || !region)) throw invalid_error("pbn_score_term_regions: null argument");
-        const int regions = kind == PBN_SCORE_CVLIK ? sd->k : 1;
-        std::vector<int> var((size_t)n_items), nt((size_t)n_items, PBN_NODE_CKDE), po{0}, par, want((size_t)n_items);
-        for (int i = 0; i < n_items; ++i) {
-            if (region[i] < 0 || region[i] >= regions) throw invalid_error("pbn_score_term_regions: region out of range (CV folds; 0 for the hold-out score)");
-            const int nv = off[i + 1] - off[i];
-            const int* v = vars + off[i];
-            var[i] = v[0];
-            want[i] = m[i] == nv ? 1 : 3;   // as in pbn_score_terms
-            par.insert(par.end(), v + 1, v + nv);
-            po.push_back((int)par.size());
-        }
-        if (n_items > 0) {
-            const int rc = score_batch_impl(sd, kind, n_items, var.data(), nt.data(), po.data(), par.data(), nullptr, 0, out, want.data(), 0, 0, nullptr, region);
-            if (rc == PBN_ERR_SINGULAR) throw singular_error(pbn_last_error());
-            if (rc == PBN_ERR_INVALID) throw invalid_error(pbn_last_error());
-            if (rc != PBN_OK) throw device_error(pbn_last_error());
-        }
-    });
-}
-
-int pbn_score_terms_put(pbn_scoredata* sd, int kind, int n_terms, const int* off, const int* vars, const int* m, const double* values) {
-    return guarded(mu_of(sd), [&] {
-        check_terms(sd, kind, n_terms, off, vars, m, "pbn_score_terms_put");
-        if (n_terms > 0 && !values) throw invalid_error("pbn_score_terms_put: null values");
-        static const size_t budget = (size_t)std::max(1ll, knob_ll("PBN_SCORE_CACHE_ENTRIES", 1ll << 21));
-        if (sd->term_total.size() > budget) { sd->term_total.clear(); ++sd->cache_resets; }   // before the new terms go in: the batch being assembled keeps its own
-        for (int i = 0; i < n_terms; ++i) sd->term_total[term_key(kind, vars + off[i], off[i + 1] - off[i], m[i])] = values[i];
-    });
-}
-
-int pbn_score_batch_parts(pbn_scoredata* sd, int kind, int n_cand, const int* var, const int* node_type, const int* par_off,
-                          const int* parents, int part, int n_parts, double* out) {
-    return guarded(mu_of(sd), [&] {
-        if (!sd || !var || !node_type || !par_off || !out) throw invalid_error("pbn_score_batch_parts: null argument");
-        if (n_parts < 1 || n_parts > PBN_HYBRID_PARTS || part < 0 || part >= n_parts) throw invalid_error("pbn_score_batch_parts: part / n_parts out of range (at most 64 parts)");
-        for (int c = 0; c < n_cand; ++c) {
-            bool disc = false;
-            for (int j = par_off[c]; j < par_off[c + 1]; ++j) disc = disc || parents[j] >= sd->n;
-            if (!disc || node_type[c] != PBN_NODE_CKDE) throw invalid_error("pbn_score_batch_parts: CKDE candidates with discrete parents only");
-        }
-        std::vector<double> whole((size_t)std::max(n_cand, 1));
-        std::fill(out, out + (size_t)n_cand * PBN_HYBRID_PARTS, 0.0);
-        if (n_cand > 0) {
-            const int rc = score_batch_impl(sd, kind, n_cand, var, node_type, par_off, parents, nullptr, 0, whole.data(), nullptr, part, n_parts, out);
-            if (rc == PBN_ERR_SINGULAR) throw singular_error(pbn_last_error());
-            if (rc == PBN_ERR_INVALID) throw invalid_error(pbn_last_error());
-            if (rc != PBN_OK) throw device_error(pbn_last_error());
-        }
-    });
-}
-
-int pbn_score_terms_missing(pbn_scoredata* sd, int kind, int n_terms, const int* off, const int* vars, const int* m, int* missing) {
-    return guarded(mu_of(sd), [&] {
-        check_terms(sd, kind, n_terms, off, vars, m, "pbn_score_terms_missing");
-        if (n_terms > 0 && !missing) throw invalid_error("pbn_score_terms_missing: null output");
-        for (int i = 0; i < n_terms; ++i)
-            missing[i] = (sd->force_precise && sd->dtype == PBN_F64) ||   // (precise mode: every term is evaluated again, by the rank it is dealt to)
-                         sd->term_total.find(term_key(kind, vars + off[i], off[i + 1] - off[i], m[i])) == sd->term_total.end() ? 1 : 0;
-    });
+    return pbn::score::score_batch_local(sd, kind, n_cand, var, node_type, par_off, parents, params, n_params, out);
 }
 
 }  // extern "C"
+

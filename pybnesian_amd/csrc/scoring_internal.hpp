@@ -1,4 +1,4 @@
-// Internal declarations shared by scoring.hip and hybrid.hip (score engine).
+// Internal declarations shared by the units of the score engine (scoring.hip, score_terms.hip, hybrid.hip and the passes they call).
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -11,6 +11,10 @@
 #include "common.hpp"
 
 namespace pbn {
+struct KdeModel;     // kde_model.hpp
+struct GPool;        // kde_group.hpp
+struct GUnit;
+struct GroupBatch;
 namespace score {
 
 constexpr double MACHINE_TOL = 1.4901161193847656e-08;  // util/math_constants.hpp:30, sqrt(eps(double))
@@ -173,6 +177,56 @@ struct HybridSink {
     double* out;                  // where the candidate's score goes
     std::vector<int> memo_key;    // non-empty: also remembered in pbn_scoredata::score_memo under this key
 };
+// One call of the batch engine (scoring.hip).  want (nullable, per candidate): 0 = the local score; 1 / 2 = only the joint / only the marginal
+// CKDE term of the candidate, summed over the regions; 3 = a marginal TERM over all of the pseudo-candidate's columns (pbn_score_terms).
+// only_region (nullable, per candidate; pbn_score_term_regions): >= 0 = that region's contribution alone (a CV fold; 0 for the hold-out score).
+// parts_out (pbn_score_batch_parts): hybrid CKDE candidates evaluated on the parts of rank parts_rank of parts_world only, per-part sums to
+// parts_out[c * PBN_HYBRID_PARTS ...].
+struct BatchArgs {
+    int kind = 0, n_cand = 0;
+    const int *var = nullptr, *node_type = nullptr, *par_off = nullptr, *parents = nullptr;   // as pbn_score_batch takes them
+    const double* params = nullptr;
+    int n_params = 0;
+    double* out = nullptr;
+    const int* want = nullptr;
+    int parts_rank = 0, parts_world = 0;
+    double* parts_out = nullptr;
+    const int* only_region = nullptr;
+    int n_parents(int c) const { return par_off[c + 1] - par_off[c]; }
+    int want_of(int c) const { return want ? want[c] : 0; }
+};
+// the engine itself: throws; the caller holds the handle's lock (guarded(mu_of(sd), ...))
+void score_batch_body(pbn_scoredata* sd, const BatchArgs& a);
+void candidate_cols(const BatchArgs& a, int c, std::vector<int>& cols);   // [variable, parents as given]
+size_t score_cache_budget();   // PBN_SCORE_CACHE_ENTRIES (default 2^21): kde_cache / score_memo / term_total start over beyond it
+// host buffers of one call, reused from candidate to candidate and from term to term (no allocation per candidate on the search's path)
+struct ScoreScratch {
+    Stats train;
+    std::vector<int> cols;
+    std::vector<double> mu, sse, beta, H;
+};
+// score_terms.hip: the plain CKDE candidates of a call (`pending`: their indices, in call order) through the set-function cache
+void score_ckde_terms(pbn_scoredata* sd, const BatchArgs& a, const std::vector<int>& pending, ScoreScratch& s);
+
+// ---- shared by the plain term engine (score_terms.hip) and the hybrid one (hybrid.hip) ----
+struct Term { double value = 0; int slot = -1; };   // a term's cached value, or its slot in the device sums
+bool f32_check_after();   // PBN_F32_CHECK (default 1; 0: measurement only): fp32 evaluations flagged by kde_wants_widening are redone on fp64 fragments
+inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
+// [x, m, sorted columns...]: the keys of kde_cache (x = region) and of term_total (x = score kind)
+std::vector<int> set_key(int x, int m, const int* v, int nv);
+// a unit of a grouped pool from a prepared model of nv columns: trained on every region but `region` (CV) or on region 0 (hold-out)
+GUnit group_unit(bool cv, int R, int region, const KdeModel& m, int nv, int64_t ntrain, int64_t ntest, int slot);
+// a pool's standardisation for the Morton keys (Wg, mug) from the covariance (nv x nv col-major) and means of its columns: L^-1 of the
+// covariance; a singular one falls back to its diagonal - the keys only order the rows
+void pool_standardise(GPool& P, const double* cov, const double* means, int nv);
+// rows of one evaluation: training [row0, row0 + n0) ++ [row1, ...), test [te0, te0 + te_n) - of the table, or of a gather list
+struct TermRows { int64_t row0, n0, row1, te0, te_n; };
+// one term through a launch chain of its own, on the current lane: carves the lane's scratch_train, packs the training rows and enqueues the sweep
+void enqueue_term_chain(pbn_ctx* ctx, KdeModel& m, const pbn_table* t, const int* cols, const TermRows& r, const int32_t* dev_rows, double* dev_sum,
+                        double* dev_max, bool precise);
+// closes collected pools - unit0 / nunits, their units behind dst's - and appends them to dst; bytes (nullable) grows by their arena bytes
+void append_pools(GroupBatch& dst, const std::vector<GPool>& pools, const std::vector<std::vector<GUnit>>& pool_units, size_t* bytes);
+
 // pbn_score_batch without / with the job's communicator (scoring.hip / shard.hip)
 int score_batch_local(pbn_scoredata* sd, int kind, int n_cand, const int* var, const int* node_type, const int* par_off, const int* parents,
                       const double* params, int n_params, double* out);
