@@ -300,7 +300,10 @@ void launch_query_prepass(const double* zq_row, const int32_t* qperm, int64_t nq
 // qrow_thr (nullable, [nqtiles * 16]) takes every query's own sum bound where it lies above its tile's final one, else the tile's
 void launch_query_window(const double* Apack, const double* nxpack, const double* Bpack, const double* nypack, int64_t ntiles, int64_t n_train,
                          int64_t nqtiles, int64_t nq, const int64_t* qtpos, int window, bool fold, double* qthr, double* qlb, double* qrow_thr,
-                         double* dbg, hipStream_t st);
+                         double* dbg, int nparts, double* part, hipStream_t st);
+// the walks of the window pass are cut into window_parts() parts, whose partial sums take window_part_bytes() of scratch (`part`)
+int window_parts(int64_t nqtiles, int num_cus);
+size_t window_part_bytes(int64_t nqtiles, int nparts);
 void sort_keys(pbn::dev_buf<char>& tmp, const uint32_t* keys_in, uint32_t* keys_out, const int32_t* vals_in, int32_t* vals_out, int64_t n,
                int bits, hipStream_t st);
 // 52 (fp64) / 40 (fp32 on the f16 cores) at 10^6 training rows, + log2(n_train / 10^6): a constant bound (2.2e-10 / 9.1e-7 of a sum) on what

@@ -490,6 +490,7 @@ static MaskDump g_masks;
 static std::atomic<bool> g_window_capture{false};
 static std::mutex g_window_mu;
 static std::vector<double> g_window_lb;
+static std::vector<int64_t> g_window_pos;   // pbn_debug_window_pos: per query the centre of its tile's window, a position in the sorted training order
 
 void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, const int* cols, int64_t row0, int64_t n,
                       double* dev_logl, double* dev_sum, const int32_t* dev_rows, double* dev_sum_marg, bool precise) {
@@ -572,13 +573,15 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     int64_t* qtpos = nullptr;
     double* qdbg = nullptr;
     double* qrow = nullptr;   // per query: its own sum bound where above its tile's (query_window_kernel), for the d = 8 screen's columns
+    double* qwpart = nullptr;   // the partial sums of the window pass's parts
+    const int wparts = window ? window_parts(nqtiles, ctx->num_cus) : 0;
     if (prune) {
         auto al = [](size_t x) { return (x + 255) / 256 * 256; };
         const size_t qbox_b = al((size_t)nqtiles * 2 * m.pdims * sizeof(double)), qthr_b = al((size_t)nqtiles * sizeof(double));
         const size_t qlb_b = al((size_t)nqtiles * 16 * sizeof(double));
         const size_t qtpos_b = window ? al((size_t)nqtiles * sizeof(int64_t)) : 0, qdbg_b = wdbg ? al((size_t)nqtiles * 16 * sizeof(double)) : 0;
-        const size_t qrow_b = window ? qlb_b : 0;
-        qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.kdims, qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b + qrow_b);
+        const size_t qrow_b = window ? qlb_b : 0, qwpart_b = window ? al(window_part_bytes(nqtiles, wparts)) : 0;
+        qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.kdims, qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b + qrow_b + qwpart_b);
         pa.perm = qs.perm;
         qperm = qs.perm;
         qbox = (double*)qs.rest; qthr = (double*)(qs.rest + qbox_b);
@@ -587,6 +590,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         if (window) qtpos = (int64_t*)(qs.rest + qbox_b + qthr_b + qlb_b);
         if (wdbg) qdbg = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b);
         if (window) qrow = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b);
+        if (window) qwpart = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b + qrow_b);
     }
     pa.pack = q; pa.npack = q + bpack_b; pa.xpack = m.cond ? q + bpack_b + ny_b : nullptr;
     pa.xnorm = xn_b ? q + bpack_b + ny_b + bx_b : nullptr;
@@ -613,16 +617,20 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
                              ctx->stream, subpart, P, m.cond ? 2 : 0, subpart ? std::log2((double)m.nsub) : 0.0, m.cond ? nullptr : m.tile_box, qtpos);
         if (window) {
             { KernelTimer kt(ctx, PBN_K_PACK); launch_query_window((const double*)m.Apack, (const double*)m.nxpack, (const double*)pa.pack, (const double*)pa.npack,
-                                                               m.ntiles, m.N, nqtiles, n, qtpos, window, fold, (double*)qthr, (double*)qlb, qrow, qdbg, ctx->stream); }
+                                                               m.ntiles, m.N, nqtiles, n, qtpos, window, fold, (double*)qthr, (double*)qlb, qrow, qdbg, wparts, qwpart, ctx->stream); }
             if (wdbg) {   // pbn_debug_sum_window: the queries' bounds, in the table's row order
                 std::vector<double> lb((size_t)n);
                 std::vector<int32_t> perm((size_t)n);
+                std::vector<int64_t> tpos((size_t)nqtiles);
                 HIP_CHECK(hipMemcpyAsync(lb.data(), qdbg, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_CHECK(hipMemcpyAsync(tpos.data(), qtpos, (size_t)nqtiles * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
                 HIP_CHECK(hipMemcpyAsync(perm.data(), qperm, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
                 HIP_CHECK(hipStreamSynchronize(ctx->stream));
                 std::lock_guard<std::mutex> lk(g_window_mu);
                 g_window_lb.assign((size_t)n, -INFINITY);
                 for (int64_t i = 0; i < n; ++i) g_window_lb[(size_t)perm[(size_t)i]] = lb[(size_t)i];
+                g_window_pos.assign((size_t)n, -1);
+                for (int64_t i = 0; i < n; ++i) g_window_pos[(size_t)perm[(size_t)i]] = tpos[(size_t)(i >> 4)];
             }
         }
     }
@@ -776,6 +784,16 @@ extern "C" int64_t pbn_debug_sum_window(double* out, int64_t cap, int capture) {
     std::lock_guard<std::mutex> lk(pbn::g_window_mu);
     const int64_t n = (int64_t)pbn::g_window_lb.size();
     for (int64_t i = 0; out && i < n && i < cap; ++i) out[i] = pbn::g_window_lb[(size_t)i];
-    if (!capture) pbn::g_window_lb.clear();
+    if (!capture) { pbn::g_window_lb.clear(); pbn::g_window_pos.clear(); }
+    return n;
+}
+
+// pbn_debug_window_pos (test aid, not part of the C ABI header): of the evaluation that pbn_debug_sum_window last captured, per query in the
+// table's row order the training position (a row of the sorted order, 0 ... N) around whose tile its query tile's window stood - the position
+// of the tile's first query; copies up to cap of them and returns how many there are.  Cleared with the bounds.
+extern "C" int64_t pbn_debug_window_pos(int64_t* out, int64_t cap) {
+    std::lock_guard<std::mutex> lk(pbn::g_window_mu);
+    const int64_t n = (int64_t)pbn::g_window_pos.size();
+    for (int64_t i = 0; out && i < n && i < cap; ++i) out[i] = pbn::g_window_pos[(size_t)i];
     return n;
 }

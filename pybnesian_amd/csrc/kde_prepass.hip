@@ -268,12 +268,38 @@ __global__ __launch_bounds__(256) void query_prepass_kernel(const double* __rest
         tpos_ = lo;
         const int64_t b = lo - PBN_PRUNE_WINDOW > 0 ? lo - PBN_PRUNE_WINDOW : 0, e = lo + PBN_PRUNE_WINDOW < n ? lo + PBN_PRUNE_WINDOW : n;
         double acc = 0.0;
-        for (int64_t t = b; t < e; ++t) {
-            double d2 = 0.0;
-            for (int k = 0; k < zd; ++k) { const double dd = zt[t * zd + k] - z[k]; d2 = __builtin_fma(dd, dd, d2); }
-            const double ex = -0.5 * d2;
+        auto term = [&](double ex) {   // the rows' terms are added up in the order of the rows
             if (ex > best) { acc = acc * exp2(best - ex) + 1.0; best = ex; }
             else acc += exp2(ex - best);
+        };
+        if (zd == 8) {
+            // Round 15: with zd a run-time number every coordinate of every row was a load of its own behind the one before - a chain of
+            // 64 x 8 load latencies per thread, and the kernel lasts as long as one thread does.  Eight dimensions (the bench's model): the
+            // coordinates by constant index, and the exponents of four rows - 32 loads in flight - before their terms are added up.  The
+            // same operations on the same numbers in the same order as the loop below: the same bits.
+            double z8[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) z8[k] = zp[k];
+            for (int64_t t = b; t < e; t += 4) {
+                double ex[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double* r = zt + (t + i < e ? t + i : e - 1) * 8;   // (past the end: the last row once more, not used)
+                    double d2 = 0.0;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) { const double dd = r[k] - z8[k]; d2 = __builtin_fma(dd, dd, d2); }
+                    ex[i] = -0.5 * d2;
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (t + i < e) term(ex[i]);
+            }
+        } else {
+            for (int64_t t = b; t < e; ++t) {
+                double d2 = 0.0;
+                for (int k = 0; k < zd; ++k) { const double dd = zt[t * zd + k] - z[k]; d2 = __builtin_fma(dd, dd, d2); }
+                term(-0.5 * d2);
+            }
         }
         if (acc > 0.0) sumb = best + log2(acc);
         // Neighbours in Morton order are neighbours in the keyed (<= 3) dimensions only: with more dimensions than that the
@@ -313,20 +339,39 @@ __global__ __launch_bounds__(256) void query_prepass_kernel(const double* __rest
         const int64_t full = n >> 4, tt = tp0 >> 4;
         const int64_t t_lo = tt - tile_window > 0 ? tt - tile_window : 0, t_hi = tt + tile_window < full ? tt + tile_window : full;
         double bmax = -INFINITY, bacc = 0.0;
-        if (lob[0] <= hib[0])
-            for (int64_t t = t_lo + l16; t < t_hi; t += 16) {
-                const double* bx = tile_box + t * 2 * pd;
-                double d2 = 0.0;
-                for (int k = 0; k < pd; ++k) {
-                    const double a1 = bx[pd + k] - lob[k], a2 = hib[k] - bx[k];
-                    const double a = a1 > a2 ? a1 : a2;
-                    d2 = __builtin_fma(a, a, d2);
+        auto corner = [&](double ex) {
+            if (!(ex == ex)) return;
+            if (ex > bmax) { bacc = bacc * exp2(bmax - ex) + 1.0; bmax = ex; }
+            else bacc += exp2(ex - bmax);
+        };
+        if (lob[0] <= hib[0]) {
+            // (round 15, as the scan above: at eight dimensions a box's sixteen numbers by constant index, their loads in flight together;
+            // the same bits)
+            if (pd == PBN_PRUNE_PD) {
+                for (int64_t t = t_lo + l16; t < t_hi; t += 16) {
+                    const double* bx = tile_box + t * 2 * PBN_PRUNE_PD;
+                    double d2 = 0.0;
+#pragma unroll
+                    for (int k = 0; k < PBN_PRUNE_PD; ++k) {
+                        const double a1 = bx[PBN_PRUNE_PD + k] - lob[k], a2 = hib[k] - bx[k];
+                        const double a = a1 > a2 ? a1 : a2;
+                        d2 = __builtin_fma(a, a, d2);
+                    }
+                    corner(-0.5 * d2);
                 }
-                const double ex = -0.5 * d2;
-                if (!(ex == ex)) continue;
-                if (ex > bmax) { bacc = bacc * exp2(bmax - ex) + 1.0; bmax = ex; }
-                else bacc += exp2(ex - bmax);
+            } else {
+                for (int64_t t = t_lo + l16; t < t_hi; t += 16) {
+                    const double* bx = tile_box + t * 2 * pd;
+                    double d2 = 0.0;
+                    for (int k = 0; k < pd; ++k) {
+                        const double a1 = bx[pd + k] - lob[k], a2 = hib[k] - bx[k];
+                        const double a = a1 > a2 ? a1 : a2;
+                        d2 = __builtin_fma(a, a, d2);
+                    }
+                    corner(-0.5 * d2);
+                }
             }
+        }
         for (int off = 1; off < 16; off <<= 1) {
             const double om = __shfl_xor(bmax, off), oa = __shfl_xor(bacc, off);
             if (om > bmax) { bacc = bacc * exp2(bmax - om) + oa; bmax = om; }
@@ -366,61 +411,189 @@ __global__ __launch_bounds__(256) void query_prepass_kernel(const double* __rest
 // of the tile (padding, NaN queries, lb <= T) gets T.  A NaN T stays a NaN in all sixteen.
 // dbg (nullable, pbn_debug_sum_window): lb per query in the sorted order, -inf where there is none.
 #define PBN_WINDOW_SLACK 0x1p-8
-template <bool FOLD>
-__global__ __launch_bounds__(256) void query_window_kernel(const double* __restrict__ Ap, const double* __restrict__ Np, const double* __restrict__ Bp,
-                                                           const double* __restrict__ NYp, int64_t ntiles, int64_t n_train, int64_t nqtiles, int64_t nq,
-                                                           const int64_t* __restrict__ qtpos, int window, double* __restrict__ qthr,
-                                                           double* __restrict__ qlb, double* __restrict__ qrow_thr, double* __restrict__ dbg) {
-    constexpr int KS = 2;
+// Round 15: how the pass runs.  One wave serves PBN_WINDOW_NQ neighbouring query tiles against ONE stream of training fragments, as the sweep
+// serves its groups: neighbouring tiles sit ~10 training tiles apart in the sorted order, their windows overlap by 98 %, and a wave per tile
+// streamed its own copy with one tile of loads in flight (0.80 ms at 1e6 x 1e5 rows, two thirds of its wave cycles waiting: profiles/r15/).
+// The walk covers the hull of the served tiles' windows and every tile adds up the terms of its OWN window only (a uniform test per tile and
+// fragment): the terms of every sum are the ones they were, so the thresholds - and with them the blocks the sweep visits, which
+// tests/test_prune_d8_sweep_gpu.py pins to the block - move in their last bits at most.  Where the hull is longer than 2.5 W tiles (few
+// queries, far apart) the wave walks each tile's own window in turn instead, so that no wave walks a table's length for a handful of
+// queries.  PBN_WINDOW_RING tiles of fragments rotate through registers: two tiles of loads are in flight beyond the one being used,
+// unconditional (past the end the last tile is loaded again) and waited for by count.  The padding test runs on the table's last tile
+// only, a NaN exponent becomes -inf in the maximum that takes it.
+// A walk is cut into `nparts` equal parts, one wave each, chosen by the host so that the CUs get the same number of workgroups to within
+// one (window_parts); a part leaves (offset, sum, largest exponent) per query, and query_window_finish_kernel combines the parts in the
+// order of their number - the same bits in every run - and writes qthr, qlb, qrow_thr and dbg by the rules above.
+#define PBN_WINDOW_NQ 4
+#define PBN_WINDOW_RING 3
+
+// the walk of one wave: G query tiles qt[0..G) against the training tiles [t0, t1); partials to part[(k * nq16) + query], k = 0 offset, 1 sum, 2 top
+template <bool FOLD, int G>
+__device__ __forceinline__ void window_walk(const double* __restrict__ Ap, const double* __restrict__ Np, const double* __restrict__ Bp,
+                                            const double* __restrict__ NYp, const int64_t (&qt)[G], const bool (&mine)[G], const int64_t (&lo)[G],
+                                            const int64_t (&hi)[G], int64_t t0, int64_t t1, int64_t n_train, int64_t nq16,
+                                            double* __restrict__ part, int lane) {
+    constexpr int KS = 2, R = PBN_WINDOW_RING;
     using V = Tr<double>::vec4;
-    const int lane = threadIdx.x & 63, lg = lane >> 4, col = lane & 15;
-    const int64_t qt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (qt >= nqtiles) return;   // (wave-uniform; no barriers)
-    const int64_t q = qt * 16 + col;
-    double b[KS];
+    const int lg = lane >> 4, col = lane & 15;
+    double b[G][KS], ny[G];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) b[ks] = Bp[(qt * KS + ks) * 64 + lane];
-    const double ny = NYp[qt * 16 + col];
-    const int64_t tt = qtpos[qt] >> 4;
-    const int64_t t_lo = tt - window > 0 ? tt - window : 0, t_hi = tt + window < ntiles ? tt + window : ntiles;
-    double mx = -INFINITY, s = 0.0, top = -INFINITY;   // integer offset, sum of 2^(x - mx), largest x
-    // the next tile's fragments are in flight while one is processed (after the last tile the last one is loaded again)
-    double a0 = 0.0, a1 = 0.0;
-    V nx = {};
-    auto load = [&](int64_t t) {
-        a0 = Ap[(t * KS) * 64 + lane];
-        a1 = Ap[(t * KS + 1) * 64 + lane];
-        if (!FOLD) nx = *(const V*)(Np + t * 16 + lg * 4);
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) b[g][ks] = Bp[(qt[g] * KS + ks) * 64 + lane];
+        ny[g] = NYp[qt[g] * 16 + col];
+    }
+    double mx[G], s[G], top[G];   // integer offset, sum of 2^(x - mx), largest x
+#pragma unroll
+    for (int g = 0; g < G; ++g) { mx[g] = -1e300; s[g] = 0.0; top[g] = -INFINITY; }
+    // one tile of fragments against the G query tiles.  PAD (a constant at every call): the table's padded last tile, whose rows beyond
+    // n_train are left out; the walk's loop never sees it.  fmax() drops a NaN exponent: -inf.
+    auto tile = [&](double c0, double c1, V n, int64_t t, bool PAD) {
+        V acc[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = FOLD ? V{ny[g], ny[g], ny[g], ny[g]} : n + ny[g];
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = Tr<double>::mfma(c0, b[g][0], acc[g]);
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g] = Tr<double>::mfma(c1, b[g][1], acc[g]);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (G > 1 && !(t >= lo[g] && t < hi[g])) continue;   // (uniform) outside this query tile's own window
+            double x[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                x[i] = __builtin_fmax(acc[g][i], -INFINITY);
+                if (PAD) x[i] = t * 16 + Tr<double>::crow(lg, i) < n_train ? x[i] : -INFINITY;
+            }
+            const double tm = __builtin_fmax(__builtin_fmax(x[0], x[1]), __builtin_fmax(x[2], x[3]));
+            // The offset is the largest ceil(tm) so far - an integer, -1e300 before the first term, so that x - mx is never inf - inf.  Where
+            // no lane's offset rises (uniform test; all but the first few tiles of a walk) nothing is rescaled; where one does, every lane
+            // rescales its sum by 2^(old - new offset): by 2^0 where its own stays, to 0 where it rises by 4000 or more (the first term: the
+            // sum is 0 anyway).  ceil, the conversion and ldexp are quarter-rate instructions: 48 cycles a block where they run.
+            if (__any(tm > mx[g])) {
+                const double nm = __builtin_fmax(mx[g], __builtin_ceil(tm));
+                s[g] = __builtin_ldexp(s[g], (int)__builtin_fmax(mx[g] - nm, -4000.0));
+                top[g] = tm > mx[g] ? tm : top[g];   // (the term that set the offset: within one unit of the largest)
+                mx[g] = nm;
+            }
+            const double nm = mx[g];
+            const float f0 = __builtin_amdgcn_exp2f((float)(x[0] - nm)), f1 = __builtin_amdgcn_exp2f((float)(x[1] - nm));
+            const float f2 = __builtin_amdgcn_exp2f((float)(x[2] - nm)), f3 = __builtin_amdgcn_exp2f((float)(x[3] - nm));
+            s[g] += (double)((f0 + f1) + (f2 + f3));
+        }
     };
-    if (t_lo < t_hi) load(t_lo);
-    for (int64_t t = t_lo; t < t_hi; ++t) {
-        V acc = FOLD ? V{ny, ny, ny, ny} : nx + ny;
-        const double c0 = a0, c1 = a1;
-        load(t + 1 < t_hi ? t + 1 : t);
-        acc = Tr<double>::mfma(c0, b[0], acc);
-        acc = Tr<double>::mfma(c1, b[1], acc);
-        double x[4], tm = -INFINITY;
+    const int64_t nfull = n_train >> 4;                    // tiles without a padding row
+    const int64_t te = t1 < nfull ? t1 : nfull;            // the loop's end
+    if (t0 < te) {
+        double a0[R], a1[R];
+        V nx[R];
+        const int64_t tl = te - 1;
+        auto load = [&](int r, int64_t t) {
+            t = t < tl ? t : tl;
+            a0[r] = Ap[(t * KS) * 64 + lane];
+            a1[r] = Ap[(t * KS + 1) * 64 + lane];
+            if (!FOLD) nx[r] = *(const V*)(Np + t * 16 + lg * 4);
+        };
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool ok = t * 16 + Tr<double>::crow(lg, i) < n_train && acc[i] == acc[i];
-            x[i] = ok ? acc[i] : -INFINITY;
-            tm = x[i] > tm ? x[i] : tm;
-        }
-        if (tm > mx) {
-            const double nm = __builtin_ceil(tm), sh = mx - nm;
-            s = sh < -2000.0 ? 0.0 : __builtin_ldexp(s, (int)sh);
-            mx = nm;
-            top = tm;
-        }
-        if (tm > -INFINITY) {
-            const float f0 = __builtin_amdgcn_exp2f((float)(x[0] - mx)), f1 = __builtin_amdgcn_exp2f((float)(x[1] - mx));
-            const float f2 = __builtin_amdgcn_exp2f((float)(x[2] - mx)), f3 = __builtin_amdgcn_exp2f((float)(x[3] - mx));
-            s += (double)((f0 + f1) + (f2 + f3));
+        for (int r = 0; r < R - 1; ++r) load(r, t0 + r);
+        for (int64_t tb = t0; tb < te; tb += R) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int64_t t = tb + r;
+                load((r + R - 1) % R, t + R - 1);   // into the registers the tile before this one has just left
+                if (t < te) tile(a0[r], a1[r], nx[r], t, false);   // (uniform)
+            }
         }
     }
-    // the four lanes of a query column (lg = 0..3)
-    for (int off = 16; off < 64; off <<= 1) {
-        const double om = __shfl_xor(mx, off), os = __shfl_xor(s, off), ot = __shfl_xor(top, off);
+    if (t0 <= nfull && nfull < t1) {   // (uniform) the padded last tile is this walk's
+        V n = {};
+        if (!FOLD) n = *(const V*)(Np + nfull * 16 + lg * 4);
+        tile(Ap[(nfull * KS) * 64 + lane], Ap[(nfull * KS + 1) * 64 + lane], n, nfull, true);
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        if (!(s[g] > 0.0)) mx[g] = -INFINITY;   // no term: no offset (a term leaves at least 0.5 in the sum at the offset it set or met)
+        // the four lanes of a query column (lg = 0..3)
+        for (int off = 16; off < 64; off <<= 1) {
+            const double om = __shfl_xor(mx[g], off), os = __shfl_xor(s[g], off), ot = __shfl_xor(top[g], off);
+            top[g] = ot > top[g] ? ot : top[g];
+            if (om > mx[g]) {
+                const double sh = mx[g] - om;
+                s[g] = (sh < -2000.0 ? 0.0 : __builtin_ldexp(s[g], (int)sh)) + os;
+                mx[g] = om;
+            } else if (om > -INFINITY) {
+                const double sh = om - mx[g];
+                s[g] += sh < -2000.0 ? 0.0 : __builtin_ldexp(os, (int)sh);
+            }
+        }
+        if (mine[g] && lg == 0) {
+            double* o = part + qt[g] * 16 + col;
+            o[0] = mx[g];
+            o[nq16] = s[g];
+            o[2 * nq16] = top[g];
+        }
+    }
+}
+
+template <bool FOLD>
+__global__ __launch_bounds__(256, 2) void query_window_kernel(const double* __restrict__ Ap, const double* __restrict__ Np, const double* __restrict__ Bp,
+                                                           const double* __restrict__ NYp, int64_t ntiles, int64_t n_train, int64_t nqtiles,
+                                                           const int64_t* __restrict__ qtpos, int window, int nparts, double* __restrict__ part) {
+    constexpr int G = PBN_WINDOW_NQ;
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform: what names a tile is scalar
+    const int64_t grp = w / nparts;
+    const int p = (int)(w - grp * nparts);
+    if (grp * G >= nqtiles) return;   // (wave-uniform; no barriers)
+    const int64_t nq16 = nqtiles * 16;
+    double* mypart = part + (int64_t)p * 3 * nq16;
+    int64_t qt[G], lo[G], hi[G];
+    bool mine[G];
+    int64_t hlo = ntiles, hhi = 0;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        mine[g] = grp * G + g < nqtiles;   // a partner tile that does not exist: the last tile once more, nothing stored
+        qt[g] = mine[g] ? grp * G + g : nqtiles - 1;
+        const int64_t tt = qtpos[qt[g]] >> 4;
+        lo[g] = tt - window > 0 ? tt - window : 0;
+        hi[g] = tt + window < ntiles ? tt + window : ntiles;
+        hlo = lo[g] < hlo ? lo[g] : hlo;
+        hhi = hi[g] > hhi ? hi[g] : hhi;
+    }
+    auto cut = [&](int64_t a, int64_t e, int64_t& t0, int64_t& t1) {   // part p of [a, e)
+        const int64_t len = e > a ? (e - a + nparts - 1) / nparts : 0;
+        t0 = a + p * len < e ? a + p * len : e;
+        t1 = t0 + len < e ? t0 + len : e;
+    };
+    if (hhi - hlo <= 2 * (int64_t)window + window / 2) {
+        int64_t t0, t1;
+        cut(hlo, hhi, t0, t1);
+        window_walk<FOLD, G>(Ap, Np, Bp, NYp, qt, mine, lo, hi, t0, t1, n_train, nq16, mypart, lane);
+    } else {
+#pragma unroll 1
+        for (int g = 0; g < G; ++g) {
+            int64_t q1[1], l1[1] = {0}, h1[1] = {0}, t0, t1;
+            bool m1[1];
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k == g) { q1[0] = qt[k]; m1[0] = mine[k]; l1[0] = lo[k]; h1[0] = hi[k]; }
+            if (!m1[0]) break;
+            cut(l1[0], h1[0], t0, t1);
+            window_walk<FOLD, 1>(Ap, Np, Bp, NYp, q1, m1, l1, h1, t0, t1, n_train, nq16, mypart, lane);
+        }
+    }
+}
+
+// one thread per query column: the parts of its walk in the order of their number, then the rules of the header comment
+__global__ __launch_bounds__(256) void query_window_finish_kernel(const double* __restrict__ part, int nparts, const double* __restrict__ NYp,
+                                                                  int64_t nqtiles, int64_t nq, double* __restrict__ qthr, double* __restrict__ qlb,
+                                                                  double* __restrict__ qrow_thr, double* __restrict__ dbg) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x, nq16 = nqtiles * 16;
+    if (q >= nq16) return;   // (whole query tiles: the 16 lanes of a tile stay together)
+    double mx = -INFINITY, s = 0.0, top = -INFINITY;
+    for (int p = 0; p < nparts; ++p) {
+        const double* o = part + (int64_t)p * 3 * nq16 + q;
+        const double om = o[0], os = o[nq16], ot = o[2 * nq16];
         top = ot > top ? ot : top;
         if (om > mx) {
             const double sh = mx - om;
@@ -431,19 +604,21 @@ __global__ __launch_bounds__(256) void query_window_kernel(const double* __restr
             s += sh < -2000.0 ? 0.0 : __builtin_ldexp(os, (int)sh);
         }
     }
+    const int64_t qt = q >> 4;
+    const double ny = NYp[q];
     const bool valid = q < nq && ny == ny;
     const double lb = (valid && s > 0.0) ? mx + log2(s) - PBN_WINDOW_SLACK : -INFINITY;
-    if (dbg && lg == 0 && q < nq) dbg[q] = lb;
-    if (qlb && lg == 0 && valid && top > qlb[q]) qlb[q] = top;
+    if (dbg && q < nq) dbg[q] = lb;
+    if (qlb && valid && top > qlb[q]) qlb[q] = top;
     double g = valid ? lb : INFINITY;
     for (int off = 1; off < 16; off <<= 1) { const double o = __shfl_xor(g, off); g = o < g ? o : g; }
     const double told = qthr[qt];   // (every lane reads it before lane 0's store below: one wave, program order)
     const bool raise = g < INFINITY && g > told;
-    if (qrow_thr && lg == 0) {
+    if (qrow_thr) {
         const double T = raise ? g : told;
-        qrow_thr[qt * 16 + col] = (valid && lb > T) ? lb : T;
+        qrow_thr[q] = (valid && lb > T) ? lb : T;
     }
-    if (lane == 0 && raise) qthr[qt] = g;
+    if ((q & 15) == 0 && raise) qthr[qt] = g;
 }
 
 void launch_pack_classic(const PackArgs& a, int dtype, hipStream_t st) {
@@ -644,13 +819,33 @@ void launch_query_prepass(const double* zq_row, const int32_t* qperm, int64_t nq
     HIP_CHECK(hipGetLastError());
 }
 
+// parts a window walk is cut into (query_window_kernel): the number in 1..8 under which the most loaded CU carries the least work - workgroups
+// of four waves are dealt to the CUs in turn, so the work of a CU is ceil(workgroups / CUs) walks of 1 / parts of a window each - and among
+// numbers within 3 % of the best the smallest: 1e5 queries on 256 CUs: 1 563 groups, 5 parts, 1 954 workgroups, 8 on a CU at most for 7.6
+int window_parts(int64_t nqtiles, int num_cus) {
+    static const int fixed = PBN_TUNE(WINDOW_PARTS, 0);
+    if (fixed > 0) return fixed < 64 ? fixed : 64;
+    const int64_t groups = ceil_div(nqtiles, PBN_WINDOW_NQ), cus = num_cus > 0 ? num_cus : 1;
+    double cost[9], best = INFINITY;
+    for (int s = 1; s <= 8; ++s) {
+        cost[s] = (double)ceil_div(ceil_div(groups * s, 4), cus) / s;
+        best = cost[s] < best ? cost[s] : best;
+    }
+    for (int s = 1; s <= 8; ++s)
+        if (cost[s] <= 1.03 * best) return s;
+    return 8;
+}
+size_t window_part_bytes(int64_t nqtiles, int nparts) { return (size_t)nparts * 3 * (size_t)nqtiles * 16 * sizeof(double); }
+
 void launch_query_window(const double* Apack, const double* nxpack, const double* Bpack, const double* nypack, int64_t ntiles, int64_t n_train,
                          int64_t nqtiles, int64_t nq, const int64_t* qtpos, int window, bool fold, double* qthr, double* qlb, double* qrow_thr, double* dbg,
-                         hipStream_t st) {
+                         int nparts, double* part, hipStream_t st) {
     if (nqtiles == 0 || window <= 0) return;
-    const dim3 grid((unsigned)ceil_div(nqtiles, 4));
-    if (fold) hipLaunchKernelGGL(query_window_kernel<true>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, nq, qtpos, window, qthr, qlb, qrow_thr, dbg);
-    else hipLaunchKernelGGL(query_window_kernel<false>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, nq, qtpos, window, qthr, qlb, qrow_thr, dbg);
+    const dim3 grid((unsigned)ceil_div(ceil_div(nqtiles, PBN_WINDOW_NQ) * nparts, 4));
+    if (fold) hipLaunchKernelGGL(query_window_kernel<true>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, qtpos, window, nparts, part);
+    else hipLaunchKernelGGL(query_window_kernel<false>, grid, dim3(256), 0, st, Apack, nxpack, Bpack, nypack, ntiles, n_train, nqtiles, qtpos, window, nparts, part);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(query_window_finish_kernel, dim3((unsigned)ceil_div(nqtiles * 16, 256)), dim3(256), 0, st, part, nparts, nypack, nqtiles, nq, qthr, qlb, qrow_thr, dbg);
     HIP_CHECK(hipGetLastError());
 }
 
