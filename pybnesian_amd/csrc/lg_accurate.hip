@@ -10,9 +10,12 @@
 // centring, the pivoted Cholesky, the solves and the residual sum of squares (a Schur complement) run in double-double on the
 // host on (p+1)^2 numbers.  The result is the least-squares solution of the DATA to full double precision - at least as
 // accurate as the reference's Householder QR - at the cost of a rare extra pass; no N x (p+1) copy, no QR kernel.
-// Rank decision: a pivot below (eps (p+1))^2 of the largest one marks a dependent column (coefficient 0), the square of
-// ColPivHouseholderQR's default threshold on |R_kk| / |R_00| (the reference pivots the uncentred matrix with its ones column;
-// here the centred one: the decisions can only differ for kappa ~ 1e15).
+// Rank decision (lg_dd_solve.hpp, which holds the host solve and states the reason): a pivot marks a dependent column
+// (coefficient 0) when it is below (eps (p+1))^2 of the largest one - the square of ColPivHouseholderQR's default threshold on
+// |R_kk| / |R_00|; the reference pivots the uncentred matrix with its ones column, here the centred one: the decisions can only
+// differ for kappa ~ 1e15 - OR when it does not rise above the roundoff that the raw double-double moments carry into the
+// centred ones, 64 * 2^-104 * max(G_ii, C_ii * max_j G_jj / C_jj): with column means tens of sigma from zero that noise is far
+// above the first threshold, and an exactly dependent parent would otherwise keep a pivot of pure noise.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
@@ -21,63 +24,13 @@
 #include "common.hpp"
 #include "scoring_internal.hpp"
 
-// The error-free transformations below (TwoSum, TwoProd) are exact only if every operation is rounded exactly as
-// written: hipcc's default for device code, -ffp-contract=fast, would fuse the product of TwoProd into the first addition of
-// the following TwoSum (s = fma(x, y, acc) instead of acc + round(x y)) and silently turn the double-double accumulation
-// back into plain double.
-#pragma STDC FP_CONTRACT OFF
+#define PBN_DD_FN __host__ __device__ inline
+#include "lg_dd_solve.hpp"
 
 namespace pbn {
 namespace score {
 
 namespace {
-
-struct dd {
-    double hi, lo;
-};
-__host__ __device__ inline dd two_sum(double a, double b) {
-    const double s = a + b, bb = s - a;
-    return {s, (a - (s - bb)) + (b - bb)};
-}
-__host__ __device__ inline dd quick_two_sum(double a, double b) {
-    const double s = a + b;
-    return {s, b - (s - a)};
-}
-__host__ __device__ inline dd two_prod(double a, double b) {
-    const double p = a * b;
-    return {p, __builtin_fma(a, b, -p)};
-}
-__host__ __device__ inline dd dd_add(dd a, dd b) {
-    dd s = two_sum(a.hi, b.hi);
-    const dd t = two_sum(a.lo, b.lo);
-    s.lo += t.hi;
-    s = quick_two_sum(s.hi, s.lo);
-    s.lo += t.lo;
-    return quick_two_sum(s.hi, s.lo);
-}
-__host__ __device__ inline dd dd_add_prod(dd acc, double a, double b) { return dd_add(acc, two_prod(a, b)); }
-inline dd dd_neg(dd a) { return {-a.hi, -a.lo}; }
-inline dd dd_sub(dd a, dd b) { return dd_add(a, dd_neg(b)); }
-inline dd dd_mul(dd a, dd b) {
-    dd p = two_prod(a.hi, b.hi);
-    p.lo += a.hi * b.lo + a.lo * b.hi;
-    return quick_two_sum(p.hi, p.lo);
-}
-inline dd dd_div(dd a, dd b) {
-    const double q1 = a.hi / b.hi;
-    dd r = dd_sub(a, dd_mul(b, {q1, 0.0}));
-    const double q2 = r.hi / b.hi;
-    r = dd_sub(r, dd_mul(b, {q2, 0.0}));
-    const double q3 = r.hi / b.hi;
-    dd q = quick_two_sum(q1, q2);
-    return dd_add(q, {q3, 0.0});
-}
-inline dd dd_sqrt(dd a) {
-    if (!(a.hi > 0.0)) return {0.0, 0.0};
-    const double x = 1.0 / std::sqrt(a.hi), ax = a.hi * x;
-    const dd diff = dd_sub(a, two_prod(ax, ax));
-    return dd_add({ax, 0.0}, {diff.hi * (x * 0.5), 0.0});
-}
 
 constexpr int DD_MAX_D = 16;   // variable + up to 15 parents
 constexpr int DD_BLOCKS = 128;
@@ -167,8 +120,7 @@ __global__ __launch_bounds__(256) void gram_dd_kernel(DdGramArgs a) {
 
 // Raw moments of `d` columns over the described rows in double-double, then the exact least-squares fit.
 double lg_fit_accurate(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t n0, int64_t row1, int64_t n,
-                       const int32_t* dev_rows, double* beta) {
-    const int p = d - 1;
+                       const int32_t* dev_rows, double* beta, int* rank) {
     if (d > DD_MAX_D) throw invalid_error("lg_fit_accurate: more than 15 parents");
     pbn_ctx* ctx = t->ctx;
     const int ng = (d + 3) / 4, tiles = ng * (ng + 1) / 2;
@@ -209,64 +161,41 @@ double lg_fit_accurate(const pbn_table* t, const int* cols, int d, int64_t row0,
                 for (int j = 0; j < 4; ++j)
                     if (4 * J + j < d) S[4 * J + j] = acc[16 + j];
         }
-    // centred SSE and means
-    const dd N = {(double)n, 0.0};
-    std::vector<dd> C((size_t)d * d), mu(d);
-    for (int i = 0; i < d; ++i) mu[i] = dd_div(S[i], N);
-    for (int j = 0; j < d; ++j)
-        for (int i = 0; i < d; ++i) C[i + (size_t)j * d] = dd_sub(G[i + (size_t)j * d], dd_mul(S[i], mu[j]));
-    // diagonally pivoted Cholesky of the parents' block (indices 1..p), rank by the squared QR threshold
-    std::vector<int> piv(p);
-    std::iota(piv.begin(), piv.end(), 0);
-    std::vector<dd> L((size_t)p * p, dd{0, 0}), diag(p);
-    for (int i = 0; i < p; ++i) diag[i] = C[(i + 1) + (size_t)(i + 1) * d];
-    const double thr = std::pow(2.220446049250313e-16 * (double)std::min<int64_t>(n, d), 2.0);
-    int rank = 0;
-    double first = 0.0;
-    for (int k = 0; k < p; ++k) {
-        int best = k;
-        for (int j = k + 1; j < p; ++j)
-            if (diag[piv[j]].hi > diag[piv[best]].hi) best = j;
-        std::swap(piv[k], piv[best]);
-        // rows of L follow the pivot order: swap the already computed parts
-        for (int c2 = 0; c2 < k; ++c2) std::swap(L[k + (size_t)c2 * p], L[best + (size_t)c2 * p]);
-        const dd pk = diag[piv[k]];
-        if (k == 0) first = pk.hi;
-        if (!(pk.hi > thr * first) || !std::isfinite(pk.hi)) break;
-        const dd lkk = dd_sqrt(pk);
-        L[k + (size_t)k * p] = lkk;
-        for (int i = k + 1; i < p; ++i) {
-            dd v = C[(piv[i] + 1) + (size_t)(piv[k] + 1) * d];
-            for (int c2 = 0; c2 < k; ++c2) v = dd_sub(v, dd_mul(L[i + (size_t)c2 * p], L[k + (size_t)c2 * p]));
-            v = dd_div(v, lkk);
-            L[i + (size_t)k * p] = v;
-            diag[piv[i]] = dd_sub(diag[piv[i]], dd_mul(v, v));
-        }
-        rank = k + 1;
-    }
-    // forward / backward solves on the leading `rank` pivots; RSS = C_yy - |w|^2
-    std::vector<dd> w(rank), z(rank);
-    dd rss = C[0];
-    for (int i = 0; i < rank; ++i) {
-        dd v = C[0 + (size_t)(piv[i] + 1) * d];
-        for (int c2 = 0; c2 < i; ++c2) v = dd_sub(v, dd_mul(L[i + (size_t)c2 * p], w[c2]));
-        w[i] = dd_div(v, L[i + (size_t)i * p]);
-        rss = dd_sub(rss, dd_mul(w[i], w[i]));
-    }
-    for (int i = rank - 1; i >= 0; --i) {
-        dd v = w[i];
-        for (int c2 = i + 1; c2 < rank; ++c2) v = dd_sub(v, dd_mul(L[c2 + (size_t)i * p], z[c2]));
-        z[i] = dd_div(v, L[i + (size_t)i * p]);
-    }
-    std::vector<dd> b(p, dd{0, 0});
-    for (int i = 0; i < rank; ++i) b[piv[i]] = z[i];
-    dd b0 = mu[0];
-    for (int j = 0; j < p; ++j) b0 = dd_sub(b0, dd_mul(b[j], mu[j + 1]));
-    beta[0] = b0.hi;
-    for (int j = 0; j < p; ++j) beta[j + 1] = b[j].hi;
-    if (n <= p + 1) return INF;
-    return std::max(rss.hi, 0.0) / ((double)n - p - 1);
+    return lg_dd_solve(n, d, S.data(), G.data(), beta, rank);
 }
 
 }  // namespace score
 }  // namespace pbn
+
+using namespace pbn;
+using namespace pbn::score;
+
+extern "C" {
+
+// pbn_debug_lg_fit_accurate (test aid, not part of the C ABI header): lg_fit_accurate as its callers reach it, on any of its addressing
+// forms.  Logical row r < n is r < n0 ? row0 + r : row1 + (r - n0), an index into host_rows (n_rows entries, uploaded here) when that
+// is given and a table row otherwise; beta: d values, *rank: the number of parents the rank decision kept.  Every addressed row is
+// checked against the table before the launch.
+int pbn_debug_lg_fit_accurate(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t n0, int64_t row1, int64_t n,
+                              const int32_t* host_rows, int64_t n_rows, double* beta, double* variance, int* rank) {
+    return guarded(mu_of(t), [&] {
+        if (!t || !cols || !beta || !variance || !rank) throw invalid_error("pbn_debug_lg_fit_accurate: null argument");
+        if (d < 1 || d > DD_MAX_D) throw invalid_error("pbn_debug_lg_fit_accurate: between 1 and 16 columns");
+        for (int i = 0; i < d; ++i)
+            if (cols[i] < 0 || cols[i] >= t->n_cols) throw invalid_error("pbn_debug_lg_fit_accurate: column index out of range");
+        const int64_t limit = host_rows ? n_rows : t->n_rows;
+        if (n < 0 || n0 < 0 || n0 > n || row0 < 0 || row1 < 0 || limit < 0 || row0 + n0 > limit || row1 + (n - n0) > limit)
+            throw invalid_error("pbn_debug_lg_fit_accurate: row ranges out of bounds");
+        HIP_CHECK(hipSetDevice(t->ctx->device));
+        dev_buf<int32_t> rows;
+        if (host_rows) {
+            for (int64_t r = 0; r < n_rows; ++r)
+                if (host_rows[r] < 0 || host_rows[r] >= t->n_rows) throw invalid_error("pbn_debug_lg_fit_accurate: row list entry out of range");
+            rows.alloc((size_t)n_rows + 1);
+            if (n_rows > 0) HIP_CHECK(hipMemcpy(rows.p, host_rows, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+        }
+        *variance = lg_fit_accurate(t, cols, d, row0, n0, row1, n, rows.p, beta, rank);
+    });
+}
+
+}  // extern "C"

@@ -148,9 +148,9 @@ void stats_minus(const Stats& a, const Stats& b, Stats& out);
 // suspect (nullable, p >= 3 only): set when the normal equations cannot be trusted (see lg_fit) - refit with lg_fit_accurate
 double lg_fit(int64_t N, int p, const double* mu, const double* S, double* beta, bool* suspect = nullptr);
 // lg_accurate.hip: least-squares fit of cols[0] on cols[1..d-1] from double-double moments of the rows
-// r < n0 ? row0 + r : row1 + (r - n0), r < n (through dev_rows when given).  d <= 16.
+// r < n0 ? row0 + r : row1 + (r - n0), r < n (through dev_rows when given).  d <= 16.  *rank (nullable): parents kept.
 double lg_fit_accurate(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t n0, int64_t row1, int64_t n,
-                       const int32_t* dev_rows, double* beta);
+                       const int32_t* dev_rows, double* beta, int* rank = nullptr);
 bool lg_guard_on();   // PBN_LG_GUARD (default 1)
 double bic_lg(int64_t N, int p, double variance);
 double lg_slogl_from_rows(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t n, const int32_t* dev_rows,
