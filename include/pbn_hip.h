@@ -408,6 +408,39 @@ int pbn_clgnet_slogl(const pbn_clgnet* g, const pbn_dtable* dt, const pbn_table*
 /* evaluation-kernel launches and the rows they covered since creation */
 int pbn_clgnet_stats(const pbn_clgnet* g, int64_t* launches, int64_t* rows);
 
+/* ---- conditional linear Gaussian nodes: the fit of a network's CLinearGaussianCPDs in one device pass ---------------
+ * Replaces, for a list of nodes, DiscreteAdaptator<LinearGaussianCPD>::fit (factors/discrete/DiscreteAdaptator.hpp:
+ * 201-276: one MLE<LinearGaussianCPD>, learning/parameters/mle_LinearGaussianCPD.hpp, per configuration of the
+ * discrete parents, on the rows of that configuration).  The input is a PAIR of tables of the same rows, as
+ * pbn_clgnet_logl takes: a pbn_dtable of codes (-1 = null) and a pbn_table of continuous columns, either dtype.
+ * Node n: the continuous variable var[n] with the continuous parents cparents[cpar_off[n] .. cpar_off[n + 1]) - at most
+ * 7, columns of `t` - and the discrete parents dparents[dpar_off[n] .. dpar_off[n + 1]) - 1 to 7, columns of `dt`.  Its
+ * configuration index is sum code_j * stride_j, the first parent fastest (DiscreteAdaptator.hpp:201-260); a row with a
+ * -1 in any discrete parent of the node belongs to no configuration of it.  A CELL is a (node, configuration) pair:
+ * node n's cells are cell_off[n] .. cell_off[n + 1] (as many as the product of its parents' cardinalities, at most
+ * PBN_CLG_FIT_MAX_CONFIGS) and its records param_off[n] .. param_off[n + 1], p + 2 doubles a cell.
+ * Per cell: rows[cell] = its number of rows; status[cell] = 0 when it has none; 1 when it was fitted - its record then
+ * holds the p + 1 coefficients, intercept first, and the variance as MLE<LinearGaussianCPD> gives it (inf when the rows
+ * are at most p + 1); 2 when the fit cannot be trusted under the condition of pbn_lg_fit_table (nearly collinear
+ * parents or a nearly exact fit, p >= 3, PBN_LG_GUARD on): the record is zeros and the caller refits the cell from
+ * its rows (pbn_table_take, pbn_lg_fit_table).
+ * shift and moments (both nullable; for tests) return what the device pass produced, node after node and cell after
+ * cell: shift D = p + 1 doubles a cell, the pilot shift of each column - the column's value in the table's FIRST row,
+ * the variable first; moments D + D (D + 1) / 2 doubles a cell: the D sums of (x - shift), then the upper triangle of
+ * the products (x_i - shift_i)(x_j - shift_j) row by row ((0,0) (0,1) .. (0,D-1) (1,1) ..), accumulated in fp64 (a
+ * float column is widened first).  Deterministic: no floating-point atomics, one order of additions (tiles of
+ * PBN_CLG_FIT_TILE_ROWS rows, chunks of consecutive tiles added in chunk order); two calls on the same inputs return
+ * the same bits.  launches (nullable): kernel launches of the call; tables without rows are legal - every status 0,
+ * no launch.  PBN_ERR_INVALID: a null argument, tables of different row counts or contexts, a column outside its
+ * table or twice among a node's discrete parents, a node without discrete parents, with more than 7 of either kind
+ * of parent or more than PBN_CLG_FIT_MAX_CONFIGS configurations, offsets that do not match the cardinalities. */
+#define PBN_CLG_FIT_MAX_CONFIGS 256
+#define PBN_CLG_FIT_TILE_ROWS 1024
+int pbn_clg_fit(pbn_ctx* ctx, const pbn_dtable* dt, const pbn_table* t, int n_nodes, const int* var, const int* dpar_off,
+                const int* dparents, const int* cpar_off, const int* cparents, const int64_t* cell_off,
+                const int64_t* param_off, int64_t* rows, double* params, unsigned char* status, double* shift,
+                double* moments, int64_t* launches);
+
 /* ---- one process per GPU: the delta-score cache sharded BEHIND the boundary (shards the serial double
  * loops of learning/operators/operators.cpp:100-132,296-347 and the fold loop of learning/scores/cv_likelihood.cpp:5-25; the
  * reference is one process and has no counterpart).  The host supplies ONE collective - an all-gather of doubles - as a function

@@ -94,6 +94,8 @@ SIGNATURES = {
     "pbn_clgnet_logl": (_int, [_vp, _vp, _vp, _dp]),
     "pbn_clgnet_slogl": (_int, [_vp, _vp, _vp, _dp]),
     "pbn_clgnet_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "pbn_clg_fit": (_int, [_vp, _vp, _vp, _int, _ip, _ip, _ip, _ip, _ip, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _dp, C.POINTER(C.c_ubyte),
+                    _dp, _dp, C.POINTER(_i64)]),
     "pbn_scoredata_set_validity": (_int, [_vp, C.POINTER(_vp)]),
     "pbn_split_layout": (_int, [_i64, _int, _int, C.c_uint32, C.c_double, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_layout": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -868,10 +868,16 @@ class BayesianNetwork(BayesianNetworkBase):
 
         if self._fit_discrete(df):
             return
+        from . import clg_fit
+
         with shared_upload(default_context(), df, self._upload_columns()):   # one PCIe pass over the model's columns for all factors
             for n in self._nodes:
                 if not self._cpd_valid(n):
                     self._cpds[n] = self._new_factor(df, n)
+            # the CLinearGaussianCPD nodes with discrete parents - and, beside them, the DiscreteFactors - in ONE device pass (clg_fit.py);
+            # whatever it does not serve is still unfitted and takes the loop below
+            clg_fit.fit_nodes(self, df, [n for n in self._nodes if not self._cpds[n].fitted()])
+            for n in self._nodes:
                 if not self._cpds[n].fitted():
                     self._cpds[n].fit(df)
 
