@@ -647,6 +647,33 @@ int pbn_mi_set_continuous_nulls(pbn_mi* h, const unsigned char* flags, const dou
  * [v1, v2, cond...] over the rows valid in all of them, then the partial-correlation t-test with valid_rows - 2 - n_cond
  * degrees of freedom.  pbn_ci_pvalue_fn signature, user = a pbn_mi handle over continuous columns. */
 double pbn_mi_lincor_pvalue(void* user, int v1, int v2, int n_cond, const int* cond);
+/* The same test, many per call (continuous/linearcorrelation.cpp:20-122; pbn_ci_pvalue_batch_fn, user = the pbn_mi handle, indices
+ * through pbn_mi_set_order's order).  Rows without a null in any continuous column (clean rows) enter every test through one Gram of
+ * all columns, taken once per handle; the other (dirty) rows are walked per test by csrc/lincor_null_batch.hip, one test per lane, for
+ * conditioning sets of up to pbn_lincor_batch_max_cond() variables when a call holds at least the batch threshold of them (per set
+ * size).  CAP: handles of more than 256 continuous columns (an LDS tile of the kernel holds 16 rows of all columns), larger sets and
+ * smaller batches loop over pbn_mi_lincor_pvalue; so does every call while the environment holds PBN_LINCOR_NULL_BATCH=0 (read per
+ * call).  Device p-values agree with pbn_mi_lincor_pvalue's to rounding, inside pbn_mi_lincor_band() (relative) near the usual
+ * significance levels; a test whose block has an eigenvalue near the pseudo-inverse threshold, fewer than 32 degrees of freedom, or
+ * not more valid rows than variables is answered by pbn_mi_lincor_pvalue before the call returns - NaN and pbn_last_error as there. */
+void pbn_mi_lincor_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond,
+                                double* out);
+/* (continuous/linearcorrelation.cpp:20-122) cumulative counters of pbn_mi_lincor_pvalue_batch - tests answered by the device, tests
+ * looped over or handed back to the scalar routine, device tests recomputed by it - and the handle's clean and dirty rows (-1 before
+ * the first device batch counted them).  Any pointer may be NULL. */
+int pbn_mi_lincor_batch_stats(const pbn_mi* h, int64_t* device_tests, int64_t* host_tests, int64_t* host_redone,
+                              int64_t* clean_rows, int64_t* dirty_rows);
+/* (continuous/linearcorrelation.cpp:20-122) batches of fewer tests per conditioning-set size loop over the scalar routine; 0 sends
+ * every batch to the device.  Default: 20, far below pbn_lincor_set_batch_threshold's - the loop it replaces costs a launch and a
+ * wait per test (csrc/lincor_null_host.hpp has the measurement). */
+int pbn_mi_lincor_set_batch_threshold(pbn_mi* h, int64_t min_tests);
+/* (continuous/linearcorrelation.cpp:20-122) the relative band around alpha inside which a search must re-evaluate a p-value of
+ * pbn_mi_lincor_pvalue_batch through pbn_mi_lincor_pvalue to decide as the serial search does (the `band` of pbn_pc_estimate). */
+double pbn_mi_lincor_band(void);
+/* Test aid (continuous/linearcorrelation.cpp:20-122): the raw moments behind a batch of pbn_mi_lincor_pvalue_batch, per test the
+ * clean part, the dirty part and their sum; layout at its definition (csrc/lincor_null_batch.hip). */
+int64_t pbn_debug_mi_lincor_moments(pbn_mi* h, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond,
+                                    double* out, int64_t cap, int64_t* shape);
 /* joint_counts (factors/discrete/discrete_indices.cpp:134-150) of n_vars categorical variables of the handle: out has
  * prod(cardinality) entries, index = sum code_i * stride_i with the first variable fastest.  Serves BDe (learning/scores/
  * bde.cpp:5-50). */

@@ -128,6 +128,11 @@ SIGNATURES = {
     "pbn_mi_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_mi_set_continuous_nulls": (_int, [_vp, C.POINTER(C.c_ubyte), _dp]),
     "pbn_mi_lincor_pvalue": (C.c_double, [_vp, _int, _int, _int, _ip]),
+    "pbn_mi_lincor_pvalue_batch": (None, [_vp, _int, _ip, _ip, _ip, _ip, _dp]),
+    "pbn_mi_lincor_batch_stats": (_int, [_vp] + [C.POINTER(_i64)] * 5),
+    "pbn_mi_lincor_set_batch_threshold": (_int, [_vp, _i64]),
+    "pbn_mi_lincor_band": (C.c_double, []),
+    "pbn_debug_mi_lincor_moments": (_i64, [_vp, _int, _ip, _ip, _ip, _ip, _dp, _i64, C.POINTER(_i64)]),
     "pbn_mi_counts": (_int, [_vp, _int, _ip, _dp]),
     "pbn_kmi_create": (_int, [_vp, C.POINTER(_vp), _int, _i64, _int, C.c_uint32, _int, _int, C.POINTER(_vp)]),
     "pbn_kmi_destroy": (None, [_vp]),

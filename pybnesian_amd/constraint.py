@@ -33,6 +33,16 @@ def _callbacks(test, names, batched):
     return fn, batch, user, keep, errors
 
 
+def _band(test, band):
+    """The caller's band; left at -1, the test's own (`_pc_band`) when it has one - a batch whose rounding differs from the built-in
+    band's measurement brings its own."""
+    if band < 0:
+        own = getattr(test, "_pc_band", None)
+        if own is not None:
+            return float(own())
+    return float(band)
+
+
 def _pairs(buf, count):
     return [(buf[2 * i], buf[2 * i + 1]) for i in range(count)]
 
@@ -50,7 +60,7 @@ def pc_estimate_indices(test, names, n_interface=0, alpha=0.05, arc_blacklist=()
     sep_pair, sep_off = (C.c_int * (cap + 2))(), (C.c_int * (cap // 2 + 2))()
     sep_set, sep_p = (C.c_int * (n * (cap // 2) + 1))(), (C.c_double * (cap // 2 + 1))()
     tests = (C.c_int64 * 3)()
-    rc = _lib.load().pbn_pc_estimate(n, int(n_interface), fn, batch, user, float(alpha), float(band), len(arc_blacklist), _flat(arc_blacklist),
+    rc = _lib.load().pbn_pc_estimate(n, int(n_interface), fn, batch, user, float(alpha), _band(test, band), len(arc_blacklist), _flat(arc_blacklist),
                                      len(arc_whitelist), _flat(arc_whitelist), len(edge_blacklist), _flat(edge_blacklist), len(edge_whitelist),
                                      _flat(edge_whitelist), int(bool(use_sepsets)), float(ambiguous_threshold), int(bool(allow_bidirected)),
                                      _name_rank(list(names)), C.byref(n_arcs), arcs, C.byref(n_edges), edges, C.byref(n_sep), sep_pair, sep_off,
@@ -80,7 +90,7 @@ def pdag_orient_indices(test, names, n_interface, alpha, arcs, edges, arc_blackl
     out_arcs, out_edges = (C.c_int * (2 * cap))(), (C.c_int * (2 * cap))()
     n_arcs, n_edges = C.c_int(0), C.c_int(0)
     tests = (C.c_int64 * 3)()
-    rc = _lib.load().pbn_pdag_orient(n, int(n_interface), fn, batch, user, float(alpha), float(band), len(arcs), _flat(arcs), len(edges), _flat(edges),
+    rc = _lib.load().pbn_pdag_orient(n, int(n_interface), fn, batch, user, float(alpha), _band(test, band), len(arcs), _flat(arcs), len(edges), _flat(edges),
                                      len(arc_blacklist), _flat(arc_blacklist), len(arc_whitelist), _flat(arc_whitelist), int(bool(allow_bidirected)),
                                      _name_rank(list(names)), C.byref(n_arcs), out_arcs, C.byref(n_edges), out_edges, tests)
     if errors:

@@ -1056,6 +1056,7 @@ int pbn_mi_set_continuous_nulls(pbn_mi* h, const unsigned char* flags, const dou
             h->cont_null[i] = flags[i] ? 1 : 0;
             if (flags[i]) { h->shift[i] = shift[i]; h->any_null = true; }
         }
+        h->ln.ready = false;   // the clean rows' moments were taken under the old shifts
     });
 }
 

@@ -76,6 +76,21 @@ struct pbn_mi {
         int64_t device_tests = 0, host_tests = 0;
         int64_t threshold = -1;      // pbn_chisq_set_batch_threshold; negative: not set, chisq.hip's CHISQ_BATCH_MIN_TESTS
     } cs;
+    // pbn_mi_lincor_pvalue_batch (lincor_null_batch.hip): the split of the table's rows into clean ones (no NaN in any continuous
+    // column: one Gram of all columns serves every test) and dirty ones (kept as a compact row-major copy that the per-test kernel
+    // walks), built by the first batch; the grow-only buffers of a launch chunk; the counters of pbn_mi_lincor_batch_stats
+    struct LincorNullState {
+        bool ready = false;
+        int64_t n_clean = 0, n_dirty = 0;
+        pbn::dev_buf<char> dirty;        // [n_dirty][n_cont] in the table's dtype
+        pbn::dev_buf<double> clean;      // count, n_cont sums, n_cont x n_cont products of x - shift over the clean rows
+        pbn::dev_buf<double> shift;      // [n_cont]: h->shift as the state was built with it
+        pbn::dev_buf<int> idx;
+        pbn::dev_buf<double> part, out, rec;
+        pbn::dev_buf<unsigned char> flag;
+        int64_t device_tests = 0, host_tests = 0, host_redone = 0;
+        int64_t threshold = -1;          // pbn_mi_lincor_set_batch_threshold; negative: not set, LINCOR_NULL_BATCH_MIN_TESTS
+    } ln;
 };
 
 namespace pbn {

@@ -123,31 +123,60 @@ class LinearCorrelation(IndependenceTest):
     def _ci_callback(self, nodes):
         if self._per_test is not None:
             lib = _lib.load()
+            self._native_order = self._is_native_order(nodes)
             _lib.check(lib.pbn_mi_set_order(self._per_test._handle, len(nodes), _lib.int_array([self._idx(n) for n in nodes])))
             return C.cast(lib.pbn_mi_lincor_pvalue, C.c_void_p), self._per_test._handle, self, []
         # native fast path: the C function itself is the callback, no Python frame per test
-        self._native_order = all(n in self._index for n in nodes) and [self._index[n] for n in nodes] == list(range(len(nodes))) and len(nodes) == len(self._names)
+        self._native_order = self._is_native_order(nodes)
         if self._native_order:
             lib = _lib.load()
             return C.cast(lib.pbn_lincor_pvalue, C.c_void_p), self._handle, self, []
         return super()._ci_callback(nodes)
 
+    def _is_native_order(self, nodes):
+        return all(n in self._index for n in nodes) and [self._index[n] for n in nodes] == list(range(len(nodes))) and len(nodes) == len(self._names)
+
     def _pc_batch_callback(self):
         """Batched native callback for searches that guard their decisions against device rounding (PC's band): one test per lane on
-        the device for a handle made from a table, a host loop for one made from a covariance.  Only beside the native _ci_callback
-        (same handle, same index order); a table with nulls has no batch form."""
-        if self._per_test is not None or not getattr(self, "_native_order", False):
+        the device for a handle made from a table - with nulls, over each test's own valid rows (csrc/lincor_null_batch.hip) -, a host
+        loop for one made from a covariance.  Only beside the native _ci_callback (same handle, same index order)."""
+        if not getattr(self, "_native_order", False):
             return None
+        if self._per_test is not None:
+            return C.cast(_lib.load().pbn_mi_lincor_pvalue_batch, C.c_void_p)
         return C.cast(_lib.load().pbn_lincor_pvalue_batch, C.c_void_p)
+
+    def _pc_band(self):
+        """The relative band around alpha inside which a search re-evaluates this test's batched p-values one by one when the caller
+        names none; -1 leaves the search's built-in band."""
+        return _lib.load().pbn_mi_lincor_band() if self._per_test is not None else -1.0
+
+    def _null_stats(self):
+        v = [C.c_int64(0) for _ in range(5)]
+        _lib.check(_lib.load().pbn_mi_lincor_batch_stats(self._per_test._handle, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def batch_stats(self):
         """Cumulative (device tests, host tests, device tests recomputed on the host) of the batched callback."""
+        if self._per_test is not None:
+            return self._null_stats()[:3]
         d, h, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         _lib.check(_lib.load().pbn_lincor_batch_stats(self._handle, C.byref(d), C.byref(h), C.byref(r)))
         return d.value, h.value, r.value
 
+    def null_rows(self):
+        """(clean rows, dirty rows) of a table with nulls - rows without / with a null in some continuous column - once a device
+        batch has counted them; None before that and for a table without nulls."""
+        if self._per_test is None:
+            return None
+        clean, dirty = self._null_stats()[3:]
+        return None if clean < 0 else (clean, dirty)
+
     def set_batch_threshold(self, min_tests):
         """Batches of fewer tests (per conditioning-set size) loop on the host; 0 sends every batch to the device."""
+        if self._per_test is not None:
+            _lib.check(_lib.load().pbn_mi_lincor_set_batch_threshold(self._per_test._handle, int(min_tests)))
+            return
         _lib.check(_lib.load().pbn_lincor_set_batch_threshold(self._handle, int(min_tests)))
 
     def __del__(self):
