@@ -9,13 +9,13 @@
 // (test, row slice): every lane forms the keys of its rows from the code columns of the test and adds 1 into a table in LDS; the
 // workgroup then adds its table into the test's table in global memory.  No sort, no permutation, one launch per chunk of tests.
 //
-// LDS atomics on one address serialise: a 2 x 2 table takes the 64 lanes of a wave to 4 addresses, a constant column to 1.  The table is
-// therefore replicated R times (copies_for): a lane adds into copy (lane mod R), and the copies are staggered by one
-// bank, so that the lanes of a 32-lane group that meet in one cell are spread over R banks.  All sums are integer: neither the order of the LDS adds nor
-// the order in which the slices of a test reach global memory can change a count.
+// The counting itself is the joint-count kernel of joint_counts.hip in its LDS form under the BY_CARD policy: the null
+// bucket of a column, code == card, fails it.  What is kept here: decoding and eligibility of the requests, a descriptor per test,
+// chisq_from_counts, the capture / phase test aid and the scalar routine.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -28,153 +28,10 @@ namespace pbn {
 namespace chisq {
 
 constexpr int MAX_CELLS = 4096;            // cells of one contingency table counted on the device (pbn_chisq_batch_max_cells)
-constexpr int MAX_COND = 6;                // conditioning variables of a device test (pbn_chisq_batch_max_cond); fixes the descriptor's arrays
+constexpr int MAX_COND = 6;                // conditioning variables of a device test (pbn_chisq_batch_max_cond)
 constexpr int MAX_VARS = MAX_COND + 2;
-constexpr int BLOCK = 256;
-constexpr int LDS_WORDS = 8192;            // 32 KiB of counters per workgroup: five workgroups per CU of the 160 KiB
-constexpr int MAX_COPIES = 32;             // replicated sub-tables of one workgroup
-constexpr int ROWS_PER_LANE_U8 = 8;        // one 8-byte load per column and step
-constexpr int ROWS_PER_LANE_I32 = 4;       // four coalesced 4-byte loads per column and step
-constexpr int SLICE_ALIGN = BLOCK * ROWS_PER_LANE_U8;   // a slice starts on a multiple of it: the 8-byte loads stay aligned
-constexpr int MIRROR_ALIGN = 16;           // the byte mirror's leading dimension is a multiple of it (rows past N hold 0xFF)
-
-// One test = one contingency table.  key of a row = sum_j code[col[j]][row] * stride[j]; the row counts when code_j < card[j] for all j.
-struct Desc {
-    int m;                    // 2 + k variables: x, y, Z in the order given
-    int col[MAX_VARS];        // discrete column index
-    int stride[MAX_VARS];     // x fastest
-    int card[MAX_VARS];
-    int G;                    // prod card
-    int copies, copy_stride;  // R replicated sub-tables in LDS, copy c at c * copy_stride (copies_for)
-    int slices;               // workgroups of this test: slice s counts rows [row0 + s * rows_per_slice, ...) up to row1
-    int64_t table_off;        // first cell of its table in the launch's count buffer
-    int64_t row0, row1, rows_per_slice;
-};
-
-// R = the largest power of two <= r_max for which R padded tables fit LDS_WORDS.  The copy stride is G rounded up to the 32 banks a
-// 4-byte LDS atomic sees, plus one: cell c of copy r lies on bank (r + c) mod 32, so the lanes of a 32-lane group that hit one cell -
-// every lane, for a constant column - go to R different banks.  (Per 32-lane group: lanes l and l + 32 of a wave share a copy and are
-// served in different LDS passes, so more than 32 copies would buy nothing.)  One copy needs no padding.
-inline void copies_for(int G, int r_max, int* copies, int* copy_stride) {
-    const int padded = ((G + 31) & ~31) + 1;
-    int r = 1;
-    while (2 * r <= r_max && 2 * r <= MAX_COPIES && (int64_t)2 * r * padded <= LDS_WORDS) r *= 2;
-    *copies = r;
-    *copy_stride = r == 1 ? G : padded;
-}
-
-namespace {
-
-// CodeT = uint8_t: the byte mirror, ROWS_PER_LANE_U8 consecutive rows per lane and step from one 8-byte load per column.
-// CodeT = int32_t: the handle's codes as they are, ROWS_PER_LANE_I32 rows per lane and step, BLOCK rows apart (coalesced 4-byte loads;
-// the columns of codes_dev are N elements apart, which aligns nothing wider).
-template <typename CodeT>
-__global__ __launch_bounds__(BLOCK) void chisq_count_kernel(const Desc* __restrict__ descs, const CodeT* __restrict__ codes, int64_t ld,
-                                                             uint32_t* __restrict__ counts) {
-    extern __shared__ uint32_t cells[];   // [copies][copy_stride]
-    const Desc& d = descs[blockIdx.x];
-    const int slice = blockIdx.y;
-    if (slice >= d.slices) return;
-    const int tid = threadIdx.x, m = d.m, G = d.G, copies = d.copies, copy_stride = d.copy_stride;
-    const int words = copies * copy_stride;
-    for (int i = tid; i < words; i += BLOCK) cells[i] = 0u;
-    __syncthreads();
-    uint32_t* mine = cells + (tid & (copies - 1)) * copy_stride;
-    const int64_t r0 = d.row0 + (int64_t)slice * d.rows_per_slice;
-    const int64_t r1 = r0 + d.rows_per_slice < d.row1 ? r0 + d.rows_per_slice : d.row1;
-    if constexpr (sizeof(CodeT) == 1) {
-        constexpr int V = ROWS_PER_LANE_U8;
-        for (int64_t r = r0 + (int64_t)tid * V; r < r1; r += (int64_t)BLOCK * V) {
-            uint32_t key[V];
-#pragma unroll
-            for (int i = 0; i < V; ++i) key[i] = 0u;
-            uint32_t bad = 0u;
-            for (int j = 0; j < m; ++j) {
-                const uint2 v = *reinterpret_cast<const uint2*>(codes + (int64_t)d.col[j] * ld + r);
-                const uint32_t stride = (uint32_t)d.stride[j], card = (uint32_t)d.card[j];
-#pragma unroll
-                for (int i = 0; i < V; ++i) {
-                    const uint32_t c = ((i < 4 ? v.x : v.y) >> (8 * (i & 3))) & 0xFFu;
-                    key[i] += c * stride;
-                    bad |= (c >= card ? 1u : 0u) << i;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < V; ++i)
-                if (!((bad >> i) & 1u) && r + i < r1) atomicAdd(mine + key[i], 1u);
-        }
-    } else {
-        constexpr int V = ROWS_PER_LANE_I32;
-        for (int64_t r = r0 + tid; r < r1; r += (int64_t)BLOCK * V) {
-            uint32_t key[V];
-#pragma unroll
-            for (int i = 0; i < V; ++i) key[i] = 0u;
-            uint32_t bad = 0u;
-#pragma unroll
-            for (int i = 0; i < V; ++i) bad |= (r + (int64_t)i * BLOCK < r1 ? 0u : 1u) << i;
-            for (int j = 0; j < m; ++j) {
-                const CodeT* col = codes + (int64_t)d.col[j] * ld + r;
-                const uint32_t stride = (uint32_t)d.stride[j], card = (uint32_t)d.card[j];
-#pragma unroll
-                for (int i = 0; i < V; ++i) {
-                    const uint32_t c = ((bad >> i) & 1u) ? card : (uint32_t)col[(int64_t)i * BLOCK];
-                    key[i] += c * stride;
-                    bad |= (c >= card ? 1u : 0u) << i;
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < V; ++i)
-                if (!((bad >> i) & 1u)) atomicAdd(mine + key[i], 1u);
-        }
-    }
-    __syncthreads();
-    // flush: the R copies of a cell, summed; a test of one slice owns its table (plain stores over the zeroed buffer)
-    uint32_t* out = counts + d.table_off;
-    const bool single = d.slices == 1;
-    for (int cell = tid; cell < G; cell += BLOCK) {
-        uint32_t s = 0u;
-        for (int c = 0; c < copies; ++c) s += cells[c * copy_stride + cell];
-        if (s == 0u) continue;
-        if (single) out[cell] = s;
-        else atomicAdd(out + cell, s);
-    }
-}
-
-// one thread packs four rows of one column
-__global__ __launch_bounds__(BLOCK) void chisq_byte_mirror_kernel(const int32_t* __restrict__ codes, int64_t n, uint8_t* __restrict__ mirror,
-                                                                   int64_t ld8) {
-    const int64_t r = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) * 4;
-    if (r >= ld8) return;
-    const int32_t* col = codes + (int64_t)blockIdx.y * n;
-    uint32_t packed = 0u;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) packed |= (r + i < n ? (uint32_t)col[r + i] & 0xFFu : 0xFFu) << (8 * i);
-    *reinterpret_cast<uint32_t*>(mirror + (int64_t)blockIdx.y * ld8 + r) = packed;
-}
-
-// descs: n_tests descriptors in device memory; codes: the byte mirror ([n_disc][ld], bytes = true) or the handle's int32 codes; the
-// count buffer must be zero where a test has more than one slice.  lds_words = max over the tests of copies * copy_stride.
-void launch_count(const Desc* descs, int n_tests, int max_slices, int lds_words, bool bytes, const void* codes, int64_t ld, uint32_t* counts,
-                  hipStream_t stream) {
-    if (n_tests <= 0) return;
-    if (lds_words < 1 || lds_words > LDS_WORDS || max_slices < 1 || max_slices > 65535) throw invalid_error("ChiSquare batch: bad launch shape");
-    const dim3 grid((unsigned)n_tests, (unsigned)max_slices), block(BLOCK);
-    const size_t lds = (size_t)lds_words * sizeof(uint32_t);
-    if (bytes) hipLaunchKernelGGL(chisq_count_kernel<uint8_t>, grid, block, lds, stream, descs, (const uint8_t*)codes, ld, counts);
-    else hipLaunchKernelGGL(chisq_count_kernel<int32_t>, grid, block, lds, stream, descs, (const int32_t*)codes, ld, counts);
-    HIP_CHECK(hipGetLastError());
-}
-
-// mirror[j * ld8 + r] = (uint8_t)codes[j * n + r], 0xFF in the padding rows n ... ld8 - 1 (ld8 a multiple of MIRROR_ALIGN)
-void launch_byte_mirror(const int32_t* codes, int64_t n, int n_disc, uint8_t* mirror, int64_t ld8, hipStream_t stream) {
-    if (n_disc <= 0 || ld8 <= 0) return;
-    if (ld8 % MIRROR_ALIGN != 0 || ld8 < n) throw invalid_error("ChiSquare batch: bad mirror shape");
-    hipLaunchKernelGGL(chisq_byte_mirror_kernel, dim3((unsigned)ceil_div(ld8 / 4, BLOCK), (unsigned)n_disc), dim3(BLOCK), 0, stream, codes, n, mirror,
-                       ld8);
-    HIP_CHECK(hipGetLastError());
-}
-
-}  // namespace
+static_assert(joint::MAX_VARS >= MAX_VARS, "x, y and the conditioning set fit the descriptor");
+static_assert(MAX_CELLS <= joint::LDS_WORDS, "a table fits the LDS form");
 
 }  // namespace chisq
 }  // namespace pbn
@@ -229,8 +86,8 @@ struct ChisqTest {   // one slot of a batch call
     int slices = 0, copies = 0;
 };
 
-// The device part of pbn_chisq_pvalue_batch: the tests `which` (all eligible), chunk by chunk - descriptors up, one memset, one launch,
-// the chunk's tables down, chisq_from_counts on the host threads.  `tables` (capture only) receives every test's integer table.
+// The device part of pbn_chisq_pvalue_batch: the tests `which` (all eligible), chunk by chunk through joint::run_chunk, then
+// chisq_from_counts on the host threads.  `tables` (capture only) receives every test's integer table.
 void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vector<int>& which, const int* cond_off, double* out, int* width,
                         std::vector<std::vector<uint32_t>>* tables) {
     pbn_ctx* ctx = h->ctx;
@@ -239,8 +96,8 @@ void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vec
     const int64_t N = h->N;
     const bool timing = (g_chisq_capture.load() & 2) != 0;
     double tp = mi_now();
-    auto phase = [&](int i) {
-        if (!timing) return;
+    std::function<void(int)> phase;   // the phase clock: request and descriptors, memset, kernel, download
+    if (timing) phase = [&](int i) {
         HIP_CHECK(hipStreamSynchronize(st));
         const double t = mi_now();
         g_chisq_phase[i] += t - tp;
@@ -254,31 +111,32 @@ void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vec
         h->cs.codes8_state = -1;
         static const bool allow = PBN_TUNE(CHISQ_BYTES, 1) != 0;
         if (allow && max_code <= 255 && h->n_disc <= 65535) {
-            h->cs.ld8 = ceil_div(N, chisq::MIRROR_ALIGN) * chisq::MIRROR_ALIGN;
+            h->cs.ld8 = ceil_div(N, joint::MIRROR_ALIGN) * joint::MIRROR_ALIGN;
             h->cs.codes8.alloc((size_t)h->cs.ld8 * h->n_disc);
-            chisq::launch_byte_mirror(h->codes_dev.p, N, h->n_disc, h->cs.codes8.p, h->cs.ld8, st);
+            joint::byte_mirror(ctx, h->codes_dev.p, N, h->n_disc, h->cs.codes8.p, h->cs.ld8);
             h->cs.codes8_state = 1;
         }
     }
     const bool bytes = h->cs.codes8_state == 1;
     *width = bytes ? 1 : 4;
-    static const int r_max = PBN_TUNE(CHISQ_COPIES, chisq::MAX_COPIES);
+    joint::Codes codes;
+    codes.codes32 = h->codes_dev.p; codes.ld32 = N;
+    if (bytes) { codes.codes8 = h->cs.codes8.p; codes.ld8 = h->cs.ld8; }
+    static const int r_max = PBN_TUNE(CHISQ_COPIES, joint::MAX_COPIES);
     static const int blocks_per_cu = PBN_TUNE(CHISQ_BLOCKS_PER_CU, 8);
-    std::vector<chisq::Desc> descs;
+    std::vector<joint::Desc> both[2];   // every test takes the LDS form
+    std::vector<joint::Desc>& descs = both[0];
     for (size_t base = 0; base < which.size();) {
         // a chunk: as many tests as keep the count buffer within CHISQ_CHUNK_CELLS
         size_t end = base, cells = 0;
         while (end < which.size() && end - base < ((size_t)1 << 18) && cells + (size_t)tests[which[end]].G <= CHISQ_CHUNK_CELLS) cells += (size_t)tests[which[end++]].G;
         const int T = (int)(end - base);
-        // slices: enough workgroups to fill the chip when the chunk has few tests, while a slice's flush (G cells) stays small against
-        // its row work: at least max(4096, 8 G) rows per slice, slice bounds on multiples of SLICE_ALIGN
-        const int64_t want = std::max<int64_t>(1, ceil_div((int64_t)ctx->num_cus * blocks_per_cu, T));
-        descs.assign((size_t)T, chisq::Desc{});
-        int max_slices = 1, lds_words = 1;
+        const int64_t want = std::max<int64_t>(1, ceil_div((int64_t)ctx->num_cus * blocks_per_cu, T));   // slices that fill the chip (plan_slices)
+        descs.assign((size_t)T, joint::Desc{});
         size_t off = 0;
         for (int i = 0; i < T; ++i) {
             ChisqTest& t = tests[which[base + i]];
-            chisq::Desc& d = descs[i];
+            joint::Desc& d = descs[i];
             d.m = t.m; d.G = t.G;
             int stride = 1;
             for (int j = 0; j < t.m; ++j) {
@@ -287,32 +145,13 @@ void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vec
                 d.stride[j] = stride;
                 stride *= d.card[j];
             }
-            chisq::copies_for(t.G, r_max, &d.copies, &d.copy_stride);
-            const int64_t cap = std::max<int64_t>(1, N / std::max<int64_t>(4096, 8 * (int64_t)t.G));
-            const int64_t s = std::min<int64_t>(std::min(want, cap), 65535);
-            d.rows_per_slice = ceil_div(ceil_div(N, s), chisq::SLICE_ALIGN) * chisq::SLICE_ALIGN;
-            d.slices = (int)ceil_div(N, d.rows_per_slice);
-            d.row0 = 0; d.row1 = N;
+            joint::plan_slices(d, 0, N, bytes, true, want, r_max);
             d.table_off = (int64_t)off;
             off += (size_t)t.G;
             t.slices = d.slices; t.copies = d.copies;
-            max_slices = std::max(max_slices, d.slices);
-            lds_words = std::max(lds_words, d.copies * d.copy_stride);
         }
-        h->cs.descs.reserve((size_t)T);
-        h->cs.counts.reserve(cells);
-        if (h->cs.host.size() < cells) h->cs.host.resize(cells);
-        HIP_CHECK(hipMemcpyAsync(h->cs.descs.p, descs.data(), (size_t)T * sizeof(chisq::Desc), hipMemcpyHostToDevice, st));
-        phase(0);
-        HIP_CHECK(hipMemsetAsync(h->cs.counts.p, 0, cells * sizeof(uint32_t), st));
-        phase(1);
-        chisq::launch_count(h->cs.descs.p, T, max_slices, lds_words, bytes, bytes ? (const void*)h->cs.codes8.p : (const void*)h->codes_dev.p,
-                            bytes ? h->cs.ld8 : N, h->cs.counts.p, st);
-        phase(2);
-        HIP_CHECK(hipMemcpyAsync(h->cs.host.data(), h->cs.counts.p, cells * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));   // (the descriptors are read by then as well)
-        phase(3);
-        const uint32_t* all = h->cs.host.data();
+        joint::run_chunk(ctx, h->cs.scratch, both, cells, codes, joint::BY_CARD, phase);
+        const uint32_t* all = h->cs.scratch.host.data();
         host_finish(T, [&](int i) {
             const int slot = which[base + i];
             const ChisqTest& t = tests[slot];

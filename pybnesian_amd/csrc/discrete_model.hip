@@ -3,7 +3,7 @@
 // models/BayesianNetwork.hpp:960-994 fit / logl / slogl of the network) - instead of one host pass over all rows per node.
 //
 // pbn_dtable: the dictionary codes of a table on the device, outside any score data and WITH nulls (code -1; 0xFF in the byte mirror,
-// which exists when every cardinality is <= 255 - no valid code is 0xFF then).  Its family tables come from family_count_kernel's
+// which exists when every cardinality is <= 255 - no valid code is 0xFF then).  Its family tables come from the joint-count kernel's
 // null-aware instantiations (family_counts.hip): a row with a null in any variable of a family is left out of that family's table.
 //
 // pbn_dnet: the concatenated CPTs of a fitted network.  dnet_logl_kernel evaluates all nodes for a tile of rows: a lane owns 8 consecutive
@@ -251,9 +251,9 @@ int pbn_dtable_create(pbn_ctx* ctx, int64_t n_rows, int n_cols, const int32_t* c
                 HIP_CHECK(hipMemcpyAsync(dt->codes_dev.p + (size_t)j * n_rows, dt->codes[j].data(), (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice,
                                          ctx->stream));
             if (*std::max_element(dt->card.begin(), dt->card.end()) <= 255 && n_cols <= 65535) {
-                dt->ld8 = ceil_div(n_rows, FAMILY_MIRROR_ALIGN) * FAMILY_MIRROR_ALIGN;
+                dt->ld8 = ceil_div(n_rows, joint::MIRROR_ALIGN) * joint::MIRROR_ALIGN;
                 dt->codes8.alloc((size_t)dt->ld8 * n_cols);
-                family_byte_mirror(ctx, dt->codes_dev.p, n_rows, n_cols, dt->codes8.p, dt->ld8);   // -1 & 0xFF = 0xFF: the null byte
+                joint::byte_mirror(ctx, dt->codes_dev.p, n_rows, n_cols, dt->codes8.p, dt->ld8);   // -1 & 0xFF = 0xFF: the null byte
             }
             HIP_CHECK(hipStreamSynchronize(ctx->stream));
         }

@@ -6,8 +6,7 @@
 #include <vector>
 
 #include "common.hpp"
-
-namespace pbn { namespace chisq { struct Desc; } }   // chisq.hip
+#include "joint_counts.hpp"
 
 // Rows grouped by the configuration of one set of discrete variables (sorted ids, first id fastest): `perm` lists the
 // rows configuration by configuration, ascending inside a configuration (stable radix sort), `off` are the segment
@@ -65,14 +64,12 @@ struct pbn_mi {
     // test aid (pbn_debug_mi_moments, mi.hip): non-null only inside its call - one record per plan of the batch, filled by group_stats_many
     std::vector<int64_t>* dbg = nullptr;
     // pbn_chisq_pvalue_batch (chisq.hip): the byte mirror of the codes ([n_disc][ld8], built by the first batch when every code fits a
-    // byte), the grow-only descriptor / count buffers of a launch chunk and the host copy of the counts
+    // byte) and the scratch of a launch chunk (joint_counts.hpp)
     struct ChisqState {
         pbn::dev_buf<uint8_t> codes8;
         int64_t ld8 = 0;
         int codes8_state = 0;        // 0 not tried yet, 1 built, -1 the codes need int32
-        pbn::dev_buf<pbn::chisq::Desc> descs;
-        pbn::dev_buf<uint32_t> counts;
-        std::vector<uint32_t> host;
+        pbn::joint::Scratch scratch;
         int64_t device_tests = 0, host_tests = 0;
         int64_t threshold = -1;      // pbn_chisq_set_batch_threshold; negative: not set, chisq.hip's CHISQ_BATCH_MIN_TESTS
     } cs;

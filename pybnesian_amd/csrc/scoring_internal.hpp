@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "joint_counts.hpp"
 
 namespace pbn {
 struct KdeModel;     // kde_model.hpp
@@ -34,12 +35,10 @@ struct Stats {  // pilot-shifted moments of a row set over all n columns (or a c
     }
 };
 
-// What a family-count pass (family_counts.hip) keeps between calls: a launch chunk's descriptors, count buffer and its host copy
-// (grow-only), and the counters behind pbn_scoredata_discrete_stats.  Score data and a pbn_dtable (discrete_model.hip) each own one.
+// What a family-count pass (family_counts.hip) keeps between calls: the scratch of a launch chunk (joint_counts.hpp) and the counters
+// behind pbn_scoredata_discrete_stats.  Score data and a pbn_dtable (discrete_model.hip) each own one.
 struct FamilyScratch {
-    pbn::dev_buf<char> fc_descs;
-    pbn::dev_buf<uint32_t> fc_counts;
-    std::vector<uint32_t> fc_host;
+    pbn::joint::Scratch fc;
     int64_t fc_device_units = 0, fc_host_units = 0, fc_launches = 0;
 };
 
@@ -254,22 +253,15 @@ void count_families(pbn_scoredata* sd, const std::vector<Region>& regions, const
 // <= 255; 0xFF in the rows past the last).  nulls: a code < 0 (0xFF in the mirror) is a null, and a row with a null in any column of a
 // family is left out of that family's tables; without it no code may be negative.  `which` indexes the families to count - each must
 // pass family_fits_device - and the regions are row ranges of the table.
-struct FamilyCodes {
+struct FamilyCodes : pbn::joint::Codes {
     pbn_ctx* ctx = nullptr;
     FamilyScratch* scratch = nullptr;
     const int* card = nullptr;       // per column
-    const int32_t* codes32 = nullptr;
-    int64_t ld32 = 0;
-    const uint8_t* codes8 = nullptr;
-    int64_t ld8 = 0;
     bool nulls = false;
 };
 bool family_fits_device(const Family& f);
 void count_families_device(const FamilyCodes& src, const std::vector<Region>& regions, const std::vector<Family>& fams, const std::vector<size_t>& which,
                            const FamilySink& sink);
-// int32 codes [n_cols][rows] on the device -> the byte mirror [n_cols][ld8] (enqueued on the context's stream)
-void family_byte_mirror(pbn_ctx* ctx, const int32_t* codes_dev, int64_t rows, int n_cols, uint8_t* mirror, int64_t ld8);
-constexpr int FAMILY_MIRROR_ALIGN = 16;   // ld8 is a multiple of it
 void family_counts_host(const pbn_scoredata* sd, const std::vector<Region>& regions, const Family& f, std::vector<std::vector<int64_t>>& tables);
 void family_codes_upload(pbn_scoredata* sd);   // after pbn_scoredata_set_discrete filled sd->codes
 Family make_family(const pbn_scoredata* sd, int var, const int* parents, int p);   // column ids of the score data; sorts the parents
