@@ -668,6 +668,11 @@ __device__ __forceinline__ void kde_sweep_body(const SweepArgs& a, const unsigne
                                                                       (((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split + ((bt - t0) >> 6)) * QG;
 #pragma unroll
                             for (int g = 0; g < QG; ++g) lv[g] = lp[g];
+                            if (a.far_mask) {   // round 16: the far blocks are kde_sweep_far32_d8_kernel's
+                                const PBN_GLOBAL unsigned long long* fp = (const PBN_GLOBAL unsigned long long*)a.far_mask + (lp - (const PBN_GLOBAL unsigned long long*)a.live_mask);
+#pragma unroll
+                                for (int g = 0; g < QG; ++g) lv[g] &= ~fp[g];
+                            }
                         } else {
 #pragma unroll
                             for (int g = 0; g < QG; ++g) lv[g] = 0;
@@ -979,6 +984,8 @@ static void launch_sweep_t(const SweepArgs& a, int KS, dim3 grid, hipStream_t st
 #include "kde_sweep_f16.inc"
 // ... and so is the f16 screen of the pruned d = 8 sweep: it counts into this unit's g_sweep_visit / g_sweep_tiles
 #include "kde_screen_d8.inc"
+// ... and the far pass behind it (round 16)
+#include "kde_far32_d8.inc"
 
 void launch_pack(const PackArgs& a, int dtype, hipStream_t st) {
     const int64_t npad = a.ntiles * 16;
@@ -1046,6 +1053,12 @@ extern "C" void pbn_debug_d8_screen(unsigned long long* kept, unsigned long long
     if (tested) (void)hipMemcpyFromSymbol(tested, HIP_SYMBOL(pbn::g_screen_tested), sizeof z);
     if (reset) { (void)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_screen_kept), &z, sizeof z); (void)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_screen_tested), &z, sizeof z); }
 }
+// ... and, of the kept blocks, those it marked far for kde_sweep_far32_d8_kernel (counted like the two above: PBN_SWEEP_COUNT_REDO)
+extern "C" void pbn_debug_d8_screen_far(unsigned long long* far, int reset) {
+    unsigned long long z = 0;
+    if (far) (void)hipMemcpyFromSymbol(far, HIP_SYMBOL(pbn::g_screen_far), sizeof z);
+    if (reset) (void)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_screen_far), &z, sizeof z);
+}
 extern "C" void pbn_debug_w32_launches(unsigned long long* n, int reset) {
     if (n) *n = pbn::g_w32_launches.load();
     if (reset) pbn::g_w32_launches.store(0);
@@ -1062,4 +1075,15 @@ extern "C" void pbn_debug_sweep_visits(unsigned long long* visited, unsigned lon
     if (visited) (void)hipMemcpyFromSymbol(visited, HIP_SYMBOL(pbn::g_sweep_visit), sizeof z);
     if (tiles) (void)hipMemcpyFromSymbol(tiles, HIP_SYMBOL(pbn::g_sweep_tiles), sizeof z);
     if (reset) { (void)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_sweep_visit), &z, sizeof z); (void)hipMemcpyToSymbol(HIP_SYMBOL(pbn::g_sweep_tiles), &z, sizeof z); }
+}
+
+
+// test aids, not part of the C ABI header: the rule's numbers (eps at ncap, theta for n rows) and the far pass's launches since the last reset
+extern "C" void pbn_debug_far32_rule(double ncap, long long n_train, double* eps, double* theta) {
+    if (eps) *eps = pbn::far32_term_error(ncap);
+    if (theta) *theta = pbn::far32_theta(n_train);
+}
+extern "C" void pbn_debug_far32_launches(unsigned long long* n, int reset) {
+    if (n) *n = pbn::g_far32_launches.load();
+    if (reset) pbn::g_far32_launches.store(0);
 }

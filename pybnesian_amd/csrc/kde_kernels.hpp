@@ -202,7 +202,27 @@ struct SweepArgs {
     // (query_window_kernel), else the tile's.  The budget argument is per query: a dropped term lies below 2^-margin of its own query's sum bound.
     // The screen kernels alone read it; null (no window pass, PBN_D8_SCREEN_ROWTHR=0) = every column against qtile_thr of its group.
     const double* qrow_thr;          // [nqtiles * 16]
+    // Round 16: the far pass (kde_far32_d8.inc).  Beside each live word the screen writes a FAR word: the live blocks of plain tiles all of whose
+    // 256 screened exponents lie below their own column's qrow_thr less far_theta - every pair proven far_theta bits below its own query's
+    // sum.  The fp64 sweep visits live & ~far, kde_sweep_far32_d8_kernel evaluates the far blocks with fp32 MFMAs into a second set of
+    // nsplit partial rows behind the sweep's.  far_mask null = no far words (the step is the one without the pass, bit for bit).
+    unsigned long long* far_mask;             // the layout of live_mask
+    const unsigned long long* tile_plain;     // bit (t & 63) of word t >> 6: none of tile t's 16 rows is padding or has 1/2|z|^2 > PBN_FAR32_NCAP
+                                              // (far_plain_kernel at fit time; ceil(ntiles / 64) + 1 words, the last one 0)
+    double far_theta;                         // far32_theta(n_train)
+    const void* far_pack;                     // [ntiles][768 B]: the training fragments and norms in fp32, the far pass's own order (far_pack_kernel)
 };
+
+// The far pass's two constants (kde_far32_d8.inc has the bound they come from).  NCAP: the largest 1/2|z|^2 (base-2 exponent units) of a row, on
+// either side, that the fp32 evaluation takes; THETA: bits below its own query's sum bound at which a pair may be evaluated in fp32, at 10^6
+// training rows - for n rows that + log2(n / 10^6), as the pruning margin moves, so that N 2^-theta is the same fraction of a sum at every size.
+#define PBN_FAR32_NCAP 256.0
+#define PBN_FAR32_BIAS 64.0
+#define PBN_FAR32_BUDGET 8e-8
+// relative error of one fp32 term and the theta that keeps n of them inside PBN_FAR32_BUDGET of a sum (host; tests read them through
+// pbn_debug_far32_rule)
+double far32_term_error(double ncap);
+double far32_theta(int64_t n_train);
 
 // Position along the Hilbert curve of a cell in n = 2 ... 4 dimensions, `bits` bits per axis (Skilling's transpose form: undo the excess rotations
 // from the top bit down, Gray-encode, interleave with axis 0 most significant) - consecutive keys are neighbouring cells, so 16 consecutive rows of
@@ -352,6 +372,11 @@ void launch_sweep(const SweepArgs& a, int dtype, int KS, bool cond, int nsplit, 
 void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t ntiles, bool is_query, void* out, hipStream_t st);
 // (which = PBN_D8_SCREEN_STREAM: 0 the serial kernel, 1 the two-phase kernel with its ring of fragment loads over a pair list, else the dense kernel)
 void launch_screen_d8(const SweepArgs& a, int nsplit, int which, hipStream_t st);
+// the far pass of that sweep (round 16): SweepArgs::tile_plain from the packed training norms (nxpack, [ntiles * 16]), at fit time; and the fp32
+// evaluation of the blocks in SweepArgs::far_mask, launched with the sweep's arguments and nsplit - partial rows nsplit .. 2 nsplit - 1 of SweepArgs::part
+void launch_far_plain(const double* norms, int64_t ntiles, unsigned long long* out, hipStream_t st);
+void launch_far_pack(const void* Apack, const void* nxpack, int64_t ntiles, void* out, hipStream_t st);   // SweepArgs::far_pack, at fit time
+void launch_sweep_far32_d8(const SweepArgs& a, int nsplit, hipStream_t st);
 void launch_finish(const FinishArgs& a, bool cond, double* dev_sum_out, hipStream_t st, double* dev_sum_marg_out = nullptr);
 // out[0] = sum of in[0 .. n), fixed order (kde_finish.hip; launch_ucv in kde_cdf.hip ends with it too - a call between two units of the
 // library, not one of its exports)

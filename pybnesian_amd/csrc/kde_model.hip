@@ -390,6 +390,8 @@ void kde_pack_train(pbn_ctx* ctx, KdeModel& m, const pbn_table* t, const int* co
     if (dev_max_norm2 && m.dtype == PBN_F32 && !m.widen) launch_max_norm2(pa, t->dtype, dev_max_norm2, ctx->stream);
     m.prune = false;
     m.scr = nullptr;
+    m.far_plain = nullptr;
+    m.far_pack = nullptr;
     const bool rot = prune && kde_prune_rotates(m);
     if (rot || (prune && kde_prune_applies(m.fdtype(), m.dm, m.N))) {
         auto al = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -447,8 +449,10 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store) {
     const SubBytes sb = sub_bytes(m, m.nsub);
     // the operands of the d = 8 screen (PBN_D8_SCREEN, read here and at every evaluation: 0 at either keeps today's path)
     const bool screen = m.wfull && !m.cond && m.dm == 8 && m.zdims == 8 && m.pdims == PBN_PRUNE_PD && m.fdtype() == PBN_F64 && knob_int("PBN_D8_SCREEN", 1) != 0;
-    const size_t sub_b = m.nsub ? al(sb.total) : 0, scr_b = screen ? (size_t)m.ntiles * 16 * 32 : 0;
-    store.alloc(box_b + zs_b + key_b + sub_b + scr_b);
+    const size_t sub_b = m.nsub ? al(sb.total) : 0, scr_b = screen ? al((size_t)m.ntiles * 16 * 32) : 0;
+    const size_t plain_b = screen ? al((size_t)(ceil_div(m.ntiles, 64) + 1) * sizeof(unsigned long long)) : 0;   // the far pass's plain bits
+    const size_t fpack_b = screen ? al((size_t)m.ntiles * 768) : 0;   // ... and its fp32 fragments (launch_far_pack)
+    store.alloc(box_b + zs_b + key_b + sub_b + scr_b + plain_b + fpack_b);
     HIP_CHECK(hipMemcpyAsync(store.p, m.tile_box, box_b, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(store.p + box_b, m.zsorted, (size_t)m.N * m.zdims * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(store.p + box_b + zs_b, m.keys_sorted, (size_t)m.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
@@ -466,6 +470,10 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store) {
         KernelTimer kt(ctx, PBN_K_PACK);
         launch_screen_pack(m.zsorted, nullptr, m.N, m.ntiles, false, sp, ctx->stream);
         m.scr = sp;
+        launch_far_plain((const double*)m.nxpack, m.ntiles, (unsigned long long*)(sp + scr_b), ctx->stream);
+        m.far_plain = (const unsigned long long*)(sp + scr_b);
+        launch_far_pack(m.Apack, m.nxpack, m.ntiles, sp + scr_b + plain_b, ctx->stream);
+        m.far_pack = sp + scr_b + plain_b;
     }
 }
 
@@ -478,7 +486,7 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store) {
 static std::atomic<bool> g_masks_capture{false};
 static std::mutex g_masks_mu;
 struct MaskDump {
-    std::vector<unsigned long long> box, live;
+    std::vector<unsigned long long> box, live, far;   // far: empty where the launch wrote no far words
     std::vector<double> qthr, zq, zt;  // per query tile: see above; the sorted queries' / training rows' whitened rows [n][8]
     std::vector<double> qrow;          // per sorted query, padding columns included [nqtiles * 16]
     long long dims[6] = {0, 0, 0, 0, 0, 0};   // sweep waves, splits, batches per split, tiles per split, training tiles, queries
@@ -660,7 +668,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     const size_t part_b = ((size_t)nsplit * nqtiles * 16 * P * sizeof(double) + 255) / 256 * 256;
     const size_t bbox_b = bboxes ? ((size_t)nsplit * ceil_div(tps, 64) * 2 * m.pdims * sizeof(double) + 255) / 256 * 256 : 0;
     // The f16 screen of the sum-only d = 8 sweep (kde_screen_d8.inc): the queries' operands and the mask words behind the batch boxes, in the same
-    // grow-only arena in stream order.  One 64-bit word per (sweep wave, batch of a split, group): 51 MB at 1e6 x 1e5 rows; beyond
+    // grow-only arena in stream order.  One 64-bit word per (sweep wave, batch of a split, group): 51 MB at 1e6 x 1e5 rows (as much again for the far words, below); beyond
     // PBN_D8_SCREEN_MAX_MB (default 512) the step runs unscreened.
     // (Both knobs are read through getenv at every evaluation, like PBN_SUM_WINDOW and PBN_MAGIC_GUARD beside them: two lookups per step, so that a test or a
     // deployment can turn them between two calls of one process.)
@@ -670,7 +678,15 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     size_t mask_b = screen ? (size_t)ceil_div(nqtiles, PBN_QG_PRUNE) * nsplit * ceil_div(tps, 64) * PBN_QG_PRUNE * sizeof(unsigned long long) : 0;
     if (screen && (double)mask_b * (mdbg ? 2.0 : 1.0) > (double)knob_int("PBN_D8_SCREEN_MAX_MB", 512) * 1048576.0) screen = false;
     if (!screen) mask_b = 0;
-    ctx->scratch_part.reserve(part_b + bbox_b + (screen ? scrq_b + mask_b * (mdbg ? 2 : 1) : 0));
+    // The far pass (round 16, kde_far32_d8.inc): far words beside the live words and a second set of partial rows.  Not without per-query bounds
+    // (PBN_D8_SCREEN_ROWTHR=0, no window pass), with PBN_D8_FAR32=0 (read per evaluation), or where the far words would take the masks over
+    // PBN_D8_SCREEN_MAX_MB: the step is then the one without the pass, bit for bit.
+    const bool rowthr = screen && qrow != nullptr && knob_int("PBN_D8_SCREEN_ROWTHR", 1) != 0;
+    const double ftheta = far32_theta(m.N);
+    const bool far = rowthr && m.far_plain != nullptr && knob_int("PBN_D8_FAR32", 1) != 0 && ftheta >= 8.0 && ftheta + 4.0 <= prune_margin(fdt, m.N, sum_only) &&
+                     (double)mask_b * (mdbg ? 3.0 : 2.0) <= (double)knob_int("PBN_D8_SCREEN_MAX_MB", 512) * 1048576.0;
+    const size_t part_rows_b = far ? ((size_t)2 * nsplit * nqtiles * 16 * P * sizeof(double) + 255) / 256 * 256 : part_b;
+    ctx->scratch_part.reserve(part_rows_b + bbox_b + (screen ? scrq_b + mask_b * ((mdbg ? 2 : 1) + (far ? 1 : 0)) : 0));
     SweepArgs sa{};
     sa.Apack = m.Apack; sa.nxpack = m.nxpack; sa.Axpack = m.Axpack;
     sa.Bpack = pa.pack; sa.nypack = pa.npack; sa.Bxpack = pa.xpack; sa.Bxnorm = pa.xnorm;
@@ -688,27 +704,39 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     sa.part = (double*)ctx->scratch_part.p;
     sa.group_masks = gmasks;
     if (bboxes) {
-        double* bb = (double*)((char*)ctx->scratch_part.p + part_b);
+        double* bb = (double*)((char*)ctx->scratch_part.p + part_rows_b);
         launch_batch_boxes(m.tile_box, m.pdims, m.ntiles, tps, (int)nsplit, bb, ctx->stream);
         sa.batch_box = bb; sa.batches_per_split = (int)ceil_div(tps, 64);
     }
     static const bool log_sweeps = PBN_TUNE(SWEEP_LOG, 0) != 0;   // one line per sweep on stderr (tools/c5_sweeps.py)
     if (log_sweeps) std::fprintf(stderr, "pbn-sweep N=%lld n=%lld d=%d cond=%d prune=%d nsub=%lld nsplit=%lld\n", (long long)m.N, (long long)n, m.d, (int)m.cond, (int)prune, (long long)(prune ? m.nsub : 0), (long long)nsplit);
     if (screen) {
-        char* sp = (char*)ctx->scratch_part.p + part_b + bbox_b;
+        char* sp = (char*)ctx->scratch_part.p + part_rows_b + bbox_b;
         sa.scr_train = m.scr; sa.scr_query = sp;
         sa.live_mask = (unsigned long long*)(sp + scrq_b);
         sa.box_mask = mdbg ? (unsigned long long*)(sp + scrq_b + mask_b) : nullptr;
         // every column against its own query's bound (round 14); 0: against its group's, the masks of round 13 bit for bit (read per evaluation)
-        sa.qrow_thr = knob_int("PBN_D8_SCREEN_ROWTHR", 1) != 0 ? qrow : nullptr;
+        sa.qrow_thr = rowthr ? qrow : nullptr;
+        if (far) {
+            sa.far_mask = (unsigned long long*)(sp + scrq_b + mask_b * (mdbg ? 2 : 1));
+            sa.tile_plain = m.far_plain;
+            sa.far_theta = ftheta;
+            sa.far_pack = m.far_pack;
+        }
         KernelTimer kt(ctx, PBN_K_PACK);
         launch_screen_pack(qs.zrow, qs.perm, n, nqtiles, true, sp, ctx->stream);
         launch_screen_d8(sa, (int)nsplit, knob_int("PBN_D8_SCREEN_STREAM", 2), ctx->stream);   // (0: the serial kernel, 1: the ring, else the dense kernel: the same masks; read per evaluation)
     }
-    { KernelTimer kt(ctx, PBN_K_SWEEP); launch_sweep(sa, fdt, m.KS, m.cond, (int)nsplit, ctx->stream); }
+    {
+        KernelTimer kt(ctx, PBN_K_SWEEP);
+        launch_sweep(sa, fdt, m.KS, m.cond, (int)nsplit, ctx->stream);
+        if (sa.far_mask) launch_sweep_far32_d8(sa, (int)nsplit, ctx->stream);
+    }
     if (screen && mdbg) {
         std::lock_guard<std::mutex> lk(g_masks_mu);
         const size_t words = mask_b / sizeof(unsigned long long);
+        g_masks.far.assign(sa.far_mask ? words : 0, 0ull);
+        if (sa.far_mask) HIP_CHECK(hipMemcpyAsync(g_masks.far.data(), sa.far_mask, mask_b, hipMemcpyDeviceToHost, ctx->stream));
         g_masks.box.resize(words); g_masks.live.resize(words); g_masks.qthr.resize((size_t)nqtiles); g_masks.zq.resize((size_t)n * 8); g_masks.zt.resize((size_t)m.N * 8);
         HIP_CHECK(hipMemcpyAsync(g_masks.zt.data(), m.zsorted, (size_t)m.N * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         std::vector<int32_t> perm((size_t)n);
@@ -747,7 +775,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     const int64_t nblocks = ceil_div(n, 256);
     ctx->scratch_misc.reserve((size_t)nblocks * 2 * sizeof(double));
     FinishArgs fa{};
-    fa.part = sa.part; fa.nsplit = (int)nsplit; fa.nqtiles = nqtiles; fa.nq = n;
+    fa.part = sa.part; fa.nsplit = (int)(sa.far_mask ? 2 * nsplit : nsplit); fa.nqtiles = nqtiles; fa.nq = n;   // (the far pass's partial rows behind the sweep's)
     fa.lognorm = m.lognorm; fa.lognorm_marg = m.lognorm_marg;
     fa.logl = dev_logl; fa.scatter = qperm; fa.block_sums = dev_sum ? (double*)ctx->scratch_misc.p : nullptr;
     fa.block_sums_marg = (m.cond && dev_sum && dev_sum_marg) ? (double*)ctx->scratch_misc.p + nblocks : nullptr;
@@ -758,7 +786,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
 
 // capture != 0 arms the aid; what = 0 the shape (six values into dims), 1 / 2 the box / live masks, 3 per query tile the largest threshold of its
 // columns (the group's where the launch screened against that: MaskDump), 4 / 5 the sorted queries' / training rows' whitened rows, 6 the
-// columns' thresholds [query tiles * 16]: copies up to cap items into out and returns how many the last screened sweep left
+// columns' thresholds [query tiles * 16], 7 the far words: copies up to cap items into out and returns how many the last screened sweep left
 extern "C" int64_t pbn_debug_d8_masks(int what, void* out, int64_t cap, int capture) {
     pbn::g_masks_capture.store(capture != 0);
     std::lock_guard<std::mutex> lk(pbn::g_masks_mu);
@@ -775,6 +803,7 @@ extern "C" int64_t pbn_debug_d8_masks(int what, void* out, int64_t cap, int capt
         case 4: return copy(d.zq.data(), d.zq.size(), 8);
         case 5: return copy(d.zt.data(), d.zt.size(), 8);
         case 6: return copy(d.qrow.data(), d.qrow.size(), 8);
+        case 7: return copy(d.far.data(), d.far.size(), 8);   // the far words (round 16); none where the launch wrote none
         default: return -1;
     }
 }

@@ -55,6 +55,9 @@ struct KdeModel {
     // fitted d = 8 handles whose sum-only sweeps are pruned on rotated boxes: the sorted rows once more as the f16 operands of the screen
     // (kde_screen_d8.inc; written by kde_prune_persist into the handle's store, 32 B per padded row); null = those sweeps run unscreened
     const void* scr = nullptr;
+    // ... and beside them one bit per training tile for the far pass (SweepArgs::tile_plain; kde_far32_d8.inc); null = no far pass
+    const unsigned long long* far_plain = nullptr;
+    const void* far_pack = nullptr;   // SweepArgs::far_pack
 };
 
 // Bytes needed for the three training-side fragment arrays.

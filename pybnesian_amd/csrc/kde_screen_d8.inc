@@ -42,6 +42,30 @@ typedef float f16acc __attribute__((ext_vector_type(16)));
 
 // measurement aid, not part of the C ABI header: (tile, group) blocks the screen kept / blocks it tested (= the blocks that pass the box test)
 __device__ unsigned long long g_screen_kept = 0, g_screen_tested = 0;
+// ... and the kept blocks it handed to the far pass (round 16)
+__device__ unsigned long long g_screen_far = 0;
+
+// The far rule (round 16), one helper for the three kernels below: they must write the same far words.  A live block of a plain tile
+// (SweepArgs::tile_plain) is FAR when every one of its 256 values s~ + E - each at or above the pair's true exponent - lies below its own
+// column's thr_far = qrow_thr[q] - far_theta, rounded down to fp32 as the live rule's threshold is: every pair of the block is then proven
+// far_theta bits below its own query's sum bound, which is what kde_far32_d8.inc's error bound needs.  A column whose query the fp32 pass does
+// not take - 1/2|z_q|^2 above PBN_FAR32_NCAP or NaN, a bound that is NaN or beyond 4 PBN_FAR32_NCAP in magnitude (the pass's offset) - carries
+// thr_far = -inf: nothing compares below it, and no block with that column is far.
+__device__ __forceinline__ float screen_far_thr(const SweepArgs& a, int64_t q) {
+    const double lb = ((const PBN_GLOBAL double*)a.qrow_thr)[q], nq = -((const PBN_GLOBAL double*)a.nypack)[q];
+    if (!(nq <= PBN_FAR32_NCAP && __builtin_fabs(lb) <= 4.0 * PBN_FAR32_NCAP)) return -INFINITY;   // (a NaN on either side)
+    const double thrd = lb - a.far_theta;
+    float tf = (float)thrd;
+    if ((double)tf > thrd) tf = __builtin_fmaf(-__builtin_fabsf(tf), 0x1p-23f, tf) - 0x1p-126f;   // at least one ulp down
+    return tf;
+}
+__device__ __forceinline__ bool screen_not_far(float colmax, float thr_far) { return !(colmax < thr_far); }
+// the plain bits of the 64 tiles from tile t on (a batch of a split starts at any tile: two words of the table-wide bitmap)
+__device__ __forceinline__ unsigned long long screen_plain_word(const SweepArgs& a, int64_t t) {
+    const PBN_GLOBAL unsigned long long* P = (const PBN_GLOBAL unsigned long long*)a.tile_plain + (t >> 6);
+    const unsigned s = (unsigned)(t & 63);
+    return s ? (P[0] >> s) | (P[1] << (64u - s)) : P[0];
+}
 
 __device__ __forceinline__ _Float16 f16_up(double x) {   // the smallest f16 >= x, x >= 0 and far below the format's top
     _Float16 hv = (_Float16)x;
@@ -100,7 +124,8 @@ __global__ __launch_bounds__(256) void kde_screen_pack_kernel(const double* __re
 #endif
 // Round 11's kernel, kept for one release as the A/B leg and the yardstick of mask equality (PBN_D8_SCREEN_STREAM=0): box tests and MFMAs
 // interleaved batch by batch, one fragment load in flight per wave.  kde_screen_d8_kernel, below, writes the same words.
-__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_kernel(SweepArgs a) {
+template <bool FAR>
+__device__ __forceinline__ void screen_d8_serial_body(const SweepArgs& a) {
     constexpr int QG = PBN_QG_PRUNE, PD = PBN_PRUNE_PD;
     static_assert(QG == 2, "two groups = the 32 columns of the MFMA");
     const int lane = threadIdx.x & 63;
@@ -136,11 +161,14 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_ker
     const double thrd = QRp ? QRp[qtl * 16 + (r & 15)] - a.prune_margin : qbs[QG * 2 * PD + gl];
     float thrf = (float)thrd;
     if ((double)thrf > thrd) thrf = __builtin_fmaf(-__builtin_fabsf(thrf), 0x1p-23f, thrf) - 0x1p-126f;   // at least one ulp down
+    float thrfar = -INFINITY;
+    if constexpr (FAR) thrfar = screen_far_thr(a, qtl * 16 + (r & 15));
     const unsigned long long G0 = 0x0000ffff0000ffffull;   // the lanes that hold group 0's columns
     const bool count = a.count_redo != 0;
     if (count && lane == 0) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
     PBN_GLOBAL unsigned long long* LM = (PBN_GLOBAL unsigned long long*)a.live_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG;
     PBN_GLOBAL unsigned long long* BM = a.box_mask ? (PBN_GLOBAL unsigned long long*)a.box_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG : nullptr;
+    PBN_GLOBAL unsigned long long* FM = FAR ? (PBN_GLOBAL unsigned long long*)a.far_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG : nullptr;
     auto frag = [&](int64_t tb, int bA, int bB) -> hf8 {
         const int64_t t = tb + (r < 16 ? bA : bB);
         return SA[(t * 16 + (r & 15)) * 2 + h];
@@ -155,6 +183,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_ker
             bm |= bmg[g];
         }
         unsigned long long my_live[QG] = {0, 0}, my_box[QG] = {0, 0};   // of MY batch (lane = batch)
+        unsigned long long my_far[QG] = {0, 0};
         while (bm) {
             const int j = __builtin_ctzll(bm);
             bm &= bm - 1;
@@ -172,7 +201,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_ker
             }
             unsigned long long mask = gm[0] | gm[1];
             if (!mask) continue;
-            unsigned long long lm0 = 0, lm1 = 0;
+            unsigned long long lm0 = 0, lm1 = 0, nf0 = 0, nf1 = 0;   // live; FAR: not far
             int bA = __builtin_ctzll(mask);
             mask &= mask - 1;
             int bB = mask ? __builtin_ctzll(mask) : bA;   // an odd number of tiles: the last MFMA takes its tile twice
@@ -198,6 +227,11 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_ker
                 const unsigned long long kA = __ballot(!(mA < thrf)), kB = __ballot(!(mB < thrf));
                 lm0 |= ((kA & G0) ? 1ull << bA : 0ull) | ((kB & G0) ? 1ull << bB : 0ull);
                 lm1 |= ((kA & ~G0) ? 1ull << bA : 0ull) | ((kB & ~G0) ? 1ull << bB : 0ull);
+                if constexpr (FAR) {
+                    const unsigned long long fA = __ballot(screen_not_far(mA, thrfar)), fB = __ballot(screen_not_far(mB, thrfar));
+                    nf0 |= ((fA & G0) ? 1ull << bA : 0ull) | ((fB & G0) ? 1ull << bB : 0ull);
+                    nf1 |= ((fA & ~G0) ? 1ull << bA : 0ull) | ((fB & ~G0) ? 1ull << bB : 0ull);
+                }
                 if (!more) break;
                 af = an; bA = nA; bB = nB;
             }
@@ -209,12 +243,20 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_ker
                 atomicAdd(&g_screen_kept, (unsigned long long)(__builtin_popcountll(lm0) + __builtin_popcountll(lm1)));
             }
             if (lane == j) { my_live[0] = lm0; my_live[1] = lm1; my_box[0] = gm[0]; my_box[1] = gm[1]; }
+            if constexpr (FAR) { if (lane == j) { my_far[0] = lm0 & ~nf0; my_far[1] = lm1 & ~nf1; } }
         }
         if (bt < t1) {
             const int64_t jb = (bt - t0) >> 6;
             LM[jb * QG] = my_live[0];
             LM[jb * QG + 1] = my_live[1];
             if (BM) { BM[jb * QG] = my_box[0]; BM[jb * QG + 1] = my_box[1]; }
+            if constexpr (FAR) {
+                const unsigned long long pw = screen_plain_word(a, bt);
+                const unsigned long long f0 = my_far[0] & pw, f1 = my_far[1] & pw;
+                FM[jb * QG] = f0;
+                FM[jb * QG + 1] = f1;
+                if (count && (f0 | f1)) atomicAdd(&g_screen_far, (unsigned long long)(__builtin_popcountll(f0) + __builtin_popcountll(f1)));
+            }
         }
     }
     // the batch slots past the table's end in a short last split hold nothing: written too, so that no word of a launch's masks is left as
@@ -223,6 +265,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_ker
         LM[jb * QG] = 0;
         LM[jb * QG + 1] = 0;
         if (BM) { BM[jb * QG] = 0; BM[jb * QG + 1] = 0; }
+        if constexpr (FAR) { FM[jb * QG] = 0; FM[jb * QG + 1] = 0; }
     }
 }
 
@@ -242,8 +285,13 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_ker
 #ifndef PBN_SCREEN_RING
 #define PBN_SCREEN_RING 4   // fragments in flight per wave (4 VGPRs each)
 #endif
-__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(SweepArgs a) {
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_kernel(SweepArgs a) { screen_d8_serial_body<false>(a); }
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_serial_far_kernel(SweepArgs a) { screen_d8_serial_body<true>(a); }
+
+template <bool FAR>
+__device__ __forceinline__ void screen_d8_ring_body(const SweepArgs& a) {
     constexpr int QG = PBN_QG_PRUNE, PD = PBN_PRUNE_PD, R = PBN_SCREEN_RING;
+    constexpr int MW = FAR ? 6 : 4;   // words per batch in msk: box, live; FAR: not far
     static_assert(QG == 2, "two groups = the 32 columns of the MFMA");
     static_assert(R >= 1 && R <= 16, "ring depth");
     const int lane = threadIdx.x & 63;
@@ -259,7 +307,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
     const PBN_GLOBAL char* __restrict__ SAc = (const PBN_GLOBAL char*)a.scr_train;
     const PBN_GLOBAL hf8* __restrict__ SQ = (const PBN_GLOBAL hf8*)a.scr_query;
     __shared__ double qbs[QG * (2 * PD + 1)];            // the groups' boxes and thresholds, as in the serial kernel
-    __shared__ unsigned long long msk[64 * 2 * QG];      // per batch of the super-batch: the box words of its groups, then the live words
+    __shared__ unsigned long long msk[64 * MW];          // per batch of the super-batch: the box words of its groups, then the live words
     if (lane < QG * 2 * PD) {
         const int g = lane / (2 * PD);
         const int64_t qt = qt0 + g < a.nqtiles ? qt0 + g : a.nqtiles - 1;
@@ -274,6 +322,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
     if (count && lane == 0) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
     PBN_GLOBAL unsigned long long* LM = (PBN_GLOBAL unsigned long long*)a.live_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG;
     PBN_GLOBAL unsigned long long* BM = a.box_mask ? (PBN_GLOBAL unsigned long long*)a.box_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG : nullptr;
+    PBN_GLOBAL unsigned long long* FM = FAR ? (PBN_GLOBAL unsigned long long*)a.far_mask + ((int64_t)qx * a.nsplit_grid + split) * a.batches_per_split * QG : nullptr;
     for (int64_t sb = t0; sb < t1; sb += 4096) {
         // ---- phase 1: the box words of the super-batch's batches (lane = batch)
         const int64_t bt = sb + 64 * lane;   // my batch's first tile
@@ -306,10 +355,10 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
             }
             if (lane == j) { my_box[0] = gm[0]; my_box[1] = gm[1]; }
         }
-        msk[lane * 4] = my_box[0];
-        msk[lane * 4 + 1] = my_box[1];
-        msk[lane * 4 + 2] = 0;
-        msk[lane * 4 + 3] = 0;
+        msk[lane * MW] = my_box[0];
+        msk[lane * MW + 1] = my_box[1];
+#pragma unroll
+        for (int k = 2; k < MW; ++k) msk[lane * MW + k] = 0;
         asm volatile("" ::: "memory");
         // ---- phase 2: the pairs of the parked words through the ring.  Everything that names a pair is scalar.
         const unsigned long long tiles = my_box[0] | my_box[1];
@@ -328,6 +377,8 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
             const double thrd = QRp ? QRp[qtl * 16 + (r & 15)] - a.prune_margin : qbs[QG * 2 * PD + gl];
             float thrf = (float)thrd;
             if ((double)thrf > thrd) thrf = __builtin_fmaf(-__builtin_fabsf(thrf), 0x1p-23f, thrf) - 0x1p-126f;   // at least one ulp down
+            float thrfar = -INFINITY;
+            if constexpr (FAR) thrfar = screen_far_thr(a, qtl * 16 + (r & 15));
             // my 16 bytes of a training row's operands: rows 0..15 of the product come from the pair's first tile, 16..31 from its second
             const unsigned loff = (unsigned)((r & 15) * 32 + h * 16), second = r < 16 ? 0u : 1u;
             const int tiles_lo = (int)(unsigned)tiles, tiles_hi = (int)(unsigned)(tiles >> 32);
@@ -370,7 +421,16 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
                 const unsigned fA = (unsigned)kA | (unsigned)(kA >> 32), fB = (unsigned)kB | (unsigned)(kB >> 32);
                 const unsigned long long l0 = ((fA & 0xffffu) ? 1ull << d.a : 0ull) | ((fB & 0xffffu) ? 1ull << d.b : 0ull);
                 const unsigned long long l1 = ((fA >> 16) ? 1ull << d.a : 0ull) | ((fB >> 16) ? 1ull << d.b : 0ull);
-                if (lane < QG) __hip_atomic_fetch_or(&msk[d.j * 4u + 2u + (unsigned)lane], lane ? l1 : l0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if constexpr (FAR) {
+                    const unsigned long long gA = __ballot(screen_not_far(mA, thrfar)), gB = __ballot(screen_not_far(mB, thrfar));
+                    const unsigned hA = (unsigned)gA | (unsigned)(gA >> 32), hB = (unsigned)gB | (unsigned)(gB >> 32);
+                    const unsigned long long n0 = ((hA & 0xffffu) ? 1ull << d.a : 0ull) | ((hB & 0xffffu) ? 1ull << d.b : 0ull);
+                    const unsigned long long n1 = ((hA >> 16) ? 1ull << d.a : 0ull) | ((hB >> 16) ? 1ull << d.b : 0ull);
+                    if (lane < 2 * QG) __hip_atomic_fetch_or(&msk[d.j * (unsigned)MW + 2u + (unsigned)lane], lane == 0 ? l0 : lane == 1 ? l1 : lane == 2 ? n0 : n1,
+                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                } else {
+                    if (lane < QG) __hip_atomic_fetch_or(&msk[d.j * 4u + 2u + (unsigned)lane], lane ? l1 : l0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
             };
             Pair dq[R];
             hf8 fq[R];
@@ -395,11 +455,18 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
         asm volatile("" ::: "memory");
         if (bt < t1) {
             const int64_t jb = (bt - t0) >> 6;
-            const unsigned long long lv0 = msk[lane * 4 + 2] & my_box[0], lv1 = msk[lane * 4 + 3] & my_box[1];
+            const unsigned long long lv0 = msk[lane * MW + 2] & my_box[0], lv1 = msk[lane * MW + 3] & my_box[1];
             LM[jb * QG] = lv0;
             LM[jb * QG + 1] = lv1;
-            if (BM) { BM[jb * QG] = msk[lane * 4]; BM[jb * QG + 1] = msk[lane * 4 + 1]; }
+            if (BM) { BM[jb * QG] = msk[lane * MW]; BM[jb * QG + 1] = msk[lane * MW + 1]; }
             if (count && (lv0 | lv1)) atomicAdd(&g_screen_kept, (unsigned long long)(__builtin_popcountll(lv0) + __builtin_popcountll(lv1)));
+            if constexpr (FAR) {
+                const unsigned long long pw = screen_plain_word(a, bt);
+                const unsigned long long f0 = lv0 & ~msk[lane * MW + 4] & pw, f1 = lv1 & ~msk[lane * MW + 5] & pw;
+                FM[jb * QG] = f0;
+                FM[jb * QG + 1] = f1;
+                if (count && (f0 | f1)) atomicAdd(&g_screen_far, (unsigned long long)(__builtin_popcountll(f0) + __builtin_popcountll(f1)));
+            }
         }
         asm volatile("" ::: "memory");   // (the next super-batch parks its words where these were read)
     }
@@ -408,6 +475,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
         LM[jb * QG] = 0;
         LM[jb * QG + 1] = 0;
         if (BM) { BM[jb * QG] = 0; BM[jb * QG + 1] = 0; }
+        if constexpr (FAR) { FM[jb * QG] = 0; FM[jb * QG + 1] = 0; }
     }
 }
 
@@ -427,8 +495,11 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(Swe
 // launch_screen_d8 hands smaller tables to the ring).
 // NW = sweep waves served by one screen wave (NW x 2 query groups against one stream of fragments): phase 1 runs per served wave in turn, a
 // batch's units run the MFMAs of the served waves in reach of it.
-template <int NW>
-__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kernel(SweepArgs a) {
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_kernel(SweepArgs a) { screen_d8_ring_body<false>(a); }
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_far_kernel(SweepArgs a) { screen_d8_ring_body<true>(a); }
+
+template <int NW, bool FAR>
+__device__ __forceinline__ void screen_d8_dense_body(const SweepArgs& a) {
     constexpr int QG = PBN_QG_PRUNE, PD = PBN_PRUNE_PD, QW = QG * (2 * PD + 1);
     static_assert(QG == 2, "two groups = the 32 columns of the MFMA");
     static_assert(NW == 1 || NW == 2, "sweep waves per screen wave");
@@ -463,6 +534,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
     const int64_t word0 = ((int64_t)qxs * NW * a.nsplit_grid + split) * a.batches_per_split * QG;
     PBN_GLOBAL unsigned long long* LM = (PBN_GLOBAL unsigned long long*)a.live_mask + word0;
     PBN_GLOBAL unsigned long long* BM = a.box_mask ? (PBN_GLOBAL unsigned long long*)a.box_mask + word0 : nullptr;
+    PBN_GLOBAL unsigned long long* FM = FAR ? (PBN_GLOBAL unsigned long long*)a.far_mask + word0 : nullptr;
     if (count && lane == 0)   // once per served sweep wave, as the ring and the serial kernel count
         for (int w = 0; w < NW && ((int64_t)qxs * NW + w) * QG < a.nqtiles; ++w) atomicAdd(&g_sweep_tiles, (unsigned long long)(t1 - t0) * QG);
     for (int64_t sb = t0; sb < t1; sb += 4096) {
@@ -514,6 +586,9 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
         unsigned long long my_scr[NW][QG];   // of MY batch (lane = batch): the tiles the screen could not prove dead, per served wave and group
 #pragma unroll
         for (int w = 0; w < NW; ++w) { my_scr[w][0] = 0; my_scr[w][1] = 0; }
+        unsigned long long my_nf[FAR ? NW : 1][QG];    // FAR: ... and the tiles with a column at or above its far threshold
+#pragma unroll
+        for (int w = 0; w < (FAR ? NW : 1); ++w) { my_nf[w][0] = 0; my_nf[w][1] = 0; }
         unsigned long long todo = __ballot(tiles != 0);   // batches whose units are still to be listed
         if (todo) {
             // what only the MFMAs need is set up here, from a lane number the compiler cannot hoist it by (see kde_screen_d8_kernel)
@@ -521,7 +596,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
             asm volatile("" : "+v"(ln));
             const int r = ln & 31, h = ln >> 5, gl = r >> 4;   // my column's group
             hf8 bq[NW];
-            float thrf[NW];
+            float thrf[NW], thrfar[FAR ? NW : 1];
 #pragma unroll
             for (int w = 0; w < NW; ++w) {
                 const int64_t qt0 = ((int64_t)qxs * NW + w) * QG;
@@ -534,6 +609,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
                 float tf = (float)thrd;
                 if ((double)tf > thrd) tf = __builtin_fmaf(-__builtin_fabsf(tf), 0x1p-23f, tf) - 0x1p-126f;   // at least one ulp down
                 thrf[w] = tf;
+                if constexpr (FAR) thrfar[w] = screen_far_thr(a, qtl * 16 + (r & 15));
             }
             // my 16 bytes of a pair's KiB: rows 0..15 of the product come from tile 2p, 16..31 from tile 2p + 1
             const unsigned loff = (unsigned)(r * 32 + h * 16);
@@ -579,6 +655,9 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
             unsigned long long word[NW];   // per lane: the bits of my column's group in the batch being screened
 #pragma unroll
             for (int w = 0; w < NW; ++w) word[w] = 0;
+            unsigned long long wordf[FAR ? NW : 1];   // FAR: the same for "not far"
+#pragma unroll
+            for (int w = 0; w < (FAR ? NW : 1); ++w) wordf[w] = 0;
             auto row_or = [](unsigned x) -> unsigned {   // OR over my row of 16 lanes, in every lane of it
                 x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, true);    // quad_perm [1, 0, 3, 2]
                 x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, true);    // quad_perm [2, 3, 0, 1]
@@ -590,7 +669,7 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
 #pragma unroll
                 for (int w = 0; w < NW; ++w) {
                     if (NW > 1 && !((d.sel >> w) & 1u)) continue;   // (uniform)
-                    unsigned b = 0;
+                    unsigned b = 0, bf = 0;
                     const f16acc zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                     // the next pair's MFMA is issued before this pair's maxima, which then run beside it (two accumulators in turn)
                     f16acc acc[4];
@@ -604,8 +683,10 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
                         const float mA = mx(mx(mx(mx(c[0], c[1]), c[2]), mx(mx(c[3], c[4]), c[5])), mx(c[6], c[7]));
                         const float mB = mx(mx(mx(mx(c[8], c[9]), c[10]), mx(mx(c[11], c[12]), c[13])), mx(c[14], c[15]));
                         b |= (!(mA < thrf[w]) ? 1u << (2 * i) : 0u) | (!(mB < thrf[w]) ? 2u << (2 * i) : 0u);
+                        if constexpr (FAR) bf |= (screen_not_far(mA, thrfar[w]) ? 1u << (2 * i) : 0u) | (screen_not_far(mB, thrfar[w]) ? 2u << (2 * i) : 0u);
                     }
                     word[w] |= (unsigned long long)(b >> d.sh) << (8u * d.u);
+                    if constexpr (FAR) wordf[w] |= (unsigned long long)(bf >> d.sh) << (8u * d.u);
                 }
                 if (d.last) {   // (uniform) the batch is through: its words over each group's lanes, kept by lane = batch
 #pragma unroll
@@ -618,6 +699,16 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
                                    ((unsigned long long)((unsigned)__builtin_amdgcn_readlane((int)hi, 16 * q) | (unsigned)__builtin_amdgcn_readlane((int)hi, 32 + 16 * q)) << 32);
                         if (lane == (int)d.j) { my_scr[w][0] = g[0]; my_scr[w][1] = g[1]; }
                         word[w] = 0;
+                        if constexpr (FAR) {
+                            const unsigned flo = row_or((unsigned)wordf[w]), fhi = row_or((unsigned)(wordf[w] >> 32));
+                            unsigned long long nf[QG];
+#pragma unroll
+                            for (int q = 0; q < QG; ++q)
+                                nf[q] = (unsigned long long)((unsigned)__builtin_amdgcn_readlane((int)flo, 16 * q) | (unsigned)__builtin_amdgcn_readlane((int)flo, 32 + 16 * q)) |
+                                        ((unsigned long long)((unsigned)__builtin_amdgcn_readlane((int)fhi, 16 * q) | (unsigned)__builtin_amdgcn_readlane((int)fhi, 32 + 16 * q)) << 32);
+                            if (lane == (int)d.j) { my_nf[w][0] = nf[0]; my_nf[w][1] = nf[1]; }
+                            wordf[w] = 0;
+                        }
                     }
                 }
             };
@@ -648,6 +739,13 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
                 LM[w * wave_words + jb * QG + 1] = lv1;
                 if (BM) { BM[w * wave_words + jb * QG] = bx0; BM[w * wave_words + jb * QG + 1] = bx1; }
                 if (count && (lv0 | lv1)) atomicAdd(&g_screen_kept, (unsigned long long)(__builtin_popcountll(lv0) + __builtin_popcountll(lv1)));
+                if constexpr (FAR) {
+                    const unsigned long long pw = screen_plain_word(a, bt);
+                    const unsigned long long f0 = lv0 & ~my_nf[w][0] & pw, f1 = lv1 & ~my_nf[w][1] & pw;
+                    FM[w * wave_words + jb * QG] = f0;
+                    FM[w * wave_words + jb * QG + 1] = f1;
+                    if (count && (f0 | f1)) atomicAdd(&g_screen_far, (unsigned long long)(__builtin_popcountll(f0) + __builtin_popcountll(f1)));
+                }
             }
         }
         asm volatile("" ::: "memory");   // (the next super-batch parks its words where these were read)
@@ -659,9 +757,14 @@ __global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kern
             LM[w * wave_words + jb * QG] = 0;
             LM[w * wave_words + jb * QG + 1] = 0;
             if (BM) { BM[w * wave_words + jb * QG] = 0; BM[w * wave_words + jb * QG + 1] = 0; }
+            if constexpr (FAR) { FM[w * wave_words + jb * QG] = 0; FM[w * wave_words + jb * QG + 1] = 0; }
         }
     }
 }
+template <int NW>
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_kernel(SweepArgs a) { screen_d8_dense_body<NW, false>(a); }
+template <int NW>
+__global__ __launch_bounds__(64, PBN_SCREEN_WAVES) void kde_screen_d8_dense_far_kernel(SweepArgs a) { screen_d8_dense_body<NW, true>(a); }
 
 void launch_screen_pack(const double* z, const int32_t* perm, int64_t n, int64_t ntiles, bool is_query, void* out, hipStream_t st) {
     const int64_t npad = ntiles * 16;
@@ -680,17 +783,26 @@ void launch_screen_d8(const SweepArgs& a_in, int nsplit, int which, hipStream_t 
     if (!a.scr_train || !a.scr_query || !a.live_mask || !a.batch_box || a.pdims != PBN_PRUNE_PD) throw invalid_error("KDE: the d = 8 screen needs its operands, masks and batch boxes");
     const int64_t nwaves = ceil_div(a.nqtiles, PBN_QG_PRUNE);
     const dim3 grid((unsigned)(nwaves * nsplit)), block(64);
-    if (which == 0) hipLaunchKernelGGL(kde_screen_d8_serial_kernel, grid, block, 0, st, a);
-    else if (which == 1 || a.ntiles < 8) hipLaunchKernelGGL(kde_screen_d8_kernel, grid, block, 0, st, a);   // (a unit of the dense kernel is 8 tiles of operands)
-    else {
+    const bool far = a.far_mask != nullptr;   // (the far forms are kernels of their own: without far words the launch is the one it was)
+    if (far && (!a.qrow_thr || !a.tile_plain || !a.nypack)) throw invalid_error("KDE: the d = 8 screen's far words need per-query bounds and the plain bits");
+    if (which == 0) {
+        if (far) hipLaunchKernelGGL(kde_screen_d8_serial_far_kernel, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(kde_screen_d8_serial_kernel, grid, block, 0, st, a);
+    } else if (which == 1 || a.ntiles < 8) {   // (a unit of the dense kernel is 8 tiles of operands)
+        if (far) hipLaunchKernelGGL(kde_screen_d8_far_kernel, grid, block, 0, st, a);
+        else hipLaunchKernelGGL(kde_screen_d8_kernel, grid, block, 0, st, a);
+    } else {
         // the shipped NW alone is instantiated; an EXPERIMENTS build has both and PBN_SCREEN_NW (the environment) picks
         const int nw = PBN_TUNE(SCREEN_NW, PBN_SCREEN_NW) == 2 ? 2 : 1;
         const dim3 dgrid((unsigned)(ceil_div(nwaves, (int64_t)nw) * nsplit));
 #ifdef PBN_EXPERIMENTS
-        if (nw == 2) hipLaunchKernelGGL(kde_screen_d8_dense_kernel<2>, dgrid, block, 0, st, a);
+        if (far && nw == 2) hipLaunchKernelGGL(kde_screen_d8_dense_far_kernel<2>, dgrid, block, 0, st, a);
+        else if (far) hipLaunchKernelGGL(kde_screen_d8_dense_far_kernel<1>, dgrid, block, 0, st, a);
+        else if (nw == 2) hipLaunchKernelGGL(kde_screen_d8_dense_kernel<2>, dgrid, block, 0, st, a);
         else hipLaunchKernelGGL(kde_screen_d8_dense_kernel<1>, dgrid, block, 0, st, a);
 #else
-        hipLaunchKernelGGL(kde_screen_d8_dense_kernel<PBN_SCREEN_NW>, dgrid, block, 0, st, a);
+        if (far) hipLaunchKernelGGL(kde_screen_d8_dense_far_kernel<PBN_SCREEN_NW>, dgrid, block, 0, st, a);
+        else hipLaunchKernelGGL(kde_screen_d8_dense_kernel<PBN_SCREEN_NW>, dgrid, block, 0, st, a);
 #endif
     }
     HIP_CHECK(hipGetLastError());

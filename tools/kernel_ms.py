@@ -5,8 +5,9 @@ tools/profile_bench.sh): the d = 8 screen, the pruned d = 8 sweep, the window pa
 import csv
 import sys
 
-ROWS = (("screen", "kde_screen_d8_kernel"), ("screen (serial)", "kde_screen_d8_serial_kernel"), ("screen (dense)", "kde_screen_d8_dense_kernel"), ("sweep", "kde_sweep_pruned_d8_kernel"),
-        ("window", "query_window_kernel"))
+ROWS = (("screen", "kde_screen_d8_kernel"), ("screen (serial)", "kde_screen_d8_serial_kernel"), ("screen (dense)", "kde_screen_d8_dense_kernel"),
+        ("screen far", "kde_screen_d8_far_kernel"), ("screen far (ser)", "kde_screen_d8_serial_far_kernel"), ("screen far (dns)", "kde_screen_d8_dense_far_kernel"),
+        ("sweep", "kde_sweep_pruned_d8_kernel"), ("far pass", "kde_sweep_far32_d8_kernel"), ("window", "query_window_kernel"))
 tot = {k: [0.0, 0] for k, _ in ROWS}
 rest, names = 0.0, []
 with open(sys.argv[1], newline="") as f:

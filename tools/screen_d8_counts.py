@@ -72,6 +72,19 @@ def counted():
 s, kept, tested, v, t = counted()
 print(f"{which}: slogl {s!r}; box-visited {v} of {t} offered ({v / max(t, 1):.4f}); "
       f"screen kept {kept} of {tested} tested ({kept / max(tested, 1):.4f})")
+# round 16: of the kept blocks, those the screen's far words hand to the fp32 pass (pbn_debug_d8_screen_far; PBN_D8_FAR32=0: none, the fp64 step)
+if hasattr(lib, "pbn_debug_d8_screen_far"):
+    far = C.c_ulonglong(0)
+    os.environ["PBN_SWEEP_COUNT_REDO"] = "1"
+    lib.pbn_debug_d8_screen_far(None, 1)
+    s_far = run()
+    lib.pbn_debug_d8_screen_far(C.byref(far), 1)
+    os.environ["PBN_SWEEP_COUNT_REDO"] = "0"
+    os.environ["PBN_D8_FAR32"] = "0"
+    s_f64 = run()
+    del os.environ["PBN_D8_FAR32"]
+    print(f"  far blocks {far.value} of {kept} kept ({far.value / max(kept, 1):.4f}); slogl with the far pass {s_far!r}, PBN_D8_FAR32=0 {s_f64!r}: "
+          f"relative difference {abs(s_far - s_f64) / abs(s_f64):.3e}")
 # round 14: the same launch with every column against its GROUP's threshold (PBN_D8_SCREEN_ROWTHR=0, read per evaluation)
 before = os.environ.get("PBN_D8_SCREEN_ROWTHR")
 os.environ["PBN_D8_SCREEN_ROWTHR"] = "0"
