@@ -483,12 +483,15 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store) {
 // launch had no per-query bounds: PBN_D8_SCREEN_ROWTHR=0, no window pass).  qthr, one number per query tile, is the LARGEST of the tile's
 // sixteen: a block all of whose columns lie below their own thresholds holds no pair at or above it - the only per-tile number of which
 // that is true - and where the launch compared against the group's bound it is that bound, as before.
+// Partial rows: what kde_finish_kernel is about to merge, copied behind both sweeps - per (row, sorted query) a pair (o, s) that stands for
+// s 2^o; rows 0 .. nsplit - 1 the fp64 sweep's, rows nsplit .. 2 nsplit - 1 the far pass's (absent where the launch ran none).
 static std::atomic<bool> g_masks_capture{false};
 static std::mutex g_masks_mu;
 struct MaskDump {
     std::vector<unsigned long long> box, live, far;   // far: empty where the launch wrote no far words
     std::vector<double> qthr, zq, zt;  // per query tile: see above; the sorted queries' / training rows' whitened rows [n][8]
     std::vector<double> qrow;          // per sorted query, padding columns included [nqtiles * 16]
+    std::vector<double> part;          // the launch's partial rows [rows][nqtiles * 16][2]: the fp64 sweep's nsplit, then the far pass's nsplit where it ran
     long long dims[6] = {0, 0, 0, 0, 0, 0};   // sweep waves, splits, batches per split, tiles per split, training tiles, queries
 };
 static MaskDump g_masks;
@@ -739,6 +742,8 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         if (sa.far_mask) HIP_CHECK(hipMemcpyAsync(g_masks.far.data(), sa.far_mask, mask_b, hipMemcpyDeviceToHost, ctx->stream));
         g_masks.box.resize(words); g_masks.live.resize(words); g_masks.qthr.resize((size_t)nqtiles); g_masks.zq.resize((size_t)n * 8); g_masks.zt.resize((size_t)m.N * 8);
         HIP_CHECK(hipMemcpyAsync(g_masks.zt.data(), m.zsorted, (size_t)m.N * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        g_masks.part.resize((size_t)(sa.far_mask ? 2 * nsplit : nsplit) * (size_t)nqtiles * 16 * P);   // (a screened launch is unconditional: P = 2)
+        HIP_CHECK(hipMemcpyAsync(g_masks.part.data(), sa.part, g_masks.part.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         std::vector<int32_t> perm((size_t)n);
         std::vector<double> zrow((size_t)n * 8);
         HIP_CHECK(hipMemcpyAsync(g_masks.box.data(), sa.box_mask, mask_b, hipMemcpyDeviceToHost, ctx->stream));
@@ -786,7 +791,9 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
 
 // capture != 0 arms the aid; what = 0 the shape (six values into dims), 1 / 2 the box / live masks, 3 per query tile the largest threshold of its
 // columns (the group's where the launch screened against that: MaskDump), 4 / 5 the sorted queries' / training rows' whitened rows, 6 the
-// columns' thresholds [query tiles * 16], 7 the far words: copies up to cap items into out and returns how many the last screened sweep left
+// columns' thresholds [query tiles * 16], 7 the far words, 8 the partial rows as doubles [rows][query tiles * 16][2] in the sorted query order of
+// what = 4 (rows: the splits of the fp64 sweep, then - where the far pass ran - as many of the far pass; a pair (o, s) is s 2^o, as
+// kde_finish_kernel reads it): copies up to cap items into out and returns how many the last screened sweep left
 extern "C" int64_t pbn_debug_d8_masks(int what, void* out, int64_t cap, int capture) {
     pbn::g_masks_capture.store(capture != 0);
     std::lock_guard<std::mutex> lk(pbn::g_masks_mu);
@@ -804,6 +811,7 @@ extern "C" int64_t pbn_debug_d8_masks(int what, void* out, int64_t cap, int capt
         case 5: return copy(d.zt.data(), d.zt.size(), 8);
         case 6: return copy(d.qrow.data(), d.qrow.size(), 8);
         case 7: return copy(d.far.data(), d.far.size(), 8);   // the far words (round 16); none where the launch wrote none
+        case 8: return copy(d.part.data(), d.part.size(), 8);   // the partial rows both sweeps left for kde_finish_kernel
         default: return -1;
     }
 }
