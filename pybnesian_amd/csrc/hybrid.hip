@@ -390,7 +390,7 @@ void launch_seg(const SegArgs& a, int d, hipStream_t st) {
 // Shifted moments of the columns `cols` (nc of them, <= 64) for EVERY cell of the grouping in one segmented, gathered Gram launch: a cell is a
 // segment of the grouped row list cut into pieces of 4 096 rows, the pieces' partials added in order per cell (launch_gram_segments).
 // out[cell]: S[i], G[i + j nc] indexed by position in `cols`.
-static void cells_gram(pbn_scoredata* sd, const HybridGrouping& g, const int* cols, int nc, std::vector<Stats>& out) {
+static int cells_gram(pbn_scoredata* sd, const HybridGrouping& g, const int* cols, int nc, std::vector<Stats>& out) {
     pbn_ctx* ctx = sd->ctx;
     const pbn_table* t = sd->table();
     const size_t cells = (size_t)g.nc * g.nregions;
@@ -407,7 +407,7 @@ static void cells_gram(pbn_scoredata* sd, const HybridGrouping& g, const int* co
     const int nblk = (int)(blk.size() / 4);
     out.assign(cells, Stats());
     for (size_t c = 0; c < cells; ++c) { out[c].zero(nc); out[c].N = g.off[c + 1] - g.off[c]; }
-    if (nblk == 0) return;
+    if (nblk == 0) return 0;
     dev_buf<int32_t> dblk(blk.size() + off.size());
     HIP_CHECK(hipMemcpyAsync(dblk.p, blk.data(), blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_CHECK(hipMemcpyAsync(dblk.p + blk.size(), off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -439,7 +439,13 @@ static void cells_gram(pbn_scoredata* sd, const HybridGrouping& g, const int* co
                 }
             }
     }
+    return nblk;
 }
+
+// what group_moments took, for pbn_debug_hybrid_moments (test aid; the layout is at its definition): non-null only inside that call, on
+// the calling thread.  Costs the product path one pointer test per group_moments call; no kernel and no result depends on it.
+struct MomentsDbg { int path = -1, pieces = 0, width = 0; };
+static thread_local MomentsDbg* g_moments_dbg = nullptr;
 
 static bool ensure_full_moments(pbn_scoredata* sd, const HybridGrouping& g) {
     if (g.full_state != 0) return g.full_state > 0;
@@ -450,7 +456,7 @@ static bool ensure_full_moments(pbn_scoredata* sd, const HybridGrouping& g) {
     if (!on || sd->has_nulls || n > 64 || cells * ((size_t)n * n + n) > ((size_t)1 << 24)) { g.full_state = -1; return false; }
     std::vector<int> all((size_t)n);
     for (int i = 0; i < n; ++i) all[i] = i;
-    cells_gram(sd, g, all.data(), n, g.full);
+    g.full_pieces = cells_gram(sd, g, all.data(), n, g.full);
     g.full_state = 1;
     return true;
 }
@@ -462,6 +468,7 @@ void group_moments(pbn_scoredata* sd, const HybridGrouping& g, const int* cols, 
     for (size_t c = 0; c < cells; ++c) { M[c].zero(d); M[c].N = g.off[c + 1] - g.off[c]; }
     if (ensure_full_moments(sd, g)) {
         const int n = sd->n;
+        if (g_moments_dbg) *g_moments_dbg = MomentsDbg{0, g.full_pieces, (n + 15) / 16};
         for (size_t c = 0; c < cells; ++c) {
             const Stats& f = g.full[c];
             Stats& st = M[c];
@@ -477,6 +484,7 @@ void group_moments(pbn_scoredata* sd, const HybridGrouping& g, const int* cols, 
     static const bool batched = PBN_TUNE(HYBRID_SEGMENTED, 1) != 0;
     if (d <= 8 && batched && g.npieces > 0) {
         const int S = d + d * (d + 1) / 2;
+        if (g_moments_dbg) *g_moments_dbg = MomentsDbg{1, g.npieces, d};
         ctx->scratch_red.reserve((size_t)(g.npieces + cells) * S);
         SegArgs a{};
         a.base = t->data; a.ld = t->ld;
@@ -507,9 +515,11 @@ void group_moments(pbn_scoredata* sd, const HybridGrouping& g, const int* cols, 
     // launch for all cells (round 3 took one Gram launch + one wait per cell here)
     static const bool cellwise = PBN_TUNE(HYBRID_CELLWISE_GRAM, 0) != 0;
     if (!cellwise && d <= 64) {
-        cells_gram(sd, g, cols, d, M);
+        const int pieces = cells_gram(sd, g, cols, d, M);
+        if (g_moments_dbg) *g_moments_dbg = MomentsDbg{2, pieces, (d + 15) / 16};
         return;
     }
+    if (g_moments_dbg) *g_moments_dbg = MomentsDbg{3, 0, (d + 15) / 16};
     for (size_t c = 0; c < cells; ++c)
         if (M[c].N > 0) gram_raw(t, cols, d, 0, M[c].N, g.rows.p + g.off[c], sd->shift_dev.p, M[c].S.data(), M[c].G.data());
 }
@@ -1095,3 +1105,60 @@ double score_hybrid(pbn_scoredata* sd, int kind, int var, int node_type, const i
 
 }  // namespace score
 }  // namespace pbn
+
+using namespace pbn;
+using namespace pbn::score;
+
+// pbn_debug_hybrid_moments (test aid, not part of the C ABI header): the per-cell moments of a hybrid candidate as score_hybrid takes
+// them.  kind: the score kind whose regions cut the rows (regions_of: PBN_SCORE_BIC one region, PBN_SCORE_CVLIK the folds, PBN_SCORE_HOLDOUT
+// train and test).  dpar: n_dpar distinct discrete column ids (n .. n + n_disc - 1), any order - sorted here as the engine sorts them
+// and handed to grouping_for, so the grouping is the handle's own (built or fetched).  cols: d continuous column ids (1 .. 64, any
+// order, taken as given).  group_moments runs exactly as score_hybrid calls it.  out receives up to `cap` doubles, per cell
+// [N, S[d], G[d * d] column-major] with cell = canonical configuration (first sorted parent fastest) * nregions + region.  rec (nullable),
+// 8 int64:
+//   0 path: 0 full (entries of the grouping's Gram over all continuous columns), 1 seg (seg_moments_kernel<T, D>), 2 own (cells_gram over
+//     the candidate's columns), 3 one gram_raw per cell (PBN_HYBRID_CELLWISE_GRAM)
+//   1 nc    2 nregions    3 pieces the path's launch took (full: the launch that filled the grouping's Gram, whenever it ran)
+//   4 NCT (paths 0, 2, 3: 16-column tiles of the launch) or D (path 1)    5 bytes of a table element    6 cells    7 0
+// Returns the doubles all cells hold together (out == NULL or cap too small: nothing beyond cap is written), -1 after an error.
+extern "C" int64_t pbn_debug_hybrid_moments(pbn_scoredata* sd, int kind, int n_dpar, const int* dpar, int d, const int* cols, double* out, int64_t cap,
+                                            int64_t* rec) {
+    int64_t total = 0;
+    const int rc = guarded(mu_of(sd), [&] {
+        if (!sd || n_dpar < 0 || (n_dpar > 0 && !dpar) || !cols) throw invalid_error("pbn_debug_hybrid_moments: bad argument");
+        if (sd->discrete_only) throw invalid_error("pbn_debug_hybrid_moments: discrete-only score data has no continuous columns");
+        if (kind != PBN_SCORE_BIC && kind != PBN_SCORE_CVLIK && kind != PBN_SCORE_HOLDOUT) throw invalid_error("pbn_debug_hybrid_moments: BIC, CV or hold-out regions");
+        if (kind == PBN_SCORE_CVLIK && sd->k <= 0) throw invalid_error("pbn_debug_hybrid_moments: score data has no CV folds");
+        if (kind == PBN_SCORE_HOLDOUT && sd->n_hold <= 0) throw invalid_error("pbn_debug_hybrid_moments: score data has no hold-out split");
+        if (d < 1 || d > 64) throw invalid_error("pbn_debug_hybrid_moments: between 1 and 64 continuous columns");
+        for (int i = 0; i < d; ++i) {
+            if (cols[i] < 0 || cols[i] >= sd->n) throw invalid_error("pbn_debug_hybrid_moments: not a continuous column");
+            // (score_hybrid sends these candidates through the masked pass, not through group_moments)
+            if (sd->has_nulls && !sd->valid[cols[i]].empty()) throw invalid_error("pbn_debug_hybrid_moments: a column of the candidate has a validity mask");
+        }
+        std::vector<int> dsorted(dpar, dpar + n_dpar);
+        std::sort(dsorted.begin(), dsorted.end());
+        for (int i = 0; i < n_dpar; ++i)
+            if (dsorted[i] < sd->n || dsorted[i] >= sd->n + sd->n_disc || (i > 0 && dsorted[i] == dsorted[i - 1]))
+                throw invalid_error("pbn_debug_hybrid_moments: distinct discrete columns");
+        HIP_CHECK(hipSetDevice(sd->ctx->device));
+        const std::vector<Region> regions = regions_of(sd, kind);
+        const std::shared_ptr<const HybridGrouping> g = grouping_for(sd, kind, dsorted, regions);
+        std::vector<Stats> M;
+        MomentsDbg dbg;
+        g_moments_dbg = &dbg;
+        try { group_moments(sd, *g, cols, d, M); } catch (...) { g_moments_dbg = nullptr; throw; }
+        g_moments_dbg = nullptr;
+        auto put = [&](double v) { if (out && total < cap) out[total] = v; ++total; };
+        for (const Stats& st : M) {
+            put((double)st.N);
+            for (int i = 0; i < d; ++i) put(st.S[i]);
+            for (size_t e = 0; e < (size_t)d * d; ++e) put(st.G[e]);
+        }
+        if (rec) {
+            rec[0] = dbg.path; rec[1] = g->nc; rec[2] = g->nregions; rec[3] = dbg.pieces; rec[4] = dbg.width;
+            rec[5] = sd->table()->dtype == PBN_F64 ? 8 : 4; rec[6] = (int64_t)M.size(); rec[7] = 0;
+        }
+    });
+    return rc == PBN_OK ? total : -1;
+}

@@ -775,6 +775,36 @@ int pbn_lg_cdf(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t
     return lg_eval(t, cols, d, row0, n, beta, variance, out, nullptr, 1);
 }
 
+// ---- test aids (not part of the C ABI header) -----------------------------------------------------------------------
+// pbn_debug_scoredata_shifts: the handle's pilot shifts, one double per continuous column.
+int pbn_debug_scoredata_shifts(const pbn_scoredata* sd, double* out) {
+    return guarded(mu_of(sd), [&] {
+        if (!sd || !out) throw invalid_error("pbn_debug_scoredata_shifts: null argument");
+        std::copy(sd->shift.begin(), sd->shift.end(), out);
+    });
+}
+
+// pbn_debug_gram_rows: gram_raw through a device row list, as the candidates of a table with nulls reach it (valid_row_moments above,
+// score_hybrid's filtered lists).  rows: n_rows >= 1 table row ids on the host (any order, repeats allowed), shift: one double per TABLE
+// column, on the host; both are uploaded here.  cols: d table columns (1 .. 64).  S: d sums, G: d * d products, column-major, of the
+// shifted columns over the list - raw, as gram_raw returns them.
+int pbn_debug_gram_rows(const pbn_table* t, int d, const int* cols, const int32_t* rows, int64_t n_rows, const double* shift, double* S, double* G) {
+    return guarded(mu_of(t), [&] {
+        if (!t || !cols || !rows || !shift || !S || !G) throw invalid_error("pbn_debug_gram_rows: null argument");
+        if (d < 1 || d > 64) throw invalid_error("pbn_debug_gram_rows: between 1 and 64 columns");
+        check_cols(t, cols, d, "pbn_debug_gram_rows");
+        if (n_rows < 1 || n_rows > 0x7fffffffll) throw invalid_error("pbn_debug_gram_rows: a row list of 1 .. 2^31 - 1 entries");
+        for (int64_t r = 0; r < n_rows; ++r)
+            if (rows[r] < 0 || rows[r] >= t->n_rows) throw invalid_error("pbn_debug_gram_rows: row list entry out of range");
+        HIP_CHECK(hipSetDevice(t->ctx->device));
+        dev_buf<int32_t> drows((size_t)n_rows + 16);   // (the lists of the engine carry the same slack)
+        dev_buf<double> dshift((size_t)t->n_cols);
+        HIP_CHECK(hipMemcpy(drows.p, rows, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(dshift.p, shift, (size_t)t->n_cols * sizeof(double), hipMemcpyHostToDevice));
+        gram_raw(t, cols, d, 0, n_rows, drows.p, dshift.p, S, G);   // synchronises
+    });
+}
+
 }  // extern "C"
 
 // ---- the batch engine: score_batch_body checks the call and sends every candidate to one of score_hybrid_candidate (a discrete column

@@ -57,6 +57,7 @@ struct HybridGrouping {
     // candidate over this grouping then takes its columns' entries on the host instead of a launch and a synchronisation of its own
     mutable std::vector<pbn::score::Stats> full;
     mutable int full_state = 0;        // 0 not tried, 1 ready, -1 not applicable (more than 64 continuous columns / too many cells)
+    mutable int full_pieces = 0;       // pieces that launch took (read by the test aid pbn_debug_hybrid_moments only)
 };
 
 struct pbn_scoredata : pbn::score::FamilyScratch {

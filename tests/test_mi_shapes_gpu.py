@@ -17,9 +17,10 @@ Rounding leg.  Real-valued tables (offsets up to +-30), same configurations: |go
 sum |x_i|), the bound of any summation order of n_g rounded products or FMAs, with want from np.longdouble products and sums of the
 rounded x - shift (reported shifts).  No measured constant.
 
-What is reached is asserted at the end (test_every_launch_form_was_seen).  NOT reached: the column-gather form gram_gring_kernel<T, NCT,
-false>, which a product build launches only when the row-major mirror cannot be allocated or exceeds its 16 GiB budget; it stays covered
-only by tools/fuzz_mi_gram.py under an EXPERIMENTS=1 build.
+What is reached is asserted at the end (test_every_launch_form_was_seen).  NOT reached from here: the column-gather form
+gram_gring_kernel<T, NCT, false>, which MutualInformation launches only when the row-major mirror cannot be allocated or exceeds its
+16 GiB budget.  It is the production form of every hybrid local score (csrc/hybrid.hip cells_gram, csrc/scoring.hip gram_raw with a
+row list) and is held there, cell by cell at the same prescribed sizes, by tests/test_hybrid_moments_shapes_gpu.py.
 
 Measured on an MI355X (this file alone, one pytest process): 13 s for the 31 tests, the slowest (test_sorted_kernels, 112 plans) 1.8 s;
 most of it is numpy.  Worst fraction of the rounding bound: 0.479 (float32 table, sorted and legacy kernels, (d1, d2)); float64 0.403
