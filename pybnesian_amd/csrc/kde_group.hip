@@ -11,10 +11,12 @@
 // order instead of the unit's own Morton order - any order gives the same sums up to rounding, the integer offsets of the
 // sweep keep the 2^x error attached to the pair) and the prepass bound (position by counting instead of by key search).
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 
 #include "kde_group.hpp"
 #include "kde_kernels.hpp"
@@ -614,6 +616,24 @@ __global__ __launch_bounds__(256) void group_reduce_kernel(GDev g, double* out) 
 
 size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
+// pbn_debug_group_stages (test aid, not part of the C ABI header; the codes are at its definition below): armed, every chunk is copied to
+// the host behind its reduce - the completed pool and unit tables, the head of the arena (the units' buffers and the element arrays, as
+// the kernels left them), the units' sums, and the pools' table values read straight from the table (not through the gather kernel).
+static std::atomic<bool> g_stage_capture{false};
+static std::mutex g_stage_mu;
+struct StageChunk {
+    std::vector<GPool> pools;
+    std::vector<GUnit> units;
+    std::vector<float> margin;                 // per unit: GSweepUnit::margin
+    std::vector<double> sums;                  // per unit: dev_out[sum_slot]
+    std::vector<std::vector<double>> rows;     // per pool: [n][d] table values in pool-position order
+    std::vector<std::vector<int64_t>> rowid;   // per pool: the table row of every pool position
+    std::vector<char> arena;                   // [0, end of blkcnt)
+    int64_t o_vals = 0, o_reg = 0;
+    long long head[12] = {};
+};
+static std::vector<StageChunk> g_stage;
+
 // Training tiles per split of a unit's sweep.  PBN_GROUP_SPLIT_TILES pins it.  fp32 sweeps: 512 up to 16 384 tiles, 1 024 up to 32 768 tiles and 2 048 above (C5's 720 000-row
 // slices: within noise of 512 in time, `profiles/r4/split_tiles_probe.txt` - but every query keeps a partial per split, 60 % of a candidate's
 // arena at 512, so the coarser split lets an arena-full hold twice the candidates); the fp64 sweeps take 4 096 since round 5: with the two-level
@@ -650,6 +670,7 @@ static int64_t moment_rule_rows(const GUnit& U) {
 void run_chunk(pbn_ctx* ctx, const pbn_table* t, GroupBatch& b, const std::vector<int>& order, size_t p0, size_t p1, double* dev_out,
                double* dev_out_max, bool force_f64) {
     const int np = (int)(p1 - p0);
+    const bool sdbg = g_stage_capture.load(std::memory_order_relaxed);   // pbn_debug_group_stages
     // ---- layout ----------------------------------------------------------------------------------------------------------
     std::vector<GPool> pools(np);
     std::vector<GUnit> units;
@@ -767,6 +788,8 @@ void run_chunk(pbn_ctx* ctx, const pbn_table* t, GroupBatch& b, const std::vecto
     int32_t* hb = (int32_t*)(h.data() + o_blkpool);
     for (int k = 0; k < np; ++k)
         for (int j = 0; j <= pools[k].nblk; ++j) hb[pools[k].blk0 + j] = k;
+    std::vector<float> dbg_margin;
+    if (sdbg) for (int u = 0; u < nu; ++u) dbg_margin.push_back(hs[u].margin);
     std::vector<int32_t> hw((size_t)(total_wg / 64 + 1));
     for (int u = 0; u < nu; ++u) {
         const int64_t w0 = units[u].wg0 / 64, w1 = w0 + ((int64_t)units[u].nwg + 63) / 64;
@@ -858,6 +881,43 @@ void run_chunk(pbn_ctx* ctx, const pbn_table* t, GroupBatch& b, const std::vecto
         hipLaunchKernelGGL(group_reduce_kernel, dim3((unsigned)nu), dim3(256), 0, st, g, dev_out);
         HIP_CHECK(hipGetLastError());
     }
+    if (sdbg) {   // pbn_debug_group_stages: one record per chunk
+        StageChunk c;
+        c.pools = pools; c.units = units; c.margin = dbg_margin;
+        c.o_vals = o_vals_b; c.o_reg = o_reg;
+        const long long head[12] = {np, nu, f16 ? 1 : 0, KS, fold ? 1 : 0, moments ? 1 : 0, bboxes ? 1 : 0, g.window, g.tile_window, g.use_sum_bound, d0, t->dtype};
+        std::memcpy(c.head, head, sizeof(head));
+        c.arena.resize(off);
+        c.sums.resize((size_t)nu);
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipMemcpy(c.arena.data(), arena, off, hipMemcpyDeviceToHost));
+        for (int u = 0; u < nu; ++u) HIP_CHECK(hipMemcpy(&c.sums[(size_t)u], dev_out + units[(size_t)u].sum_slot, sizeof(double), hipMemcpyDeviceToHost));
+        const size_t es = dtype_size(t->dtype);
+        for (const GPool& P : pools) {
+            std::vector<int64_t> id((size_t)P.n);
+            if (P.rows) {
+                std::vector<int32_t> list((size_t)P.n);
+                HIP_CHECK(hipMemcpy(list.data(), P.rows + P.row_base, (size_t)P.n * sizeof(int32_t), hipMemcpyDeviceToHost));
+                for (int i = 0; i < P.n; ++i) id[(size_t)i] = list[(size_t)i];
+            } else {
+                for (int i = 0; i < P.n; ++i) id[(size_t)i] = P.row_base + i;
+            }
+            const int64_t lo = *std::min_element(id.begin(), id.end()), hi = *std::max_element(id.begin(), id.end());
+            std::vector<double> x((size_t)P.n * P.d);
+            std::vector<char> col((size_t)(hi - lo + 1) * es);
+            for (int j = 0; j < P.d; ++j) {
+                HIP_CHECK(hipMemcpy(col.data(), (const char*)t->col(P.cols[j]) + (size_t)lo * es, col.size(), hipMemcpyDeviceToHost));
+                for (int i = 0; i < P.n; ++i) {
+                    const size_t k = (size_t)(id[(size_t)i] - lo);
+                    x[(size_t)i * P.d + j] = t->dtype == PBN_F64 ? ((const double*)col.data())[k] : (double)((const float*)col.data())[k];
+                }
+            }
+            c.rows.push_back(std::move(x));
+            c.rowid.push_back(std::move(id));
+        }
+        std::lock_guard<std::mutex> lk(g_stage_mu);
+        g_stage.push_back(std::move(c));
+    }
 }
 
 // bytes of arena a pool needs (its element arrays + its units' buffers), for chunking
@@ -940,3 +1000,88 @@ void kde_group_run(pbn_ctx* ctx, const pbn_table* t, GroupBatch& b, double* dev_
 }
 
 }  // namespace pbn
+
+// pbn_debug_group_stages (test aid, not part of the C ABI header).  capture != 0 arms the aid (run_chunk then synchronises behind its reduce
+// and appends one record per chunk), capture == 0 disarms it; capture == 0 with chunk < 0 also clears the store.  chunk < 0: returns the
+// number of records.  Otherwise copies up to cap items of (chunk, what, index) into out and returns how many there are (-1: no such item):
+//   what 0 (index ignored) 12 int64: pools, units, f16, KS, fold, moment pass ran, batch boxes ran, window, tile_window, use_sum_bound, d, table dtype
+//   pool `index` of the chunk:
+//   10 int64 [8 + 8 + 65 + 64]: n, R, d, kd, nblk, row_base, nunits, unit0 (first unit in the chunk's unit order), cols[8], rb[65], test_unit[64]
+//   11 double [64 + 8]: Wg, mug      12 double [n][d]: table values by pool position (gather list resolved)      13 uint32 [n]: sorted vals
+//   14 uint8 [n]: reg of the sorted elements      15 int64 [n]: table row by pool position
+//   unit `index` of the chunk:
+//   20 int64 [14]: pool, test_region, train_mask, N, nq, ntiles, nqtiles, tps, nsplit, nsplit_fin, sum_slot, mstride, bbox present, mom present
+//   21 double [3 + 64 + 8]: lognorm, the sweep record's prune margin, dev_out[sum_slot], W, mu
+//   22 zs double [N][d]   23 zq double [nq][d]   24 qpos int32 [nqtiles 16]   25 box double [ntiles][2 kd]   26 bbox double [nsplit nbps][2 kd]
+//   27 qbox double [nqtiles][2 kd]   28 qthr double [nqtiles]   29 qlb double [nqtiles 16]   30 rad2 float [ntiles]
+//   31 mom double [record][mstride] (value k of tile t at [k mstride + t])   32 part double [nsplit_fin][nqtiles 16][2]
+extern "C" int64_t pbn_debug_group_stages(int chunk, int what, int index, void* out, int64_t cap, int capture) {
+    using namespace pbn;
+    g_stage_capture.store(capture != 0);
+    std::lock_guard<std::mutex> lk(g_stage_mu);
+    if (chunk < 0) {
+        const int64_t n = (int64_t)g_stage.size();
+        if (!capture) g_stage.clear();
+        return n;
+    }
+    if (chunk >= (int)g_stage.size()) return -1;
+    const StageChunk& c = g_stage[(size_t)chunk];
+    auto copy = [&](const void* src, size_t count, size_t size) -> int64_t {
+        if (out && count) std::memcpy(out, src, std::min<size_t>(count, (size_t)std::max<int64_t>(cap, 0)) * size);
+        return (int64_t)count;
+    };
+    if (what == 0) return copy(c.head, 12, 8);
+    if (what >= 10 && what < 20) {
+        if (index < 0 || index >= (int)c.pools.size()) return -1;
+        const GPool& P = c.pools[(size_t)index];
+        switch (what) {
+            case 10: {
+                std::vector<long long> v = {P.n, P.R, P.d, P.kd, P.nblk, P.row_base, P.nunits, P.unit0};
+                v.insert(v.end(), P.cols, P.cols + PBN_GROUP_MAX_D);
+                v.insert(v.end(), P.rb, P.rb + PBN_GROUP_MAX_R + 1);
+                v.insert(v.end(), P.test_unit, P.test_unit + PBN_GROUP_MAX_R);
+                return copy(v.data(), v.size(), 8);
+            }
+            case 11: {
+                std::vector<double> v(P.Wg, P.Wg + PBN_GROUP_MAX_D * PBN_GROUP_MAX_D);
+                v.insert(v.end(), P.mug, P.mug + PBN_GROUP_MAX_D);
+                return copy(v.data(), v.size(), 8);
+            }
+            case 12: return copy(c.rows[(size_t)index].data(), c.rows[(size_t)index].size(), 8);
+            case 13: return copy(c.arena.data() + c.o_vals + P.elem0 * 4, (size_t)P.n, 4);
+            case 14: return copy(c.arena.data() + c.o_reg + P.elem0, (size_t)P.n, 1);
+            case 15: return copy(c.rowid[(size_t)index].data(), c.rowid[(size_t)index].size(), 8);
+            default: return -1;
+        }
+    }
+    if (index < 0 || index >= (int)c.units.size()) return -1;
+    const GUnit& U = c.units[(size_t)index];
+    const GPool& P = c.pools[(size_t)U.pool];
+    const char* a = c.arena.data();
+    const int64_t mstride = ((int64_t)U.ntiles + 63) / 64 * 64, nbps = (U.tps + 63) / 64;
+    switch (what) {
+        case 20: {
+            const long long v[14] = {U.pool, U.test_region, (long long)U.train_mask, U.N, U.nq, U.ntiles, U.nqtiles, U.tps, U.nsplit, U.nsplit_fin,
+                                     U.sum_slot, mstride, U.bbox ? 1 : 0, U.mom ? 1 : 0};
+            return copy(v, 14, 8);
+        }
+        case 21: {
+            std::vector<double> v = {U.lognorm, (double)c.margin[(size_t)index], c.sums[(size_t)index]};
+            v.insert(v.end(), U.W, U.W + PBN_GROUP_MAX_D * PBN_GROUP_MAX_D);
+            v.insert(v.end(), U.mu, U.mu + PBN_GROUP_MAX_D);
+            return copy(v.data(), v.size(), 8);
+        }
+        case 22: return copy(a + U.zs, (size_t)U.N * P.d, 8);
+        case 23: return copy(a + U.zq, (size_t)U.nq * P.d, 8);
+        case 24: return copy(a + U.qpos, (size_t)U.nqtiles * 16, 4);
+        case 25: return copy(a + U.box, (size_t)U.ntiles * 2 * P.kd, 8);
+        case 26: return U.bbox ? copy(a + U.bbox, (size_t)U.nsplit * nbps * 2 * P.kd, 8) : 0;
+        case 27: return copy(a + U.qbox, (size_t)U.nqtiles * 2 * P.kd, 8);
+        case 28: return copy(a + U.qthr, (size_t)U.nqtiles, 8);
+        case 29: return copy(a + U.qlb, (size_t)U.nqtiles * 16, 8);
+        case 30: return U.rad2 ? copy(a + U.rad2, (size_t)U.ntiles, 4) : 0;
+        case 31: return U.mom ? copy(a + U.mom, (size_t)mstride * pbn_mom_rec(P.d), 8) : 0;
+        case 32: return copy(a + U.part, (size_t)U.nsplit_fin * U.nqtiles * 16 * 2, 8);
+        default: return -1;
+    }
+}
