@@ -616,6 +616,22 @@ double pbn_mi_pvalue(void* user, int v1, int v2, int n_cond, const int* cond);
 void pbn_mi_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond,
                          double* out); /* pbn_ci_pvalue_batch_fn: one launch for many tests */
 int pbn_mi_set_order(pbn_mi* h, int n, const int* ids);
+/* The count-only tests of pbn_mi_pvalue_batch - x, y and Z all categorical: the discrete overloads of
+ * learning/independences/hybrid/mutual_information.cpp:926-1055,1093-1137 over the joint_counts layout of
+ * factors/discrete/discrete_indices.cpp:134-150.  Those with at most 6 conditioning variables, no variable named twice and at most
+ * pbn_mi_discrete_batch_max_cells() cells whose variable set the handle has not grouped yet are counted in one device pass per launch
+ * chunk (the joint-count kernel of pbn_chisq_pvalue_batch: no sort, no row grouping); the statistic is pbn_mi_pvalue's own host
+ * routine on those integer counts, so a batched p-value is bit-identical to pbn_mi_pvalue of the same test.  Every other test of the
+ * call takes the grouping path, and so does every test while the environment holds PBN_MI_DISCRETE_BATCH=0 (read per call).
+ * pbn_mi_discrete_batch_stats: cumulative count-only tests of batch calls counted by the kernel / read off a cached grouping / sent to
+ * the grouping path (each output may be NULL). */
+int pbn_mi_discrete_batch_stats(const pbn_mi* h, int64_t* device_tests, int64_t* cached_tests, int64_t* grouped_tests);
+/* mutual_information.cpp:926-1055,1093-1137, discrete_indices.cpp:134-150: calls with fewer eligible count-only tests than min_tests
+ * keep them on the grouping path (0: every eligible test goes to the kernel).  Results do not depend on it. */
+int pbn_mi_discrete_set_batch_threshold(pbn_mi* h, int64_t min_tests);
+/* mutual_information.cpp:926-1055,1093-1137, discrete_indices.cpp:134-150: the cell cap of a count-only test on the kernel (prod of
+ * the cardinalities of x, y and Z). */
+int pbn_mi_discrete_batch_max_cells(void);
 /* ChiSquare::pvalue (learning/independences/discrete/chi_square.cpp:8-139) over the discrete columns of the same
  * handle (pbn_ci_pvalue_fn signature). */
 double pbn_chisq_pvalue(void* user, int v1, int v2, int n_cond, const int* cond);

@@ -125,6 +125,9 @@ SIGNATURES = {
     "pbn_chisq_batch_max_cells": (_int, []),
     "pbn_chisq_batch_max_cond": (_int, []),
     "pbn_mi_set_order": (_int, [_vp, _int, _ip]),
+    "pbn_mi_discrete_batch_stats": (_int, [_vp] + [C.POINTER(_i64)] * 3),
+    "pbn_mi_discrete_set_batch_threshold": (_int, [_vp, _i64]),
+    "pbn_mi_discrete_batch_max_cells": (_int, []),
     "pbn_mi_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_mi_set_continuous_nulls": (_int, [_vp, C.POINTER(C.c_ubyte), _dp]),
     "pbn_mi_lincor_pvalue": (C.c_double, [_vp, _int, _int, _int, _ip]),

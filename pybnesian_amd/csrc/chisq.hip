@@ -10,8 +10,9 @@
 // workgroup then adds its table into the test's table in global memory.  No sort, no permutation, one launch per chunk of tests.
 //
 // The counting itself is the joint-count kernel of joint_counts.hip in its LDS form under the BY_CARD policy: the null
-// bucket of a column, code == card, fails it.  What is kept here: decoding and eligibility of the requests, a descriptor per test,
-// chisq_from_counts, the capture / phase test aid and the scalar routine.
+// bucket of a column, code == card, fails it.  What is kept here: decoding and eligibility of the requests, chisq_from_counts, the
+// capture / phase test aid, the scalar routine - and mi::count_tables, the chunk runner (byte mirror, a descriptor per test, slices,
+// launch chunks) that the count-only tests of pbn_mi_pvalue_batch (mi.hip) share.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -31,7 +32,7 @@ constexpr int MAX_CELLS = 4096;            // cells of one contingency table cou
 constexpr int MAX_COND = 6;                // conditioning variables of a device test (pbn_chisq_batch_max_cond)
 constexpr int MAX_VARS = MAX_COND + 2;
 static_assert(joint::MAX_VARS >= MAX_VARS, "x, y and the conditioning set fit the descriptor");
-static_assert(MAX_CELLS <= joint::LDS_WORDS, "a table fits the LDS form");
+static_assert(MAX_CELLS <= mi::COUNT_LDS_MAX_CELLS && mi::COUNT_LDS_MAX_CELLS <= joint::LDS_WORDS, "a table fits the LDS form");
 
 }  // namespace chisq
 }  // namespace pbn
@@ -78,22 +79,13 @@ std::mutex g_chisq_mu;
 std::vector<int64_t> g_chisq_rec;
 double g_chisq_phase[5] = {0, 0, 0, 0, 0};   // seconds: request and descriptors, memset, kernel, download, host finish
 
-struct ChisqTest {   // one slot of a batch call
-    int m = 0;
-    int vars[chisq::MAX_VARS];   // variable ids, x, y, Z
-    int G = 0;
-    int where = -1;              // 1 device, 0 host, -1 refused (NaN)
-    int slices = 0, copies = 0;
-};
+using ChisqTest = mi::CountTest;   // one slot of a batch call; where: 1 device, 0 host, -1 refused (NaN)
 
-// The device part of pbn_chisq_pvalue_batch: the tests `which` (all eligible), chunk by chunk through joint::run_chunk, then
-// chisq_from_counts on the host threads.  `tables` (capture only) receives every test's integer table.
+// The device part of pbn_chisq_pvalue_batch: the tests `which` (all eligible) counted by mi::count_tables, then chisq_from_counts on the
+// host threads, chunk by chunk.  `tables` (capture only) receives every test's integer table.
 void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vector<int>& which, const int* cond_off, double* out, int* width,
                         std::vector<std::vector<uint32_t>>* tables) {
-    pbn_ctx* ctx = h->ctx;
-    HIP_CHECK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int64_t N = h->N;
+    hipStream_t st = h->ctx->stream;
     const bool timing = (g_chisq_capture.load() & 2) != 0;
     double tp = mi_now();
     std::function<void(int)> phase;   // the phase clock: request and descriptors, memset, kernel, download
@@ -103,6 +95,30 @@ void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vec
         g_chisq_phase[i] += t - tp;
         tp = t;
     };
+    *width = mi::count_tables(h, tests, which, phase, [&](size_t base, int T, const std::vector<joint::Desc>& descs, const uint32_t* all) {
+        host_finish(T, [&](int i) {
+            const int slot = which[base + i];
+            const ChisqTest& t = tests[slot];
+            const uint32_t* c = all + descs[i].table_off;
+            std::vector<double> cnt((size_t)t.G);
+            for (int g = 0; g < t.G; ++g) cnt[g] = (double)c[g];
+            const int cx = descs[i].card[0], cy = descs[i].card[1];
+            out[slot] = chisq_from_counts(cnt.data(), cx, cy, t.G / (cx * cy), cond_off[slot + 1] - cond_off[slot]);
+            if (tables) (*tables)[slot].assign(c, c + t.G);
+        });
+        if (timing) { const double t = mi_now(); g_chisq_phase[4] += t - tp; tp = t; }
+        h->cs.device_tests += T;
+    });
+}
+
+}  // namespace
+
+// mi_internal.hpp: the one chunk runner behind pbn_chisq_pvalue_batch and the count-only tests of pbn_mi_pvalue_batch
+int pbn::mi::count_tables(pbn_mi* h, std::vector<CountTest>& tests, const std::vector<int>& which, const std::function<void(int)>& phase,
+                          const std::function<void(size_t, int, const std::vector<joint::Desc>&, const uint32_t*)>& finish) {
+    pbn_ctx* ctx = h->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    const int64_t N = h->N;
     if (h->cs.codes8_state == 0) {   // the byte mirror: a quarter of the bytes of every later pass
         // built when every CODE fits a byte: card - 1, or card where the column has a null bucket, <= 255.  256 categories without a null
         // still fit; their code 255 is also the byte that pads the mirror past N, which the kernel's row bound keeps out, not its value.
@@ -118,24 +134,26 @@ void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vec
         }
     }
     const bool bytes = h->cs.codes8_state == 1;
-    *width = bytes ? 1 : 4;
     joint::Codes codes;
     codes.codes32 = h->codes_dev.p; codes.ld32 = N;
     if (bytes) { codes.codes8 = h->cs.codes8.p; codes.ld8 = h->cs.ld8; }
     static const int r_max = PBN_TUNE(CHISQ_COPIES, joint::MAX_COPIES);
     static const int blocks_per_cu = PBN_TUNE(CHISQ_BLOCKS_PER_CU, 8);
-    std::vector<joint::Desc> both[2];   // every test takes the LDS form
-    std::vector<joint::Desc>& descs = both[0];
+    std::vector<joint::Desc> both[2];   // LDS form, global form: what run_chunk launches
+    std::vector<joint::Desc> descs;     // the chunk's tests in call order
     for (size_t base = 0; base < which.size();) {
         // a chunk: as many tests as keep the count buffer within CHISQ_CHUNK_CELLS
         size_t end = base, cells = 0;
         while (end < which.size() && end - base < ((size_t)1 << 18) && cells + (size_t)tests[which[end]].G <= CHISQ_CHUNK_CELLS) cells += (size_t)tests[which[end++]].G;
+        if (end == base) throw invalid_error("joint counts: a table larger than a launch chunk");
         const int T = (int)(end - base);
         const int64_t want = std::max<int64_t>(1, ceil_div((int64_t)ctx->num_cus * blocks_per_cu, T));   // slices that fill the chip (plan_slices)
         descs.assign((size_t)T, joint::Desc{});
+        both[0].clear(); both[1].clear();
         size_t off = 0;
+        int n_global = 0;
         for (int i = 0; i < T; ++i) {
-            ChisqTest& t = tests[which[base + i]];
+            CountTest& t = tests[which[base + i]];
             joint::Desc& d = descs[i];
             d.m = t.m; d.G = t.G;
             int stride = 1;
@@ -145,30 +163,25 @@ void chisq_batch_device(pbn_mi* h, std::vector<ChisqTest>& tests, const std::vec
                 d.stride[j] = stride;
                 stride *= d.card[j];
             }
-            joint::plan_slices(d, 0, N, bytes, true, want, r_max);
+            const bool lds = t.G <= COUNT_LDS_MAX_CELLS;
+            joint::plan_slices(d, 0, N, bytes, lds, want, r_max);
             d.table_off = (int64_t)off;
             off += (size_t)t.G;
-            t.slices = d.slices; t.copies = d.copies;
+            t.slices = d.slices; t.copies = lds ? d.copies : 0;
+            n_global += lds ? 0 : 1;
+        }
+        if (n_global == 0) {   // every ChiSquare chunk: the descriptors as they stand, no copy
+            both[0].swap(descs);
+        } else {
+            for (const joint::Desc& d : descs) both[d.G <= COUNT_LDS_MAX_CELLS ? 0 : 1].push_back(d);
         }
         joint::run_chunk(ctx, h->cs.scratch, both, cells, codes, joint::BY_CARD, phase);
-        const uint32_t* all = h->cs.scratch.host.data();
-        host_finish(T, [&](int i) {
-            const int slot = which[base + i];
-            const ChisqTest& t = tests[slot];
-            const uint32_t* c = all + descs[i].table_off;
-            std::vector<double> cnt((size_t)t.G);
-            for (int g = 0; g < t.G; ++g) cnt[g] = (double)c[g];
-            const int cx = descs[i].card[0], cy = descs[i].card[1];
-            out[slot] = chisq_from_counts(cnt.data(), cx, cy, t.G / (cx * cy), cond_off[slot + 1] - cond_off[slot]);
-            if (tables) (*tables)[slot].assign(c, c + t.G);
-        });
-        if (timing) { const double t = mi_now(); g_chisq_phase[4] += t - tp; tp = t; }
-        h->cs.device_tests += T;
+        if (n_global == 0) both[0].swap(descs);
+        finish(base, T, descs, h->cs.scratch.host.data());
         base = end;
     }
+    return bytes ? 1 : 4;
 }
-
-}  // namespace
 
 extern "C" {
 

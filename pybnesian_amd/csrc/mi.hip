@@ -9,6 +9,7 @@
 // moments are additive, so every pooled covariance is a sum of per-configuration moments on the host.
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -16,6 +17,7 @@
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <mutex>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -32,6 +34,17 @@ using namespace pbn;
 #define MI_SORTED_MAX_CONT 16     // continuous variables the register-accumulator kernel is instantiated for (152 accumulators)
 #define MI_SORTED_ROWS 4096       // rows of one configuration a 256-thread block sums
 #define MI_GROUP_CACHE 1024       // cached row groupings (one per set of discrete variables), least recently used out
+// pbn_mi_pvalue_batch: a call with fewer eligible count-only tests without a cached grouping keeps them on the grouping path; the cell
+// cap of such a test.  Both from tools/mi_discrete_timing.py on an MI355X (profiles/mi_discrete/mi_discrete_timing.json).
+#define MI_DISCRETE_BATCH_MIN_TESTS 2
+
+namespace pbn {
+namespace mi {
+constexpr int DISCRETE_MAX_CELLS = 1 << 22;
+constexpr int DISCRETE_MAX_COND = 6;       // conditioning variables of a device test
+static_assert(joint::MAX_VARS >= DISCRETE_MAX_COND + 2, "x, y and the conditioning set fit the descriptor");
+}  // namespace mi
+}  // namespace pbn
 
 namespace {
 
@@ -715,19 +728,24 @@ struct Engine {
         h->t_device += mi_now() - td0;
     }
 
-    // Per-configuration statistics of a list of tests.  The counts are the segment lengths of the test's DiscGroup (no
-    // data pass at all for a purely discrete test); the continuous moments come from the sorted-segment kernels, batched
-    // by the number of continuous variables.  More than MI_SORTED_MAX_CONT continuous variables: the LDS-cell kernel.
-    void group_stats_many(const std::vector<Plan>& plans, std::vector<std::vector<double>>& outs) {
-        outs.assign(plans.size(), {});
-        if (h->N <= 0) { for (size_t t = 0; t < plans.size(); ++t) outs[t].assign((size_t)plans[t].G * plans[t].stats, 0.0); return; }
-        while (h->groups.size() > MI_GROUP_CACHE) {   // least recently used out (never during a batch: groups are referenced below)
+    // the grouping cache back to its size, least recently used out (never during a batch: groups are referenced there)
+    void trim_groups() {
+        while (h->groups.size() > MI_GROUP_CACHE) {
             auto lru = h->groups.begin();
             for (auto it = h->groups.begin(); it != h->groups.end(); ++it)
                 if (it->second->stamp < lru->second->stamp) lru = it;
             if (lru->second->full_ready) h->full_bytes_held -= std::min(h->full_bytes_held, full_bytes(*lru->second));
             h->groups.erase(lru);
         }
+    }
+
+    // Per-configuration statistics of a list of tests.  The counts are the segment lengths of the test's DiscGroup (no
+    // data pass at all for a purely discrete test); the continuous moments come from the sorted-segment kernels, batched
+    // by the number of continuous variables.  More than MI_SORTED_MAX_CONT continuous variables: the LDS-cell kernel.
+    void group_stats_many(const std::vector<Plan>& plans, std::vector<std::vector<double>>& outs) {
+        outs.assign(plans.size(), {});
+        if (h->N <= 0) { for (size_t t = 0; t < plans.size(); ++t) outs[t].assign((size_t)plans[t].G * plans[t].stats, 0.0); return; }
+        trim_groups();
         std::vector<Plan> legacy;
         std::vector<size_t> legacy_idx;
         std::vector<const std::vector<int>*> cmap(plans.size(), nullptr);
@@ -967,6 +985,17 @@ struct Engine {
     }
 };
 
+// pbn_debug_mi_discrete (test aid, not part of the C ABI header; see its definition)
+std::atomic<int> g_mid_capture{0};
+std::mutex g_mid_mu;
+std::vector<int64_t> g_mid_rec;
+
+// cells of one count-only test of pbn_mi_pvalue_batch on the device (pbn_mi_discrete_batch_max_cells)
+int discrete_max_cells() {
+    static const int v = std::max(1, PBN_TUNE(MI_DISCRETE_MAX_CELLS, mi::DISCRETE_MAX_CELLS));
+    return v;
+}
+
 }  // namespace
 
 // ---- what chisq.hip and lincor.hip use of this unit (mi_internal.hpp) ----------------------------------------------
@@ -1105,10 +1134,21 @@ double pbn_mi_pvalue(void* user, int v1, int v2, int n_cond, const int* cond) {
 
 // Batched form: n_tests independence tests in as few launches as scratch memory allows (pbn_ci_pvalue_batch_fn).
 // cond_off has n_tests + 1 entries into cond.  NaN in out[i] marks a failed test (pbn_last_error has the last reason).
+//
+// The count-only tests of a call (x, y and Z all categorical: plan.c == 0) need the cell counts of one table and nothing else.  Those that
+// are eligible - at most mi::DISCRETE_MAX_COND conditioning variables, no variable twice, N > 0, at most pbn_mi_discrete_batch_max_cells()
+// cells - and whose variable set has no cached grouping are counted by the joint-count kernel (mi::count_tables, chisq.hip; DESIGN.md
+// 3.19): no DiscGroup, no sort, no permutation.  The descriptor lists the columns in the plan's own order with strides of card under
+// BY_CARD, so the device table IS the plan's statistics vector; mi_from_stats, rows_of, df and gamma_q then run on the same integers as
+// doubles as after a grouping - out[i] is bit-identical to pbn_mi_pvalue of test i.  A cached grouping is read as before; every other
+// test of the call goes through group_stats_many as before.  PBN_MI_DISCRETE_BATCH=0 (read per call) sends everything there.
 void pbn_mi_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, const int* cond_off, const int* cond, double* out) {
     pbn_mi* h = (pbn_mi*)user;
-    for (int i = 0; i < n_tests; ++i) out[i] = std::nan("");
-    (void)guarded([&] {
+    for (int i = 0; out && i < n_tests; ++i) out[i] = std::nan("");
+    // the context's lock first, as pbn_chisq_pvalue_batch takes it (the byte mirror and the count scratch of the handle are shared with
+    // it), then the process-wide one that this entry point and the scalar routine have always held
+    (void)guarded(mu_of(h), [&] {
+        std::lock_guard<std::recursive_mutex> api_lock(api_mutex());
         if (!h || !v1 || !v2 || !cond_off || !out) throw invalid_error("pbn_mi_pvalue_batch: null argument");
         Engine e{h};
         std::vector<Query> qs(n_tests);
@@ -1121,9 +1161,74 @@ void pbn_mi_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, 
             qs[i] = e.make(vars[0], vars[1], (int)vars.size() - 2, vars.data() + 2);
             plans[i] = e.plan(qs[i]);
         }
+        const int64_t groups0 = h->groups_built;
+        const bool capture = g_mid_capture.load() != 0;
+        // where a test goes: -1 not count-only, 0 the grouping path, 1 the kernel, 2 a cached grouping
+        std::vector<signed char> where((size_t)n_tests, -1);
+        for (int i = 0; i < n_tests; ++i) where[i] = plans[i].c == 0 ? 0 : -1;
+        std::vector<mi::CountTest> cts;
+        std::vector<int> device;
+        if (knob_int("PBN_MI_DISCRETE_BATCH", 1) != 0 && h->N > 0) {   // read per call
+            e.trim_groups();   // before the look-ups: what is cached now stays for the whole call
+            cts.resize((size_t)n_tests);
+            const int max_cells = discrete_max_cells();
+            for (int i = 0; i < n_tests; ++i) {
+                const Engine::Plan& p = plans[i];
+                if (p.c != 0) continue;
+                const int m = (int)p.disc.size();
+                if (m > mi::DISCRETE_MAX_COND + 2 || p.G > max_cells) continue;
+                vars = p.disc;
+                std::sort(vars.begin(), vars.end());
+                if (std::adjacent_find(vars.begin(), vars.end()) != vars.end()) continue;   // a variable named twice
+                auto it = h->groups.find(vars);
+                if (it != h->groups.end()) { where[i] = 2; continue; }
+                mi::CountTest& t = cts[i];
+                t.m = m; t.G = p.G;
+                for (int j = 0; j < m; ++j) t.vars[j] = p.disc[j];
+                device.push_back(i);
+            }
+            if ((int64_t)device.size() < (h->db.threshold < 0 ? MI_DISCRETE_BATCH_MIN_TESTS : h->db.threshold)) device.clear();
+        }
         std::vector<std::vector<double>> st;
+        std::vector<std::vector<uint32_t>> tables;
+        if (capture) tables.resize((size_t)n_tests);
+        int width = 0;
         const double t0 = mi_now(), g0 = h->t_group, d0 = h->t_device;
-        e.group_stats_many(plans, st);
+        if (device.empty()) {
+            e.group_stats_many(plans, st);
+        } else {
+            st.assign((size_t)n_tests, {});
+            const double td = mi_now();
+            width = mi::count_tables(h, cts, device, nullptr, [&](size_t base, int T, const std::vector<joint::Desc>& descs, const uint32_t* all) {
+                host_finish(T, [&](int i) {
+                    const int slot = device[base + i];
+                    const uint32_t* c = all + descs[i].table_off;
+                    const int G = cts[slot].G;
+                    st[slot].resize((size_t)G);
+                    for (int g = 0; g < G; ++g) st[slot][g] = (double)c[g];
+                    if (capture) tables[slot].assign(c, c + G);
+                });
+                ++h->device_launches;
+            });
+            h->t_device += mi_now() - td;
+            for (int i : device) where[i] = 1;
+            h->device_passes += (int64_t)device.size();   // pbn_mi_stats: one device pass per test served
+            h->count_only += (int64_t)device.size();
+            std::vector<Engine::Plan> rest;
+            std::vector<int> rest_idx;
+            for (int i = 0; i < n_tests; ++i)
+                if (where[i] != 1) { rest.push_back(plans[i]); rest_idx.push_back(i); }
+            if (!rest.empty()) {
+                std::vector<std::vector<double>> rs;
+                e.group_stats_many(rest, rs);
+                for (size_t j = 0; j < rest.size(); ++j) st[rest_idx[j]].swap(rs[j]);
+            }
+        }
+        for (int i = 0; i < n_tests; ++i) {
+            if (where[i] == 1) ++h->db.device_tests;
+            else if (where[i] == 2) ++h->db.cached_tests;
+            else if (plans[i].c == 0) ++h->db.grouped_tests;
+        }
         const double t1 = mi_now();
         h->t_prep += (t1 - t0) - (h->t_group - g0) - (h->t_device - d0);
         // determinants, entropies and chi-square tails of the tests: independent host arithmetic on their statistics - spread over
@@ -1135,7 +1240,61 @@ void pbn_mi_pvalue_batch(void* user, int n_tests, const int* v1, const int* v2, 
         host_finish(n_tests, finish);
         h->t_host += mi_now() - t1;
         ++h->batches;
+        if (capture) {
+            std::vector<int64_t> r{3, n_tests, groups0, h->groups_built};
+            for (int i = 0; i < n_tests; ++i) {
+                const bool dev = where[i] == 1;
+                r.insert(r.end(), {(int64_t)where[i], dev ? width : 0, dev ? cts[i].slices : 0, dev ? cts[i].copies : 0,
+                                   plans[i].c == 0 ? (int64_t)plans[i].G : 0, (int64_t)tables[i].size()});
+                r.insert(r.end(), tables[i].begin(), tables[i].end());
+            }
+            std::lock_guard<std::mutex> lk(g_mid_mu);
+            g_mid_rec.insert(g_mid_rec.end(), r.begin(), r.end());
+        }
     });
+}
+
+// mutual_information.cpp:926-1055,1093-1137 on the joint_counts layout of discrete_indices.cpp:134-150: the counters of the count-only
+// tests of pbn_mi_pvalue_batch
+int pbn_mi_discrete_batch_stats(const pbn_mi* h, int64_t* device_tests, int64_t* cached_tests, int64_t* grouped_tests) {
+    return guarded(mu_of(h), [&] {
+        if (!h) throw invalid_error("pbn_mi_discrete_batch_stats: null argument");
+        if (device_tests) *device_tests = h->db.device_tests;
+        if (cached_tests) *cached_tests = h->db.cached_tests;
+        if (grouped_tests) *grouped_tests = h->db.grouped_tests;
+    });
+}
+
+int pbn_mi_discrete_set_batch_threshold(pbn_mi* h, int64_t min_tests) {
+    return guarded(mu_of(h), [&] {
+        if (!h || min_tests < 0) throw invalid_error("pbn_mi_discrete_set_batch_threshold: bad argument");
+        h->db.threshold = min_tests;
+    });
+}
+
+int pbn_mi_discrete_batch_max_cells(void) { return discrete_max_cells(); }
+
+// pbn_debug_mi_discrete (test aid, not part of the C ABI header; the record layout of pbn_debug_chisq).  op 1 arms the capture and clears
+// it, op 0 disarms and clears, op 2 copies up to `cap` int64 of the records into out and returns how many are held.  While armed, every
+// pbn_mi_pvalue_batch call that succeeds appends one record:
+//   3, n_tests, the handle's count of row groupings built before the call and after it, then per test in call order
+//      where (1 = counted by the kernel, 2 = read off a cached grouping, 0 = a count-only test on the grouping path, -1 = not a
+//      count-only test), code width in bytes (1 = the byte mirror, 4 = int32; 0 off the kernel), slices, R (the replicated LDS
+//      sub-tables, 0 in the global form; both 0 off the kernel), G (cells; 0 when the test is not count-only), n (G on the kernel, else
+//      0), and the n cell counts as copied back from the device, x fastest, then y, then Z as given.
+// Unarmed, a call pays one flag test; no kernel and no result depends on any of it.
+int64_t pbn_debug_mi_discrete(int op, int64_t* out, int64_t cap) {
+    std::lock_guard<std::mutex> lk(g_mid_mu);
+    if (op == 0 || op == 1) {
+        g_mid_rec.clear();
+        g_mid_capture.store(op);
+        return 0;
+    }
+    if (op == 2) {
+        for (int64_t i = 0; out && i < (int64_t)g_mid_rec.size() && i < cap; ++i) out[i] = g_mid_rec[(size_t)i];
+        return (int64_t)g_mid_rec.size();
+    }
+    return -1;
 }
 
 // Index space of pbn_mi_pvalue: external index i stands for variable ids[i] (n == 0 restores the identity).

@@ -1,6 +1,7 @@
 // The pbn_mi handle (mi.hip) as the other independence tests over it see it - ChiSquare (chisq.hip) and the null-aware
 // LinearCorrelation (lincor.hip): the handle, its row groupings, and the two services of mi.hip they build on.
 #pragma once
+#include <functional>
 #include <map>
 #include <memory>
 #include <vector>
@@ -73,6 +74,12 @@ struct pbn_mi {
         int64_t device_tests = 0, host_tests = 0;
         int64_t threshold = -1;      // pbn_chisq_set_batch_threshold; negative: not set, chisq.hip's CHISQ_BATCH_MIN_TESTS
     } cs;
+    // the count-only tests of pbn_mi_pvalue_batch (mi.hip): counted through the same mirror and scratch (cs above, under the context's
+    // lock); the counters of pbn_mi_discrete_batch_stats
+    struct DiscreteBatchState {
+        int64_t device_tests = 0, cached_tests = 0, grouped_tests = 0;
+        int64_t threshold = -1;      // pbn_mi_discrete_set_batch_threshold; negative: not set, mi.hip's MI_DISCRETE_BATCH_MIN_TESTS
+    } db;
     // pbn_mi_lincor_pvalue_batch (lincor_null_batch.hip): the split of the table's rows into clean ones (no NaN in any continuous
     // column: one Gram of all columns serves every test) and dirty ones (kept as a compact row-major copy that the per-test kernel
     // walks), built by the first batch; the grow-only buffers of a launch chunk; the counters of pbn_mi_lincor_batch_stats
@@ -101,6 +108,27 @@ void group_stats(pbn_mi* h, const std::vector<int>& cont, const std::vector<int>
 // vars = [v1, v2, cond...] as variable ids: through the handle's order (pbn_mi_set_order) when one is set, else as given.  false when
 // an index lies outside the order.  No kind check and no message: every entry point refuses in its own words.
 bool map_request(const pbn_mi* h, int v1, int v2, int n_cond, const int* cond, std::vector<int>& vars);
+
+// One table of a batch call that counts on the device: ChiSquare's contingency tables (chisq.hip) and the count-only tests of
+// pbn_mi_pvalue_batch (mi.hip).
+struct CountTest {
+    int m = 0;
+    int vars[joint::MAX_VARS];   // variable ids, x, y, Z: the first fastest
+    int G = 0;                   // prod card
+    int where = -1;              // the caller's: where the test ran
+    int slices = 0, copies = 0;  // as launched (copies 0: the global form)
+};
+
+constexpr int COUNT_LDS_MAX_CELLS = 4096;   // larger tables take the kernel's global-atomics form
+
+// The tables of the tests `which` (indices into `tests`; m, vars and G set, every variable categorical and named once) under the
+// BY_CARD policy, launch chunk by launch chunk: the byte mirror of the handle built on first use, a descriptor per test (its columns in
+// the test's own order, strides of card), plan_slices, joint::run_chunk.  After every chunk `finish(base, T, descs, counts)` gets the
+// tests which[base .. base + T), their descriptors and the count buffer on the host: the table of test i starts at
+// counts[descs[i].table_off].  `phase`, when set, is run_chunk's after_step.  Returns the code width in bytes (1 the mirror, 4 int32).
+// The caller holds the context's lock: the mirror and the scratch are the handle's (pbn_mi::cs).
+int count_tables(pbn_mi* h, std::vector<CountTest>& tests, const std::vector<int>& which, const std::function<void(int)>& phase,
+                 const std::function<void(size_t base, int T, const std::vector<joint::Desc>& descs, const uint32_t* counts)>& finish);
 
 }  // namespace mi
 }  // namespace pbn

@@ -283,6 +283,17 @@ class MutualInformation(IndependenceTest):
         """Batched native callback (same handle / index order as _ci_callback): independent tests share a launch."""
         return C.cast(_lib.load().pbn_mi_pvalue_batch, C.c_void_p)
 
+    def batch_stats(self):
+        """Cumulative (counted on the device, read off a cached grouping, sent to the grouping path) of the count-only tests - x, y and
+        Z all categorical - of the batched callback (csrc/mi.hip)."""
+        d, c, g = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(_lib.load().pbn_mi_discrete_batch_stats(self._handle, C.byref(d), C.byref(c), C.byref(g)))
+        return d.value, c.value, g.value
+
+    def set_batch_threshold(self, min_tests):
+        """Calls with fewer eligible count-only tests keep them on the grouping path; 0 sends every eligible test to the device."""
+        _lib.check(_lib.load().pbn_mi_discrete_set_batch_threshold(self._handle, int(min_tests)))
+
     def __del__(self):
         try:
             if _lib.alive() and getattr(self, "_handle", None):
