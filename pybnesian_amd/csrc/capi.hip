@@ -228,8 +228,12 @@ int pbn_table_read(const pbn_table* t, const int* cols, int n_sel, void* outp) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Shifted Gram of up to 64 columns -> host means (d) and centred SSE (d x d, col-major).
-static void sse_block(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t n, double* means, double* sse) {
+// Shifted Gram of up to 64 columns -> host means (d) and centred SSE (d x d, col-major), in two parts.
+// table_gram: the raw result of ONE launch - pilot shifts (of the d selected columns, in their order), shifted column sums S (d) and products
+// G (d x d, col-major, the upper triangle of the tiles mirrored).  shift_in (nullable, test aid only): one double per TABLE column on the host,
+// uploaded in place of the pilot launch.  rec (nullable): blocks asked for, grid launched, element size, NCT.
+static void table_gram(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t n, const double* shift_in, double* shift_out, double* S,
+                       double* G, int64_t* rec) {
     pbn_ctx* ctx = t->ctx;
     const int nct = (d + 15) / 16;
     const int WS = gram_ws(nct);
@@ -246,15 +250,16 @@ static void sse_block(const pbn_table* t, const int* cols, int d, int64_t row0, 
     a.base = t->data; a.ld = t->ld; a.n_cols = d; a.row0 = row0; a.rows = nullptr; a.n = n;
     for (int i = 0; i < d; ++i) a.gc.cols[i] = cols[i];
     a.rows_per_block = rpb; a.shift = shift; a.partial = partial; a.num_cus = ctx->num_cus;
-    launch_pilot(t->data, t->ld, a.gc, d, row0, nullptr, n, t->dtype, shift, ctx->stream);
-    { KernelTimer kt(ctx, PBN_K_GRAM); launch_gram(a, t->dtype, nblocks, total, ctx->stream); }
+    if (shift_in) HIP_CHECK(hipMemcpyAsync(shift, shift_in, nsh * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    else launch_pilot(t->data, t->ld, a.gc, d, row0, nullptr, n, t->dtype, shift, ctx->stream);
+    int grid = 0;
+    { KernelTimer kt(ctx, PBN_K_GRAM); grid = launch_gram(a, t->dtype, nblocks, total, ctx->stream); }
     std::vector<double> h((size_t)WS + nsh);
     HIP_CHECK(hipMemcpyAsync(h.data(), total, ((size_t)WS + nsh) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     const double* hs = h.data() + WS;            // pilot shifts, indexed by table column
-    const double* S = h.data() + (WS - nct * 16);  // shifted column sums
-    const double N = (double)n;
-    for (int i = 0; i < d; ++i) means[i] = hs[cols[i]] + (n > 0 ? S[i] / N : 0.0);
+    const double* Sx = h.data() + (WS - nct * 16);  // shifted column sums
+    for (int i = 0; i < d; ++i) { shift_out[i] = hs[cols[i]]; S[i] = Sx[i]; }
     int p = 0;
     for (int I = 0; I < nct; ++I)
         for (int J = I; J < nct; ++J, ++p) {
@@ -262,15 +267,50 @@ static void sse_block(const pbn_table* t, const int* cols, int d, int64_t row0, 
             for (int e = 0; e < 256; ++e) {
                 const int reg = e >> 6, lane = e & 63;
                 const int r = I * 16 + (lane >> 4) + 4 * reg, c = J * 16 + (lane & 15);
-                if (r >= d || c >= d) continue;
-                const double v = tile[e] - (n > 0 ? S[r] * S[c] / N : 0.0);
-                sse[r + (size_t)c * d] = v;
-                if (I != J) sse[c + (size_t)r * d] = v;
+                if (r >= d || c >= d || (I == J && r > c)) continue;   // diagonal tiles hold both triangles: the upper one, for exact symmetry
+                G[r + (size_t)c * d] = tile[e];
+                G[c + (size_t)r * d] = tile[e];
             }
         }
-    // diagonal tiles hold both triangles; symmetrise from the upper one for exact symmetry
+    if (rec) { rec[0] = nblocks; rec[1] = grid; rec[2] = (int64_t)dtype_size(t->dtype); rec[3] = nct; }
+}
+
+// the host centring of table_gram's result: means = shift + S / N, sse = G - S_r S_c / N, symmetric from the upper triangle
+static void centre_gram(int d, int64_t n, const double* shift, const double* S, const double* G, double* means, double* sse) {
+    const double N = (double)n;
+    for (int i = 0; i < d; ++i) means[i] = shift[i] + (n > 0 ? S[i] / N : 0.0);
     for (int c = 0; c < d; ++c)
-        for (int r = 0; r < c; ++r) sse[c + (size_t)r * d] = sse[r + (size_t)c * d];
+        for (int r = 0; r <= c; ++r) {
+            const double v = G[r + (size_t)c * d] - (n > 0 ? S[r] * S[c] / N : 0.0);
+            sse[r + (size_t)c * d] = v;
+            sse[c + (size_t)r * d] = v;
+        }
+}
+
+static void sse_block(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t n, double* means, double* sse) {
+    std::vector<double> raw((size_t)2 * d + (size_t)d * d);
+    double* shift = raw.data(), *S = shift + d, *G = S + d;
+    table_gram(t, cols, d, row0, n, nullptr, shift, S, G, nullptr);
+    centre_gram(d, n, shift, S, G, means, sse);
+}
+
+// pbn_debug_table_gram (test aid, not part of the C ABI header): the raw result of the ONE launch behind pbn_table_sse on up to 64 columns,
+// before the host centring - the block arithmetic, launches and decode are sse_block's own (table_gram above).  cols: d table columns
+// (1 .. 64), rows [row0, row0 + n) of the table; the argument checks are pbn_table_sse's.  shift_in non-null: one double per TABLE column,
+// uploaded in place of the pilot launch; null: the pilot runs as in production.  shift_out: d doubles, the shift each selected column was
+// centred on (what the pilot left, or shift_in's entries).  S: d shifted column sums, G: d * d shifted products, column-major, symmetric.
+// rec: four int64 - the blocks sse_block asked for, the grid launch_gram launched (capped at GD_BLOCKS_PER_CU blocks per CU), the table's
+// element size in bytes, and NCT = ceil(d / 16).
+int pbn_debug_table_gram(const pbn_table* t, int d, const int* cols, int64_t row0, int64_t n, const double* shift_in, double* shift_out, double* S,
+                         double* G, int64_t* rec) {
+    return guarded(mu_of(t), [&] {
+        check_cols(t, cols, d, "pbn_debug_table_gram");
+        check_range(t, row0, n, "pbn_debug_table_gram");
+        if (!shift_out || !S || !G || !rec) throw invalid_error("pbn_debug_table_gram: null output");
+        if (d < 1 || d > 64) throw invalid_error("pbn_debug_table_gram: between 1 and 64 columns");
+        HIP_CHECK(hipSetDevice(t->ctx->device));
+        table_gram(t, cols, d, row0, n, shift_in, shift_out, S, G, rec);
+    });
 }
 
 int pbn_table_sse(const pbn_table* t, const int* cols, int d, int64_t row0, int64_t n, double* means, double* sse) {

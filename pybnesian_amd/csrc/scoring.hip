@@ -89,11 +89,13 @@ static int64_t seg_rows() {
     }();
     return v;
 }
+// rec (nullable, read by the test aid pbn_debug_scoredata_segments only): pieces launched, launches, element size, NCT of the last launch.
 void compute_stats_segments(const pbn_scoredata* sd, const std::vector<int64_t>& r0, const std::vector<int64_t>& r1, size_t s0, size_t s1,
-                            std::vector<Stats>& out) {
+                            std::vector<Stats>& out, int64_t* rec = nullptr) {
     const int n = sd->n;
     const int64_t SEG_ROWS = seg_rows();
     for (size_t i = s0; i < s1; ++i) { out[i].zero(n); out[i].N = r1[i] - r0[i]; }
+    if (rec) { rec[0] = rec[1] = rec[3] = 0; rec[2] = (int64_t)dtype_size(sd->dtype); }
     if (s1 <= s0) return;
     const pbn_table* t = sd->table();
     pbn_ctx* ctx = t->ctx;
@@ -122,6 +124,7 @@ void compute_stats_segments(const pbn_scoredata* sd, const std::vector<int64_t>&
         for (int i = 0; i < d; ++i) a.gc.cols[i] = cols[i];
         a.rows_per_block = SEG_ROWS; a.blk = dblk.p; a.shift = sd->shift_dev.p; a.partial = partial; a.num_cus = ctx->num_cus;
         { KernelTimer kt(ctx, PBN_K_GRAM); launch_gram_segments(a, t->dtype, nblk, dblk.p + blk.size(), nseg, outd, ctx->stream); }
+        if (rec) { rec[0] = nblk; rec[1] += 1; rec[3] = nct; }
         std::vector<double> h((size_t)nseg * WS);
         HIP_CHECK(hipMemcpyAsync(h.data(), outd, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -802,6 +805,48 @@ int pbn_debug_gram_rows(const pbn_table* t, int d, const int* cols, const int32_
         HIP_CHECK(hipMemcpy(drows.p, rows, (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
         HIP_CHECK(hipMemcpy(dshift.p, shift, (size_t)t->n_cols * sizeof(double), hipMemcpyHostToDevice));
         gram_raw(t, cols, d, 0, n_rows, drows.p, dshift.p, S, G);   // synchronises
+    });
+}
+
+// pbn_debug_scoredata_segments: compute_stats_segments, the segmented form of the contiguous Gram kernels, on row ranges given by the caller.
+// n_seg > 0: segment i is rows [r0[i], r1[i]) of the handle's (permuted) table, 0 <= r0[i] <= r1[i] <= rows; ranges may be empty and may
+// overlap.  S: n_seg * n shifted column sums, G: n_seg * n * n shifted products (column-major, symmetric) over ALL n continuous columns,
+// centred on the handle's pilot shifts (pbn_debug_scoredata_shifts).  rec: 4 + n_seg int64 - the pieces launched (4 096 rows each,
+// PBN_MOMENT_SEG_ROWS), the launches (1 up to 64 columns, one per pair of 32-column blocks above), the table's element size in bytes, NCT
+// of the last launch, then the row count N the engine recorded per segment.
+// n_seg == 0: reports the handle's own segments instead - rec[0] = their number M, then per segment (region, r0, r1) in rec[1 + 3 i ..],
+// and, where S and G are non-null, the installed moments seg[i].S (M * n) and seg[i].G (M * n * n).  rec must hold 1 + 3 M entries; with
+// S == G == null only rec[0] is written, so that the caller can size the second call.
+int pbn_debug_scoredata_segments(pbn_scoredata* sd, int n_seg, const int64_t* r0, const int64_t* r1, double* S, double* G, int64_t* rec) {
+    return guarded(mu_of(sd), [&] {
+        if (!sd || !rec || n_seg < 0) throw invalid_error("pbn_debug_scoredata_segments: bad argument");
+        if (sd->discrete_only) throw invalid_error("pbn_debug_scoredata_segments: discrete-only score data has no continuous columns");
+        const size_t n = (size_t)sd->n;
+        if (n_seg == 0) {
+            const size_t M = sd->seg.size();
+            rec[0] = (int64_t)M;
+            if (!S && !G) return;
+            if (!S || !G) throw invalid_error("pbn_debug_scoredata_segments: S and G together");
+            for (size_t i = 0; i < M; ++i) {
+                rec[1 + 3 * i] = sd->seg_region[i]; rec[2 + 3 * i] = sd->seg_r0[i]; rec[3 + 3 * i] = sd->seg_r1[i];
+                std::copy(sd->seg[i].S.begin(), sd->seg[i].S.end(), S + i * n);
+                std::copy(sd->seg[i].G.begin(), sd->seg[i].G.end(), G + i * n * n);
+            }
+            return;
+        }
+        if (!r0 || !r1 || !S || !G) throw invalid_error("pbn_debug_scoredata_segments: null argument");
+        const int64_t rows = sd->table()->n_rows;
+        for (int i = 0; i < n_seg; ++i)
+            if (r0[i] < 0 || r1[i] < r0[i] || r1[i] > rows) throw invalid_error("pbn_debug_scoredata_segments: row range out of bounds");
+        HIP_CHECK(hipSetDevice(sd->ctx->device));
+        std::vector<int64_t> a(r0, r0 + n_seg), b(r1, r1 + n_seg);
+        std::vector<Stats> out((size_t)n_seg);
+        compute_stats_segments(sd, a, b, 0, (size_t)n_seg, out, rec);
+        for (int i = 0; i < n_seg; ++i) {
+            rec[4 + i] = out[i].N;
+            std::copy(out[i].S.begin(), out[i].S.end(), S + (size_t)i * n);
+            std::copy(out[i].G.begin(), out[i].G.end(), G + (size_t)i * n * n);
+        }
     });
 }
 

@@ -1191,7 +1191,7 @@ void launch_pilot(const void* base, int64_t ld, const GramCols& gc, int n_cols, 
     HIP_CHECK(hipGetLastError());
 }
 
-void launch_gram(const GramArgs& a_in, int dtype, int nblocks, double* out, hipStream_t st) {
+int launch_gram(const GramArgs& a_in, int dtype, int nblocks, double* out, hipStream_t st) {
     GramArgs a = a_in;
     // PBN_GRAM_DEBUG (1 = no MFMAs, 2 = no loads: floors of the two halves, garbage statistics) exists in measurement builds only
     // (-DPBN_GRAM_MEASURE, tools/gram_variants.sh); the production library refuses it instead of silently returning garbage
@@ -1233,6 +1233,7 @@ void launch_gram(const GramArgs& a_in, int dtype, int nblocks, double* out, hipS
         for (int b = 0; b < nblocks; ++b)
             fprintf(stderr, "S %d %lld %lld %llx\n", b, h[(size_t)b * 3] - t0, h[(size_t)b * 3 + 1] - t0, h[(size_t)b * 3 + 2]);
     }
+    return nblocks;
 }
 
 void launch_gram_segments(const GramArgs& a_in, int dtype, int nblocks, const int32_t* blk_off, int n_seg, double* out, hipStream_t st) {

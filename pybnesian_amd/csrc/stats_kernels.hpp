@@ -107,7 +107,7 @@ __device__ __forceinline__ double lg_value(double z, double cte) { return -0.5 *
 int gram_ws(int nct);  // doubles per partial: nct(nct+1)/2 tiles of 256 + nct*16 column sums
 void launch_pilot(const void* base, int64_t ld, const GramCols& gc, int n_cols, int64_t row0, const int32_t* rows,
                   int64_t n, int dtype, double* shift, hipStream_t st);
-void launch_gram(const GramArgs& a, int dtype, int nblocks, double* out, hipStream_t st);
+int launch_gram(const GramArgs& a, int dtype, int nblocks, double* out, hipStream_t st);   // returns the grid it launched (<= nblocks)
 // Segmented form: the rows (a.rows: a gather list, or null = the table's own order) are cut into segments, the blocks of the
 // table a.blk each cover a piece of one segment, and out receives one partial layout (gram_ws doubles) PER SEGMENT: segment g
 // is the sum of partial SLOTS blk_off[g] .. blk_off[g + 1] - 1 (blk_off: device, [n_seg + 1]) in a fixed association (four runs in slot
