@@ -441,6 +441,39 @@ int pbn_clg_fit(pbn_ctx* ctx, const pbn_dtable* dt, const pbn_table* t, int n_no
                 const int64_t* param_off, int64_t* rows, double* params, unsigned char* status, double* shift,
                 double* moments, int64_t* launches);
 
+/* ---- rows grouped by configuration of discrete columns, on the device ---------------------------------------------
+ * pbn_rowgroups replaces, for a factor that keeps one base factor per configuration of its discrete evidence
+ * (factors/discrete/DiscreteAdaptator.hpp:201-348 fit / logl / slogl over factors/discrete/discrete_indices.cpp:93-204),
+ * the per-configuration row selection on the host, the arrow take of the frame and the upload of each slice.
+ * PBN_ROWGROUPS_MAX_CONFIGS: the 32-bit counters one workgroup keeps in LDS, one a configuration - 32 KiB, so that
+ * five workgroups share a CU's 160 KiB (csrc/row_groups.hip). */
+typedef struct pbn_rowgroups pbn_rowgroups;
+#define PBN_ROWGROUPS_MAX_CONFIGS 8192
+/* factors/discrete/discrete_indices.cpp:93-204 as DiscreteAdaptator.hpp:201-348 uses it: the rows of dt ordered by
+ * configuration of the m key columns (first column fastest, strides = running product of the cardinalities: the
+ * adaptator's index), rows of one configuration in source order; a row with a -1 code in a key column, or whose bit in
+ * valid_bitmap (nullable; one bit a row, little-endian, pbn_table_create's convention) is 0, is in no group.  Three
+ * launches (count, scan, scatter), deterministic: two calls give the same list.  A table without rows, or one whose rows
+ * are all excluded, is legal: every group is empty.  PBN_ERR_INVALID, before anything is launched: a null argument,
+ * m < 1 or m > 7, a column out of range or named twice, more than PBN_ROWGROUPS_MAX_CONFIGS configurations. */
+int pbn_dtable_group_rows(const pbn_dtable* dt, int m, const int* cols, const unsigned char* valid_bitmap,
+                          pbn_rowgroups** out);
+/* The configurations of discrete_indices.cpp:93-204 / DiscreteAdaptator.hpp:201-348: *n_configs = their number G;
+ * offsets (G + 1 HOST entries, nullable): configuration c's rows are entries offsets[c] .. offsets[c + 1] of the list. */
+int pbn_rowgroups_offsets(const pbn_rowgroups* g, int64_t* n_configs, int64_t* offsets);
+/* The grouped list itself (discrete_indices.cpp:93-204 / DiscreteAdaptator.hpp:201-348: the slices' row indices):
+ * offsets[G] source row numbers on the HOST, grouped order. */
+int pbn_rowgroups_rows(const pbn_rowgroups* g, int32_t* rows);
+/* DiscreteAdaptator.hpp:201-348's slice of one configuration (indices of discrete_indices.cpp:93-204): the rows of
+ * configuration c, columns cols[0 .. n_cols) of t in that order, as a NEW owned table - device to device, allocated as
+ * pbn_table_take allocates (ld = max(64, n rounded up to 64)): byte for byte the table an upload of those rows and
+ * columns gives.  t has the rows of the grouped table and lives on its context.  An empty configuration gives a table of
+ * 0 rows.  The gather is enqueued on the context's stream, in order with whatever reads the table next. */
+int pbn_table_take_group(const pbn_table* t, const int* cols, int n_cols, const pbn_rowgroups* g, int64_t c,
+                         pbn_table** out);
+/* frees the list of discrete_indices.cpp:93-204 / DiscreteAdaptator.hpp:201-348's slices; tables gathered from it live on */
+void pbn_rowgroups_destroy(pbn_rowgroups* g);
+
 /* ---- one process per GPU: the delta-score cache sharded BEHIND the boundary (shards the serial double
  * loops of learning/operators/operators.cpp:100-132,296-347 and the fold loop of learning/scores/cv_likelihood.cpp:5-25; the
  * reference is one process and has no counterpart).  The host supplies ONE collective - an all-gather of doubles - as a function

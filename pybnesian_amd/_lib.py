@@ -96,6 +96,11 @@ SIGNATURES = {
     "pbn_clgnet_stats": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_clg_fit": (_int, [_vp, _vp, _vp, _int, _ip, _ip, _ip, _ip, _ip, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), _dp, C.POINTER(C.c_ubyte),
                     _dp, _dp, C.POINTER(_i64)]),
+    "pbn_dtable_group_rows": (_int, [_vp, _int, _ip, _vp, C.POINTER(_vp)]),
+    "pbn_rowgroups_offsets": (_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "pbn_rowgroups_rows": (_int, [_vp, _vp]),
+    "pbn_table_take_group": (_int, [_vp, _ip, _int, _vp, _i64, C.POINTER(_vp)]),
+    "pbn_rowgroups_destroy": (None, [_vp]),
     "pbn_scoredata_set_validity": (_int, [_vp, C.POINTER(_vp)]),
     "pbn_split_layout": (_int, [_i64, _int, _int, C.c_uint32, C.c_double, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "pbn_scoredata_layout": (_int, [_vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),

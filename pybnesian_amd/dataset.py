@@ -283,11 +283,26 @@ def shared_upload(ctx, df, columns=None):
     table = None
     if len(cols) >= 2 and len({rb.schema.field(c).type for c in cols}) == 1 and rb.num_rows > 0:
         table, _ = DeviceTable.from_dataframe(ctx, rb, cols, drop_null=False)
-    _shared.entry = (rb, ctx, table, frozenset(cols))
+    # the fifth entry: what the factors of the scope build ONCE for all of them, at the first that asks (shared_slot) - the code table of
+    # the dictionary columns (adaptator_group.py); "columns" are the names the scope was restricted to
+    slot = {"columns": wanted}
+    _shared.entry = (rb, ctx, table, frozenset(cols), slot)
     try:
         yield table
     finally:
         _shared.entry = prev
+        for name, built in slot.items():
+            if name != "columns" and hasattr(built, "close"):
+                built.close()
+
+
+def shared_slot(ctx, rb):
+    """The dictionary of the enclosing `shared_upload` scope when it was opened on this very context and record batch, else None.
+    Whatever a factor stores in it lives to the end of the scope and is closed there when it has a `close`."""
+    shared = getattr(_shared, "entry", None)
+    if shared is not None and rb is shared[0] and ctx is shared[1]:
+        return shared[4]
+    return None
 
 
 class CrossValidation:

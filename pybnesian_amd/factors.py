@@ -271,6 +271,19 @@ class CKDE(Factor):
         out[mask] = vals
         return out
 
+    def logl_table(self, table):
+        """`logl` of every row of a device-resident table that holds the factor's variables: what `logl` does after its upload."""
+        self._check_fitted("CKDE")
+        if table.dtype != self._dtype:
+            raise ValueError("Data type of training and test datasets is different.")
+        if self._split:
+            lj = self.kde_joint().logl_table(table)
+            return lj - self.kde_marg().logl_table(table) if self._evidence else lj
+        m = table.num_rows
+        vals = np.empty(m, dtype=np.float64)
+        _lib.check(_lib.load().pbn_kde_logl(self._handle, table.handle, _lib.int_array(table.index(self._variables)), 0, m, _lib.dptr(vals)))
+        return vals
+
     def cdf(self, df):
         """CKDE.cdf (factors/continuous/CKDE.hpp:126, 509-558): P(X <= x | evidence) per row, NaN at null rows."""
         rb, table, mask = self._upload_test(df)
@@ -388,13 +401,26 @@ class LinearGaussianCPD(Factor):
         rb = as_record_batch(df)
         same_type(rb, self._variables)
         table, mask = DeviceTable.from_dataframe(default_context(), rb, self._variables)
+        vals, s = self._eval_table(table, want_logl)
+        return rb, mask, vals, s
+
+    def _eval_table(self, table, want_logl):
         m = table.num_rows
         vals = np.empty(m) if want_logl else None
         s = C.c_double(0.0)
         d = len(self._variables)
         _lib.check(_lib.load().pbn_lg_logl(table.handle, _lib.int_array(table.index(self._variables)), d, 0, m, _lib.dptr(np.ascontiguousarray(self.beta)),
                                            float(self.variance), _lib.dptr(vals) if want_logl else None, C.byref(s)))
-        return rb, mask, vals, s.value
+        return vals, s.value
+
+    def logl_table(self, table):
+        """`logl` of every row of a device-resident table that holds the factor's variables: what `logl` does after its upload."""
+        self._check_fitted("LinearGaussianCPD")
+        return self._eval_table(table, True)[0]
+
+    def slogl_table(self, table):
+        self._check_fitted("LinearGaussianCPD")
+        return self._eval_table(table, False)[1]
 
     def logl(self, df):
         rb, mask, vals, _ = self._eval(df, True)
@@ -676,7 +702,9 @@ class _DiscreteAdaptator(Factor):
     def _base(self, continuous_evidence):
         raise NotImplementedError
 
-    def _fit_base(self, factor, df):
+    def _fit_base(self, factor, df, table=False):
+        """Fit the base factor of one configuration on its rows - a frame, or with `table` a device table of them - and say whether
+        it is kept."""
         raise NotImplementedError
 
     def _split(self, rb):
@@ -713,7 +741,11 @@ class _DiscreteAdaptator(Factor):
     def fit(self, df):
         import pyarrow as pa
 
+        from . import adaptator_group
+
         rb = as_record_batch(df)
+        if adaptator_group.fit(self, rb):   # one device partition of the rows (adaptator_group.py); False: the loop below
+            return
         self._disc, self._cont = self._split(rb)
         self._categories = [_dictionary_column(rb, d).dictionary.to_pylist() for d in self._disc]
         self._factors = []
@@ -754,8 +786,13 @@ class _DiscreteAdaptator(Factor):
     def logl(self, df):
         import pyarrow as pa
 
+        from . import adaptator_group
+
         self._check_fitted(self._name)
         rb = as_record_batch(df)
+        served = adaptator_group.logl(self, rb)
+        if served is not None:
+            return served
         if not self._disc:
             return self._factors[0].logl(rb)
         idx, valid = self._config(rb)
@@ -769,8 +806,13 @@ class _DiscreteAdaptator(Factor):
     def slogl(self, df):
         import pyarrow as pa
 
+        from . import adaptator_group
+
         self._check_fitted(self._name)
         rb = as_record_batch(df)
+        served = adaptator_group.slogl(self, rb)
+        if served is not None:
+            return served
         if not self._disc:
             return self._factors[0].slogl(rb)
         idx, valid = self._config(rb)
@@ -820,8 +862,8 @@ class CLinearGaussianCPD(_DiscreteAdaptator):
     def _base(self, continuous_evidence):
         return LinearGaussianCPD(self._variable, continuous_evidence)
 
-    def _fit_base(self, factor, df):
-        factor.fit(df)
+    def _fit_base(self, factor, df, table=False):
+        (factor.fit_table if table else factor.fit)(df)
         return not (factor.variance < 1.4901161193847656e-08 or np.isinf(factor.variance))
 
 
@@ -838,9 +880,9 @@ class HCKDE(_DiscreteAdaptator):
     def _base(self, continuous_evidence):
         return CKDE(self._variable, continuous_evidence)
 
-    def _fit_base(self, factor, df):
+    def _fit_base(self, factor, df, table=False):
         try:
-            factor.fit(df)
+            (factor.fit_table if table else factor.fit)(df)
             return True
         except _lib.SingularCovarianceData:
             return False
