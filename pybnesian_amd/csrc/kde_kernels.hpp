@@ -311,10 +311,19 @@ void launch_batch_boxes(const double* tile_box, int pd, int64_t ntiles, int64_t 
 // subpart (nullable): per query (in sorted order) the (offset, sum) partials of a sweep over a subsample of nsub training rows,
 // P doubles per query, the pair to use at [which]: offset + log2(sum) - log2(nsub) is a second lower bound of the query's
 // largest exponent
+// What comes off the subsample's log2 sum before it bounds anything (query_prepass_kernel), in log2 units, abs + rel |log2 sum|: the error
+// budget of the sweep that computed it.  fp64 fragments: 2^-24 - the 2^x polynomial errs by 2.3e-9 of a term (3.3e-9 units), and the rounding
+// of the Gram form, (d + 3) 2^-53 (|z_q|^2 + |z_t|^2) units, stays below the rest up to |z|^2 ~ 10^7; f16x2 fragments: the fp32 tables' own
+// tolerance per log-density, atol 5e-4 / rtol 1e-4 in natural units, rounded up to powers of two in log2 units.  Against margins of 28 to 52
+// units this moves no measurable number of tiles.
+inline void prune_subsample_slack(int fragment_dtype, double& abs_units, double& rel) {
+    if (fragment_dtype == PBN_F64) { abs_units = 0x1p-24; rel = 0.0; }
+    else { abs_units = 0x1p-10; rel = 0x1p-13; }
+}
 void launch_query_prepass(const double* zq_row, const int32_t* qperm, int64_t nq, const uint32_t* qkeys_sorted, const double* ztrain_sorted,
                           const uint32_t* tkeys_sorted, int64_t n, int zd, int pd, double* qbox, double* qthr, double* qlb, hipStream_t st,
                           const double* subpart = nullptr, int P = 2, int which = 0, double log2_nsub = 0.0, const double* tile_box = nullptr,
-                          int64_t* qtpos = nullptr);
+                          int64_t* qtpos = nullptr, int sub_dtype = PBN_F64);
 // sum-only pruned sweeps of the rotated (d = 7, 8) models, KS = 2: per query tile the exact terms over the `window` training tiles on either
 // side of qtpos[tile] (query_prepass_kernel) raise qthr (lower bound of log2 of the tile's sums) and qlb (of each query's largest exponent);
 // qrow_thr (nullable, [nqtiles * 16]) takes every query's own sum bound where it lies above its tile's final one, else the tile's

@@ -213,6 +213,7 @@ struct PruneSide {
     uint32_t* keys;      // [n] sorted
     int32_t* perm;       // [n] sorted position -> logical row
     char* rest;          // first free byte behind them (256-aligned)
+    uint32_t* keys_unsorted;   // [n] in logical order (what sort_keys read: pbn_debug_prune_stages)
 };
 static PruneSide prune_sort_side(pbn_ctx* ctx, dev_buf<char>& arena, const PackArgs& pa, int dtype, int zd, int kd, size_t extra_bytes) {
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -227,9 +228,46 @@ static PruneSide prune_sort_side(pbn_ctx* ctx, dev_buf<char>& arena, const PackA
     int32_t* iota = (int32_t*)p; p += ib;
     s.perm = (int32_t*)p; p += ib;
     s.rest = p;
+    s.keys_unsorted = keys_unsorted;
     launch_prune_keys(pa, dtype, zd, kd, s.zrow, keys_unsorted, iota, ctx->stream);
     sort_keys(ctx->scratch_sort, keys_unsorted, s.keys, iota, s.perm, pa.n, prune_key_bits(kd) * kd, ctx->stream);
     return s;
+}
+
+// pbn_debug_prune_stages (test aid, not part of the C ABI header; the codes are at its definition below): armed, every pruned fit
+// (kde_pack_train) and every pruned evaluation (kde_eval_enqueue) copies what its prepass kernels left to the host behind a stream
+// synchronisation; the last PBN_STAGES_KEEP of either kind are kept.  Unarmed it costs one atomic load per fit or evaluation.
+#define PBN_STAGES_KEEP 4
+static std::atomic<bool> g_stages_capture{false};
+static std::mutex g_stages_mu;
+struct StageFit {
+    long long head[14] = {};           // N, d, dm, zdims, pdims, kdims, nsub, ntiles, wfull, cond, fdtype, src_f32, key bits, Hilbert order at 3 / 4 key dimensions
+    double cell = 0.0;                 // prune_key_cell(kdims)
+    std::vector<double> W, mu;         // what the kernels were handed: [d][d] row-major (Wrot where rotated), [d]
+    std::vector<double> zrow, zsorted, box;
+    std::vector<uint32_t> keys_unsorted, keys;
+    std::vector<int32_t> perm;
+};
+struct StageEval {
+    long long head[21] = {};           // n, nqtiles, nsplit, tps, batches_per_split, sum_only, bboxes, qlb, window, subsample, P, which, N, d, cond, fdtype, partial rows, qg, num_cus, tile bytes, KS
+    double num[2] = {0.0, 0.0};        // prune_margin, log2(nsub)
+    std::vector<double> zrow, subpart, qbox, qthr, qlb, bbox, part;
+    std::vector<uint32_t> keys_unsorted, keys;
+    std::vector<int32_t> qperm;
+    std::vector<int64_t> qtpos;
+};
+static std::vector<StageFit> g_stage_fits;
+static std::vector<StageEval> g_stage_evals;
+template <typename T>
+static void stage_fetch(std::vector<T>& dst, const void* src, size_t count, hipStream_t st) {
+    dst.assign(count, T());
+    if (count && src) HIP_CHECK(hipMemcpyAsync(dst.data(), src, count * sizeof(T), hipMemcpyDeviceToHost, st));
+}
+template <typename R>
+static void stage_keep(std::vector<R>& all, R&& r) {
+    std::lock_guard<std::mutex> lk(g_stages_mu);
+    if (all.size() >= PBN_STAGES_KEEP) all.erase(all.begin());
+    all.push_back(std::move(r));
 }
 
 // Up to 6 marginal dimensions (PBN_PRUNE_MAX_DIMS overrides): at 1e6 x 1e5 rows (tools/prune_dims67.py, boxes over 4 dimensions)
@@ -415,6 +453,24 @@ void kde_pack_train(pbn_ctx* ctx, KdeModel& m, const pbn_table* t, const int* co
         double* box = (double*)s.rest;
         double* zsorted = (double*)(s.rest + box_b);
         launch_tile_boxes(s.zrow, s.perm, m.N, m.zdims, m.pdims, box, zsorted, ctx->stream);
+        if (g_stages_capture.load()) {   // pbn_debug_prune_stages: before scratch_prune is used again
+            StageFit f;
+            const long long head[14] = {(long long)m.N, m.d, m.dm, m.zdims, m.pdims, m.kdims, (long long)m.nsub, (long long)m.ntiles, m.wfull ? 1 : 0, m.cond ? 1 : 0,
+                                        m.fdtype(), pa.src_f32, prune_key_bits(m.kdims), PBN_TUNE(PRUNE_HILBERT_ND, 1)};
+            for (int i = 0; i < 14; ++i) f.head[i] = head[i];
+            f.cell = prune_key_cell(m.kdims);
+            f.W = m.wfull ? m.Wrot : m.W;
+            f.mu = m.mu;
+            const size_t N = (size_t)m.N;
+            stage_fetch(f.zrow, s.zrow, N * m.zdims, ctx->stream);
+            stage_fetch(f.keys_unsorted, s.keys_unsorted, N, ctx->stream);
+            stage_fetch(f.keys, s.keys, N, ctx->stream);
+            stage_fetch(f.perm, s.perm, N, ctx->stream);
+            stage_fetch(f.zsorted, zsorted, N * m.zdims, ctx->stream);
+            stage_fetch(f.box, box, (size_t)m.ntiles * 2 * m.pdims, ctx->stream);
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            stage_keep(g_stage_fits, std::move(f));
+        }
         pa.perm = s.perm;
         m.prune = true;
         m.tile_box = box; m.zsorted = zsorted; m.keys_sorted = s.keys;
@@ -581,6 +637,8 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     // 64 is even within noise, 1024 costs 3.2 ms of window for 0.435 (profiles/r8/)
     const int window = (prune && m.wfull && m.KS == 2) ? std::max(0, knob_int("PBN_SUM_WINDOW", 256)) : 0;
     const bool wdbg = window > 0 && g_window_capture.load();
+    const bool sdbg = prune && g_stages_capture.load();   // pbn_debug_prune_stages
+    StageEval sev;
     int64_t* qtpos = nullptr;
     double* qdbg = nullptr;
     double* qrow = nullptr;   // per query: its own sum bound where above its tile's (query_window_kernel), for the d = 8 screen's columns
@@ -590,7 +648,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         auto al = [](size_t x) { return (x + 255) / 256 * 256; };
         const size_t qbox_b = al((size_t)nqtiles * 2 * m.pdims * sizeof(double)), qthr_b = al((size_t)nqtiles * sizeof(double));
         const size_t qlb_b = al((size_t)nqtiles * 16 * sizeof(double));
-        const size_t qtpos_b = window ? al((size_t)nqtiles * sizeof(int64_t)) : 0, qdbg_b = wdbg ? al((size_t)nqtiles * 16 * sizeof(double)) : 0;
+        const size_t qtpos_b = (window || sdbg) ? al((size_t)nqtiles * sizeof(int64_t)) : 0, qdbg_b = wdbg ? al((size_t)nqtiles * 16 * sizeof(double)) : 0;
         const size_t qrow_b = window ? qlb_b : 0, qwpart_b = window ? al(window_part_bytes(nqtiles, wparts)) : 0;
         qs = prune_sort_side(ctx, ctx->scratch_pruneq, pa, fdt, m.zdims, m.kdims, qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b + qrow_b + qwpart_b);
         pa.perm = qs.perm;
@@ -598,7 +656,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         qbox = (double*)qs.rest; qthr = (double*)(qs.rest + qbox_b);
         static const bool use_qlb = PBN_TUNE(SWEEP_QLB, 1) != 0;   // offsets of the pruned plain sweeps from the prepass bounds
         if (use_qlb) qlb = (double*)(qs.rest + qbox_b + qthr_b);
-        if (window) qtpos = (int64_t*)(qs.rest + qbox_b + qthr_b + qlb_b);
+        if (window || sdbg) qtpos = (int64_t*)(qs.rest + qbox_b + qthr_b + qlb_b);   // (armed aid: the positions are written whatever the model)
         if (wdbg) qdbg = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b);
         if (window) qrow = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b);
         if (window) qwpart = (double*)(qs.rest + qbox_b + qthr_b + qlb_b + qtpos_b + qdbg_b + qrow_b);
@@ -625,7 +683,20 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
             subpart = ss.part;
         }
         launch_query_prepass(qs.zrow, qs.perm, n, qs.keys, m.zsorted, m.keys_sorted, m.N, m.zdims, m.pdims, (double*)qbox, (double*)qthr, (double*)qlb,
-                             ctx->stream, subpart, P, m.cond ? 2 : 0, subpart ? std::log2((double)m.nsub) : 0.0, m.cond ? nullptr : m.tile_box, qtpos);
+                             ctx->stream, subpart, P, m.cond ? 2 : 0, subpart ? std::log2((double)m.nsub) : 0.0, m.cond ? nullptr : m.tile_box, qtpos, fdt);
+        if (sdbg) {   // as query_prepass_kernel left them: the window pass overwrites qthr / qlb in place, the sweep reuses scratch_part
+            stage_fetch(sev.zrow, qs.zrow, (size_t)n * m.zdims, ctx->stream);
+            stage_fetch(sev.keys_unsorted, qs.keys_unsorted, (size_t)n, ctx->stream);
+            stage_fetch(sev.keys, qs.keys, (size_t)n, ctx->stream);
+            stage_fetch(sev.qperm, qs.perm, (size_t)n, ctx->stream);
+            stage_fetch(sev.subpart, subpart, subpart ? (size_t)nqtiles * 16 * P : 0, ctx->stream);
+            stage_fetch(sev.qbox, qbox, (size_t)nqtiles * 2 * m.pdims, ctx->stream);
+            stage_fetch(sev.qthr, qthr, (size_t)nqtiles, ctx->stream);
+            stage_fetch(sev.qlb, qlb, qlb ? (size_t)nqtiles * 16 : 0, ctx->stream);
+            stage_fetch(sev.qtpos, qtpos, (size_t)nqtiles, ctx->stream);
+            HIP_CHECK(hipStreamSynchronize(ctx->stream));
+            sev.num[1] = subpart ? std::log2((double)m.nsub) : 0.0;
+        }
         if (window) {
             { KernelTimer kt(ctx, PBN_K_PACK); launch_query_window((const double*)m.Apack, (const double*)m.nxpack, (const double*)pa.pack, (const double*)pa.npack,
                                                                m.ntiles, m.N, nqtiles, n, qtpos, window, fold, (double*)qthr, (double*)qlb, qrow, qdbg, wparts, qwpart, ctx->stream); }
@@ -777,6 +848,18 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     // f16x2 fragments: queries beyond the f16 range were clamped by the pack - their partials are recomputed in fp64 (a flag test otherwise)
     if (b3) launch_far_fix(pa, m.Apack, m.Axpack, m.KS, m.N, m.ntiles, sa.part, (int)nsplit, nqtiles, m.cond, ctx->stream);
 
+    if (sdbg) {   // what kde_finish_kernel is about to merge, and the batch boxes of the walk
+        const long long rows = sa.far_mask ? 2 * nsplit : nsplit;
+        stage_fetch(sev.part, sa.part, (size_t)rows * nqtiles * 16 * P, ctx->stream);
+        stage_fetch(sev.bbox, sa.batch_box, bboxes ? (size_t)nsplit * ceil_div(tps, 64) * 2 * m.pdims : 0, ctx->stream);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        const long long head[21] = {(long long)n, (long long)nqtiles, (long long)nsplit, (long long)tps, (long long)ceil_div(tps, 64), sum_only ? 1 : 0, bboxes ? 1 : 0,
+                                    qlb ? 1 : 0, window, m.nsub ? 1 : 0, P, m.cond ? 2 : 0, (long long)m.N, m.d, m.cond ? 1 : 0, fdt, rows,
+                                    sweep_qg(fdt, m.cond, m.KS, true), ctx->num_cus, (long long)tile_bytes, m.KS};
+        for (int i = 0; i < 21; ++i) sev.head[i] = head[i];
+        sev.num[0] = sa.prune_margin;
+        stage_keep(g_stage_evals, std::move(sev));
+    }
     const int64_t nblocks = ceil_div(n, 256);
     ctx->scratch_misc.reserve((size_t)nblocks * 2 * sizeof(double));
     FinishArgs fa{};
@@ -833,4 +916,73 @@ extern "C" int64_t pbn_debug_window_pos(int64_t* out, int64_t cap) {
     const int64_t n = (int64_t)pbn::g_window_pos.size();
     for (int64_t i = 0; out && i < n && i < cap; ++i) out[i] = pbn::g_window_pos[(size_t)i];
     return n;
+}
+
+// pbn_debug_prune_stages (test aid, not part of the C ABI header).  capture > 0 arms the aid, 0 disarms it and forgets what was kept, < 0 leaves it as it
+// is (a read).  side 0 = the pruned fits, 1 = the pruned evaluations; back = 0 the last one, 1 the one before ... (PBN_STAGES_KEEP are kept);
+// what = -1 returns how many are kept; size = f(what) with a null buffer.
+// Copies up to cap items into out (null: none) and returns how many there are, -1 for an unknown code or a record that does not exist.
+// Fits (kde_pack_train):
+//   0 header, 14 int64: N, d, dm, zdims, pdims, kdims, nsub, ntiles, wfull, cond, fragment dtype, src_f32, key bits per axis, Hilbert order at 3 / 4 key dimensions
+//   1 key cell (1 double)   2 whitening matrix handed to the kernels [d][d] row-major (Wrot where rotated)   3 mu [d]
+//   4 zrow [N][zdims], logical order   5 unsorted keys (uint32)   6 sorted keys (uint32)   7 perm (int32)   8 zsorted [N][zdims]   9 tile_box [ntiles][2 pdims]
+// Evaluations (kde_eval_enqueue):
+//   0 header, 21 int64: n, nqtiles, nsplit, tps, batches_per_split, sum_only, bboxes, qlb in use, window (tiles, 0 = no window pass), subsample in use, P (doubles per
+//     partial), which (slot of the subsample's sum), N, d, cond, fragment dtype, partial rows (nsplit, twice that with a far pass), query groups per wave of the
+//     pruned sweep (sweep_qg), the context's num_cus, bytes of a training tile's fragments and KS - what the split rule of kde_eval_enqueue starts from
+//   1 prune_margin, log2(nsub) (2 doubles)
+//   4 query zrow [n][zdims], logical order   5 unsorted keys   6 sorted keys   7 qperm (int32)   8 subpart [nqtiles 16][P] (empty without a subsample)
+//   9 qbox [nqtiles][2 pdims]   10 qthr [nqtiles]   11 qlb [nqtiles 16] (empty where unused)   12 qtpos (int64) [nqtiles] - 9 to 12 as query_prepass_kernel
+//   left them, before the window pass   13 batch boxes [nsplit batches_per_split][2 pdims] (empty without)   14 partial rows [rows][nqtiles 16][P] as
+//   kde_finish_kernel reads them
+extern "C" int64_t pbn_debug_prune_stages(int side, int back, int what, void* out, int64_t cap, int capture) {
+    if (capture >= 0) pbn::g_stages_capture.store(capture != 0);
+    std::lock_guard<std::mutex> lk(pbn::g_stages_mu);
+    if (capture == 0) { pbn::g_stage_fits.clear(); pbn::g_stage_evals.clear(); }
+    auto copy = [&](const void* src, size_t count, size_t size) -> int64_t {
+        if (out && count) std::memcpy(out, src, std::min<size_t>(count, (size_t)std::max<int64_t>(cap, 0)) * size);
+        return (int64_t)count;
+    };
+    if (side == 0) {
+        const auto& all = pbn::g_stage_fits;
+        if (what == -1) return (int64_t)all.size();
+        if (back < 0 || (size_t)back >= all.size()) return -1;
+        const pbn::StageFit& f = all[all.size() - 1 - (size_t)back];
+        switch (what) {
+            case 0: return copy(f.head, 14, 8);
+            case 1: return copy(&f.cell, 1, 8);
+            case 2: return copy(f.W.data(), f.W.size(), 8);
+            case 3: return copy(f.mu.data(), f.mu.size(), 8);
+            case 4: return copy(f.zrow.data(), f.zrow.size(), 8);
+            case 5: return copy(f.keys_unsorted.data(), f.keys_unsorted.size(), 4);
+            case 6: return copy(f.keys.data(), f.keys.size(), 4);
+            case 7: return copy(f.perm.data(), f.perm.size(), 4);
+            case 8: return copy(f.zsorted.data(), f.zsorted.size(), 8);
+            case 9: return copy(f.box.data(), f.box.size(), 8);
+            default: return -1;
+        }
+    }
+    if (side == 1) {
+        const auto& all = pbn::g_stage_evals;
+        if (what == -1) return (int64_t)all.size();
+        if (back < 0 || (size_t)back >= all.size()) return -1;
+        const pbn::StageEval& e = all[all.size() - 1 - (size_t)back];
+        switch (what) {
+            case 0: return copy(e.head, 21, 8);
+            case 1: return copy(e.num, 2, 8);
+            case 4: return copy(e.zrow.data(), e.zrow.size(), 8);
+            case 5: return copy(e.keys_unsorted.data(), e.keys_unsorted.size(), 4);
+            case 6: return copy(e.keys.data(), e.keys.size(), 4);
+            case 7: return copy(e.qperm.data(), e.qperm.size(), 4);
+            case 8: return copy(e.subpart.data(), e.subpart.size(), 8);
+            case 9: return copy(e.qbox.data(), e.qbox.size(), 8);
+            case 10: return copy(e.qthr.data(), e.qthr.size(), 8);
+            case 11: return copy(e.qlb.data(), e.qlb.size(), 8);
+            case 12: return copy(e.qtpos.data(), e.qtpos.size(), 8);
+            case 13: return copy(e.bbox.data(), e.bbox.size(), 8);
+            case 14: return copy(e.part.data(), e.part.size(), 8);
+            default: return -1;
+        }
+    }
+    return -1;
 }

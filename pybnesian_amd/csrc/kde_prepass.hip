@@ -251,8 +251,9 @@ __global__ __launch_bounds__(256) void query_prepass_kernel(const double* __rest
                                                             const uint32_t* __restrict__ qkeys, const double* __restrict__ zt,
                                                             const uint32_t* __restrict__ tkeys, int64_t n, int zd, int pd,
                                                             double* __restrict__ qbox, double* __restrict__ qthr, double* __restrict__ qlb,
-                                                            const double* __restrict__ subpart, int P, int which, double log2_nsub, int sum_bound,
-                                                            const double* __restrict__ tile_box, int tile_window, int64_t* __restrict__ qtpos) {
+                                                            const double* __restrict__ subpart, int P, int which, double log2_nsub, double sub_abs,
+                                                            double sub_rel, int sum_bound, const double* __restrict__ tile_box, int tile_window,
+                                                            int64_t* __restrict__ qtpos) {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool valid = q < nq;
     double z[PBN_MAX_D];
@@ -308,7 +309,11 @@ __global__ __launch_bounds__(256) void query_prepass_kernel(const double* __rest
         // exponent whatever the dimension: max_t s2 >= log2(sum over the subsample of 2^s2) - log2(size of the subsample).
         if (subpart) {
             const double* sp = subpart + q * P + which;
-            const double ls = sp[0] + log2(sp[1]);   // log2 of the sum over the subsample: a part of the whole sum
+            // log2 of the sum over the subsample: a part of the whole sum - AS THE SWEEP COMPUTED IT.  Where the subsample holds the one row that
+            // makes up a query's whole sum (a query far from every row), the sweep's own error put the "part" above the whole (3.2e-9 units:
+            // the 2^x polynomial; tests/test_prune_stages_gpu.py, ckde-d5), so its error budget comes off first (prune_subsample_slack)
+            const double lr = sp[0] + log2(sp[1]);
+            const double ls = lr - (sub_abs + sub_rel * __builtin_fabs(lr));
             const double lb = ls - log2_nsub;        // ... and its mean term: a lower bound of the LARGEST term
             best = lb > best ? lb : best;
             sumb = ls > sumb ? ls : sumb;
@@ -810,12 +815,14 @@ void launch_batch_boxes(const double* tile_box, int pd, int64_t ntiles, int64_t 
 }
 void launch_query_prepass(const double* zq_row, const int32_t* qperm, int64_t nq, const uint32_t* qkeys_sorted, const double* ztrain_sorted,
                           const uint32_t* tkeys_sorted, int64_t n, int zd, int pd, double* qbox, double* qthr, double* qlb, hipStream_t st,
-                          const double* subpart, int P, int which, double log2_nsub, const double* tile_box, int64_t* qtpos) {
+                          const double* subpart, int P, int which, double log2_nsub, const double* tile_box, int64_t* qtpos, int sub_dtype) {
     if (nq == 0) return;
+    double sub_abs, sub_rel;
+    prune_subsample_slack(sub_dtype, sub_abs, sub_rel);
     static const int sum_bound = PBN_TUNE(GROUP_SUM_BOUND, 1);
     static const int tile_window = std::max(0, PBN_TUNE(GROUP_TILE_WINDOW, 256));
     hipLaunchKernelGGL(query_prepass_kernel, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0, st, zq_row, qperm, nq, qkeys_sorted, ztrain_sorted,
-                       tkeys_sorted, n, zd, pd, qbox, qthr, qlb, subpart, P, which, log2_nsub, sum_bound, tile_box, tile_window, qtpos);
+                       tkeys_sorted, n, zd, pd, qbox, qthr, qlb, subpart, P, which, log2_nsub, sub_abs, sub_rel, sum_bound, tile_box, tile_window, qtpos);
     HIP_CHECK(hipGetLastError());
 }
 
