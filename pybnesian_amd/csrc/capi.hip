@@ -17,8 +17,8 @@
 namespace pbn {
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
-std::recursive_mutex& api_mutex() {
-    static std::recursive_mutex m;
+entry_mutex& api_mutex() {
+    static entry_mutex m;
     return m;
 }
 }  // namespace pbn
@@ -63,6 +63,9 @@ void pbn::ctx_release(pbn_ctx* ctx) {
     (void)hipStreamDestroy(ctx->stream);
     for (auto& ln : ctx->parked)
         if (ln.stream) { (void)hipStreamSynchronize(ln.stream); (void)hipStreamDestroy(ln.stream); (void)hipEventDestroy(ln.fence); }
+    for (auto& f : ctx->front)
+        if (f.stream) { (void)hipStreamSynchronize(f.stream); (void)hipStreamDestroy(f.stream); (void)hipEventDestroy(f.ready); (void)hipEventDestroy(f.released); }
+    if (ctx->front_fence) (void)hipEventDestroy(ctx->front_fence);
     delete ctx;
 }
 
@@ -507,17 +510,17 @@ static void kde_eval_enqueue(pbn_kde* k, const pbn_table* test, const int* cols,
         // last workgroups of a pruned sweep drain for 2-3 ms) runs under it; the difference waits for both on the device
         const bool lanes = pbn::score_lanes() > 1 && !ctx->profiling;
         if (lanes) { ctx->ensure_lanes(1); ctx->lanes_wait_for_stream(1); }
-        pbn::kde_eval_enqueue(ctx, k->split_joint->m, test, cols, row0, n, lj, sj, nullptr, nullptr, precise);
+        pbn::kde_eval_enqueue(ctx, k->split_joint->m, test, cols, row0, n, lj, sj, nullptr, nullptr, precise, /*front_lanes=*/true);
         {
             pbn::LaneSwitch lane(ctx, lanes ? 1 : 0);
-            pbn::kde_eval_enqueue(ctx, k->split_marg->m, test, cols + 1, row0, n, lm, sm, nullptr, nullptr, precise);
+            pbn::kde_eval_enqueue(ctx, k->split_marg->m, test, cols + 1, row0, n, lm, sm, nullptr, nullptr, precise, /*front_lanes=*/true);
         }
         if (lanes) ctx->stream_waits_for_lane(0);
         if (dev_logl) launch_diff(dev_logl, lj, lm, n, ctx->stream);
         if (dev_sum) launch_diff(dev_sum, sj, sm, 1, ctx->stream);
         return;
     }
-    pbn::kde_eval_enqueue(k->ctx, k->m, test, cols, row0, n, dev_logl, dev_sum, nullptr, nullptr, precise);
+    pbn::kde_eval_enqueue(k->ctx, k->m, test, cols, row0, n, dev_logl, dev_sum, nullptr, nullptr, precise, /*front_lanes=*/true);
 }
 
 int pbn_kde_logl_dev(pbn_kde* k, const pbn_table* test, const int* cols, int64_t row0, int64_t n, double* dev_out) {

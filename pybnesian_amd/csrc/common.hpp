@@ -48,7 +48,13 @@ void set_last_error(const std::string& s);
 // of whatever context they touch - so a search no longer blocks the rest of the process for its whole duration (round 2: one
 // process-wide mutex).  Host-only entry points (bandwidths, split layouts, samplers) and creation / destruction of contexts use the
 // process-wide mutex.  All mutexes are recursive: entry points call each other, and Python callbacks re-enter on the same thread.
-std::recursive_mutex& api_mutex();
+// (entry_mutex: a recursive mutex that also counts the entry points taken under it - guarded() below; every context's lock and the
+// process-wide one are of this type)
+struct entry_mutex : std::recursive_mutex {
+    uint64_t entries = 0;   // entry points that have run under this lock so far (guarded), the running ones included
+    int depth = 0;          // ... and how many of them are on the stack now: 1 = a top-level call
+};
+entry_mutex& api_mutex();
 #define PBN_API_LOCK std::lock_guard<std::recursive_mutex> pbn_api_lock_(::pbn::api_mutex())
 
 inline void hip_check(hipError_t e, const char* what, const char* file, int line) {
@@ -83,6 +89,21 @@ int guarded(std::recursive_mutex& mu, F&& f) noexcept {
         set_last_error(e.what());
         return PBN_ERR_INVALID;
     }
+}
+// ... on a context's lock (mu_of) or the process-wide one: the entry is counted while it holds the lock.  The front lanes of the handle
+// evaluations (pbn_ctx::front, kde_eval_enqueue) tell from the count whether any other entry point ran on the context since the last
+// evaluation left.  The destroy entry points lock without guarded() and are not counted: they free what their handle owns, behind a
+// synchronisation of the context's stream, and enqueue nothing that a later evaluation reads.
+template <typename F>
+int guarded(entry_mutex& mu, F&& f) noexcept {
+    return guarded(static_cast<std::recursive_mutex&>(mu), [&] {
+        struct Scope {
+            entry_mutex& m;
+            explicit Scope(entry_mutex& m_) : m(m_) { ++m.entries; ++m.depth; }
+            ~Scope() { --m.depth; }
+        } scope(mu);
+        f();
+    });
 }
 template <typename F>
 int guarded(F&& f) noexcept {   // host-only entry points: the process-wide mutex
@@ -131,7 +152,7 @@ inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // ---- handle definitions (opaque in the C header) ---------------------------------------------
 
 struct pbn_ctx {
-    std::recursive_mutex mu;   // every entry point working on this context holds it (pbn::mu_of)
+    pbn::entry_mutex mu;       // every entry point working on this context holds it (pbn::mu_of)
     std::atomic<int> refs{1};  // the creator's reference + one per live handle (pbn::ctx_ptr): see pbn_ctx_destroy
     int device = 0;
     hipStream_t stream = nullptr;
@@ -196,6 +217,42 @@ struct pbn_ctx {
         for (int k = 0; k < n_parked && k < MAX_PARKED; ++k)
             if (parked[k].stream) HIP_CHECK(hipStreamSynchronize(parked[k].stream));
     }
+    // Front lanes (handle evaluations, kde_eval_enqueue): the query side of a pruned evaluation - keys, sort, pack, subsample sweep, prepass,
+    // window pass - reads only the test table and the fitted model, so evaluation k enqueues it on front lane k mod 2, with that lane's
+    // arenas, where it runs beside the sweep of evaluation k - 1; everything behind it stays on `stream` in call order.  Not the
+    // parked lanes: a score batch may be using those.
+    //   ready      recorded on the lane behind the query side; `stream` waits for it before the rest of the evaluation
+    //   released   recorded on `stream` behind that rest, which reads the lane's q / pruneq: the lane waits for it before evaluation k + 2
+    //              writes them again
+    // Every evaluation joins its lane into `stream` before it returns, so nothing enqueued later on `stream` can overtake a lane.
+    struct Front {
+        hipStream_t stream = nullptr;
+        pbn::dev_buf<char> q, pruneq, sort, part;
+        hipEvent_t ready = nullptr, released = nullptr;
+        bool was_released = false;
+    };
+    Front front[2];
+    hipEvent_t front_fence = nullptr;   // recorded on `stream` where a lane has to see everything enqueued so far
+    int front_next = 0;                 // the lane of the next evaluation
+    int front_last = -1;                // the lane of the last one (its `ready` is recorded), -1 = none yet
+    // mu.entries as the last front-lane evaluation left it, valid where that evaluation was a top-level entry point's and did not throw:
+    // the next one may skip waiting for `stream` where no other entry point ran in between (kde_eval_enqueue)
+    uint64_t front_exit = 0;
+    bool front_exit_valid = false;
+    void ensure_front() {
+        for (Front& f : front)
+            if (!f.stream) {
+                HIP_CHECK(hipStreamCreateWithFlags(&f.stream, hipStreamNonBlocking));
+                HIP_CHECK(hipEventCreateWithFlags(&f.ready, hipEventDisableTiming));
+                HIP_CHECK(hipEventCreateWithFlags(&f.released, hipEventDisableTiming));
+            }
+        if (!front_fence) HIP_CHECK(hipEventCreateWithFlags(&front_fence, hipEventDisableTiming));
+    }
+    void swap_front(int k) {
+        Front& f = front[k];
+        std::swap(stream, f.stream);
+        std::swap(scratch_q, f.q); std::swap(scratch_pruneq, f.pruneq); std::swap(scratch_sort, f.sort); std::swap(scratch_part, f.part);
+    }
     // optional per-kernel timing (pbn_ctx_set_profiling): HIP events recorded on `stream` around launches
     bool profiling = false;
     bool timing = false;   // events recorded (KernelTimer), behaviour unchanged: pbn_ctx_set_profiling(ctx, 2)
@@ -242,9 +299,9 @@ struct ctx_pin {
 namespace pbn {
 // the lock an entry point takes: the context's own, through any handle that carries a `ctx` member; a null handle falls back to
 // the process-wide mutex (the call then fails on its own null check)
-inline std::recursive_mutex& mu_of(const pbn_ctx* c) { return c ? const_cast<pbn_ctx*>(c)->mu : api_mutex(); }
+inline entry_mutex& mu_of(const pbn_ctx* c) { return c ? const_cast<pbn_ctx*>(c)->mu : api_mutex(); }
 template <typename H>
-inline std::recursive_mutex& mu_of(const H* h) { return h ? mu_of(static_cast<const pbn_ctx*>(h->ctx)) : api_mutex(); }
+inline entry_mutex& mu_of(const H* h) { return h ? mu_of(static_cast<const pbn_ctx*>(h->ctx)) : api_mutex(); }
 }  // namespace pbn
 
 // ---- run-time switches ---------------------------------------------------------------------------------------------------------------

@@ -559,8 +559,70 @@ static std::mutex g_window_mu;
 static std::vector<double> g_window_lb;
 static std::vector<int64_t> g_window_pos;   // pbn_debug_window_pos: per query the centre of its tile's window, a position in the sorted training order
 
+// The front stage of a pruned handle evaluation (pbn_ctx::front): while it is open, ctx->stream and the arenas of the query side are front lane
+// k's, so the routines in between keep saying ctx->stream / ctx->scratch_*.
+//   open     lane k waits for `released` of its last use, and for what it has to see of ctx->stream: where the evaluation follows another front-lane
+//            evaluation with no entry point of the context in between (pbn_ctx::front_exit), that is the other evaluation's query side alone - it saw
+//            everything enqueued before it, and nothing it reads was enqueued since -, so the lane waits for that lane's `ready` and runs beside the
+//            sweep still on ctx->stream; in every other case (another entry point in between on any handle, a nested entry point, a throw) it waits
+//            for everything enqueued on ctx->stream so far
+//   join     `ready` on the lane, the lane's resources back, ctx->stream waits for `ready`
+//   release  `released` on ctx->stream behind the rest of the evaluation; the count of entry points is noted for the next evaluation
+// A throw in between leaves the join recorded (the destructor) and the next evaluation waits in full.
+static std::atomic<unsigned long long> g_front_evals{0}, g_front_chained{0};   // pbn_debug_front_lanes
+struct FrontStage {
+    pbn_ctx* ctx; int k = -1; bool open = false;
+    FrontStage(pbn_ctx* c, bool on) : ctx(c) {
+        if (!on) return;
+        ctx->ensure_front();
+        k = ctx->front_next;
+        ctx->front_next ^= 1;
+        pbn_ctx::Front& f = ctx->front[k];
+        if (f.was_released) HIP_CHECK(hipStreamWaitEvent(f.stream, f.released, 0));
+        const entry_mutex& mu = ctx->mu;
+        const bool chained = ctx->front_exit_valid && ctx->front_last >= 0 && mu.depth == 1 && (mu.entries == ctx->front_exit || mu.entries == ctx->front_exit + 1);
+        ctx->front_exit_valid = false;
+        if (chained) {
+            if (ctx->front_last != k) HIP_CHECK(hipStreamWaitEvent(f.stream, ctx->front[ctx->front_last].ready, 0));
+        } else {
+            HIP_CHECK(hipEventRecord(ctx->front_fence, ctx->stream));
+            HIP_CHECK(hipStreamWaitEvent(f.stream, ctx->front_fence, 0));
+        }
+        ctx->swap_front(k);
+        open = true;
+        g_front_evals.fetch_add(1);
+        if (chained) g_front_chained.fetch_add(1);
+    }
+    void join() {
+        if (!open) return;
+        open = false;
+        ctx->swap_front(k);
+        pbn_ctx::Front& f = ctx->front[k];
+        HIP_CHECK(hipEventRecord(f.ready, f.stream));
+        HIP_CHECK(hipStreamWaitEvent(ctx->stream, f.ready, 0));
+        ctx->front_last = k;
+    }
+    void release() {
+        if (k < 0) return;
+        pbn_ctx::Front& f = ctx->front[k];
+        HIP_CHECK(hipEventRecord(f.released, ctx->stream));
+        f.was_released = true;
+        ctx->front_exit = ctx->mu.entries;
+        ctx->front_exit_valid = ctx->mu.depth == 1;
+    }
+    ~FrontStage() {
+        if (!open) return;
+        ctx->swap_front(k);
+        pbn_ctx::Front& f = ctx->front[k];
+        if (hipEventRecord(f.ready, f.stream) == hipSuccess) { (void)hipStreamWaitEvent(ctx->stream, f.ready, 0); ctx->front_last = k; }
+        else (void)hipStreamSynchronize(f.stream);
+    }
+    FrontStage(const FrontStage&) = delete;
+    FrontStage& operator=(const FrontStage&) = delete;
+};
+
 void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, const int* cols, int64_t row0, int64_t n,
-                      double* dev_logl, double* dev_sum, const int32_t* dev_rows, double* dev_sum_marg, bool precise) {
+                      double* dev_logl, double* dev_sum, const int32_t* dev_rows, double* dev_sum_marg, bool precise, bool front_lanes) {
     check_cols(test, cols, m.d, "pbn_kde_logl");
     const bool sum_only = dev_logl == nullptr && !precise;   // only sums leave this call, at the sum-only error budget
     if (!dev_rows) check_range(test, row0, n, "pbn_kde_logl");
@@ -609,6 +671,13 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     }
     const size_t es = dtype_size(fdt);
     const int64_t nqtiles = ceil_div(n, 16);
+    // a rotated (d = 7, 8) model prunes its sum-only sweeps only; per-row logl outputs take the plain sweep over the same (sorted) pack
+    const bool prune = m.prune && (sum_only || !m.wfull);
+    // the capture aids synchronise and read scratch: read once, and no front lane while one is armed
+    const bool cap_stages = g_stages_capture.load(), cap_window = g_window_capture.load(), cap_masks = g_masks_capture.load();
+    // The query side on a front lane (FrontStage above; the handle entry points of capi.hip ask for it, the score engine has lanes of its own): pruned
+    // evaluations only.  PBN_KDE_PIPELINE=0 (read per evaluation): everything on ctx->stream, as before the lanes.
+    FrontStage front(ctx, front_lanes && prune && m.d <= PBN_W_INLINE_D && !cap_stages && !cap_window && !cap_masks && knob_int("PBN_KDE_PIPELINE", 1) != 0);
     // query fragments in scratch: Bpack | nypack | Bxpack
     const bool b3 = use_f16x2(fdt);
     const size_t bpack_b = b3 ? (size_t)nqtiles * m.KS * 64 * 16 : (size_t)nqtiles * m.KS * 64 * es,
@@ -630,14 +699,12 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     const double* qlb = nullptr;
     const int32_t* qperm = nullptr;
     PruneSide qs{};
-    // a rotated (d = 7, 8) model prunes its sum-only sweeps only; per-row logl outputs take the plain sweep over the same (sorted) pack
-    const bool prune = m.prune && (sum_only || !m.wfull);
-    // ... and those sweeps tighten the prepass bounds with the exact terms of a window of training tiles (query_window_kernel): W tiles on either
+    // pruned sum-only sweeps of a rotated model tighten the prepass bounds with the exact terms of a window of training tiles (query_window_kernel): W tiles on either
     // side, PBN_SUM_WINDOW (0 = the prepass bounds alone).  W = 256: C2 visits 0.525 -> 0.441 of its blocks, 27.3 -> 24.3 ms;
     // 64 is even within noise, 1024 costs 3.2 ms of window for 0.435 (profiles/r8/)
     const int window = (prune && m.wfull && m.KS == 2) ? std::max(0, knob_int("PBN_SUM_WINDOW", 256)) : 0;
-    const bool wdbg = window > 0 && g_window_capture.load();
-    const bool sdbg = prune && g_stages_capture.load();   // pbn_debug_prune_stages
+    const bool wdbg = window > 0 && cap_window;
+    const bool sdbg = prune && cap_stages;   // pbn_debug_prune_stages
     StageEval sev;
     int64_t* qtpos = nullptr;
     double* qdbg = nullptr;
@@ -716,6 +783,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
             }
         }
     }
+    front.join();   // from here on ctx->stream in call order: batch boxes, screen, sweep, far pass, finish
 
     // split the training tiles so that the grid is a few waves deep on every CU
     const int64_t qblocks = ceil_div(nqtiles, 4 * sweep_qg(fdt, m.cond, m.KS, prune));
@@ -746,7 +814,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     // PBN_D8_SCREEN_MAX_MB (default 512) the step runs unscreened.
     // (Both knobs are read through getenv at every evaluation, like PBN_SUM_WINDOW and PBN_MAGIC_GUARD beside them: two lookups per step, so that a test or a
     // deployment can turn them between two calls of one process.)
-    const bool mdbg = g_masks_capture.load();
+    const bool mdbg = cap_masks;
     bool screen = prune && sum_only && m.scr != nullptr && bboxes && wmul && m.KS == 2 && m.pdims == PBN_PRUNE_PD && m.zdims == 8 && knob_int("PBN_D8_SCREEN", 1) != 0;
     const size_t scrq_b = screen ? (size_t)nqtiles * 16 * 32 : 0;
     size_t mask_b = screen ? (size_t)ceil_div(nqtiles, PBN_QG_PRUNE) * nsplit * ceil_div(tps, 64) * PBN_QG_PRUNE * sizeof(unsigned long long) : 0;
@@ -868,6 +936,7 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     fa.logl = dev_logl; fa.scatter = qperm; fa.block_sums = dev_sum ? (double*)ctx->scratch_misc.p : nullptr;
     fa.block_sums_marg = (m.cond && dev_sum && dev_sum_marg) ? (double*)ctx->scratch_misc.p + nblocks : nullptr;
     { KernelTimer kt(ctx, PBN_K_FINISH); launch_finish(fa, m.cond, dev_sum, ctx->stream, dev_sum_marg); }
+    front.release();
 }
 
 }  // namespace pbn
@@ -897,6 +966,14 @@ extern "C" int64_t pbn_debug_d8_masks(int what, void* out, int64_t cap, int capt
         case 8: return copy(d.part.data(), d.part.size(), 8);   // the partial rows both sweeps left for kde_finish_kernel
         default: return -1;
     }
+}
+
+// pbn_debug_front_lanes (test aid, not part of the C ABI header): evaluations whose query side went to a front lane since the last reset, and
+// how many of them skipped the wait for the context's stream (FrontStage)
+extern "C" void pbn_debug_front_lanes(unsigned long long* evals, unsigned long long* chained, int reset) {
+    if (evals) *evals = pbn::g_front_evals.load();
+    if (chained) *chained = pbn::g_front_chained.load();
+    if (reset) { pbn::g_front_evals.store(0); pbn::g_front_chained.store(0); }
 }
 
 extern "C" int64_t pbn_debug_sum_window(double* out, int64_t cap, int capture) {

@@ -105,8 +105,11 @@ void kde_prune_persist(pbn_ctx* ctx, KdeModel& m, dev_buf<char>& store);
 // precise: a sum is wanted (dev_logl == nullptr) but at the accuracy of the per-row path - the polynomial 2^f, the pruning margin of the
 // per-row sweeps, no fp32 tail.  The callers' second evaluation of a sum that came out too close to zero for the sum-only path's
 // absolute error budget (kde_sum_needs_precision).
+// front_lanes: a pruned evaluation enqueues its query side on one of the context's two front lanes (pbn_ctx::front), beside the previous
+// evaluation's sweep; the results land on the context's stream where and when they did before.  The handle entry points only.
 void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, const int* cols, int64_t row0, int64_t n,
-                      double* dev_logl, double* dev_sum, const int32_t* dev_rows = nullptr, double* dev_sum_marg = nullptr, bool precise = false);
+                      double* dev_logl, double* dev_sum, const int32_t* dev_rows = nullptr, double* dev_sum_marg = nullptr, bool precise = false,
+                      bool front_lanes = false);
 // The sum-only fp64 sweeps carry an ABSOLUTE error per log-density of at most 1.4e-7 (2^f on the fp32 unit) + 1.1e-7 (dropped mass) +
 // 8e-8 (fp32 far tail) = 3.3e-7; measured with every rounding made one-sided (tests/test_error_budget_gpu.py): 3e-8.  Relative to a sum
 // of n log-densities that is harmless unless the sum is a cancellation to ~0 (a table whose density happens to sit near 1 in its units):
