@@ -79,7 +79,9 @@ __device__ __forceinline__ hpiece h_piece(float x) {   // f16(x), never subnorma
     const hpiece h = (hpiece)x;
     return __builtin_fabsf((float)h) < 0x1p-14f ? (hpiece)0.0f : h;
 }
-// z -> (a1, a2 2^6) and the represented value a1 + a2
+// z -> (a1, a2 2^6) and the represented value a1 + a2: |z - (a1 + a2)| <= max(2^-22 |z|, 2^-20) for |z| <= 65504 (a low piece under 2^-20 is
+// flushed by h_piece: wherever |z - a1| < 2^-20 the error is that absolute residual - for values beside an f16 up to |z| ~ 4)
+// (the compiler contracts (hpiece)(float)z into ONE double -> half rounding: tests/f16_restatement.py split2; the bound holds for either order)
 __device__ __forceinline__ double split2(double z, hpiece& hi, hpiece& lo, bool& clamped) {
     clamped = !(__builtin_fabs(z) <= (double)PBN_H_MAX);
     z = z > (double)PBN_H_MAX ? (double)PBN_H_MAX : (z < -(double)PBN_H_MAX ? -(double)PBN_H_MAX : z);
@@ -89,7 +91,8 @@ __device__ __forceinline__ double split2(double z, hpiece& hi, hpiece& lo, bool&
     lo = h_piece((float)(r * (double)PBN_H_LO));
     return (double)(float)hi + (double)(float)lo * (1.0 / (double)PBN_H_LO);
 }
-// x = 2^15 p1 + 2^5 p2 + 2^-6 p3 (|x| clamped to 65504 x 2^15 = 2.1e9: the padding norm -1e30 becomes that, far below every real exponent)
+// x = 2^15 p1 + 2^5 p2 + 2^-6 p3 (|x| clamped to 65504 x 2^15 = 2.1e9: the padding norm -1e30 becomes that, far below every real exponent);
+// residual <= max(2^-33 |x|, 2^-20): a third piece under 2^-20 is flushed like every other
 __device__ __forceinline__ void split3s(float x, hpiece& p1, hpiece& p2, hpiece& p3) {
     constexpr float XMAX = PBN_H_MAX * PBN_H_C1;
     x = x > XMAX ? XMAX : (x < -XMAX ? -XMAX : x);

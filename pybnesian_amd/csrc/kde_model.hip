@@ -270,6 +270,25 @@ static void stage_keep(std::vector<R>& all, R&& r) {
     all.push_back(std::move(r));
 }
 
+// pbn_debug_f16_stages (test aid, not part of the C ABI header; the codes are at its definition below): armed, every evaluation of
+// kde_eval_enqueue whose fragments are f16x2 (use_f16x2(fdt)), pruned or not, copies its fragments and its partial sums - before and after
+// kde_far_fix_kernel - to the host behind a stream synchronisation; the last PBN_F16_STAGES_KEEP are kept.  Unarmed it costs one atomic load
+// per evaluation; no kernel and no launch argument depends on it.
+#define PBN_F16_STAGES_KEEP 4
+static std::atomic<bool> g_f16_capture{false};
+static std::mutex g_f16_mu;
+struct F16Stage {
+    long long head[19] = {};           // see pbn_debug_f16_stages
+    double num[3] = {0.0, 0.0, 0.0};   // SweepArgs::prune_margin, the model's lognorm and lognorm_marg (FinishArgs)
+    std::vector<double> W, mu;         // what the pack kernels were handed: [d][d] row-major, [d]
+    std::vector<int32_t> cols, qperm;  // the table's columns in the order of W's; sorted position -> query row (pruned evaluations)
+    std::vector<uint16_t> apack, axpack, bpack, bxpack;   // f16 bit patterns
+    std::vector<float> npack, xnorm;
+    std::vector<unsigned char> far;
+    std::vector<double> part_sweep, part_fixed;
+};
+static std::vector<F16Stage> g_f16_stages;
+
 // Up to 6 marginal dimensions (PBN_PRUNE_MAX_DIMS overrides): at 1e6 x 1e5 rows (tools/prune_dims67.py, boxes over 4 dimensions)
 // d = 6 gains 10 % in fp64 and 9-13 % in fp32 on correlated and on independent normal data and is even on heavy-tailed data;
 // d = 7 is even at best (heavy-tailed: +3...5 %), d = 8 loses 10 %.
@@ -675,9 +694,10 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     const bool prune = m.prune && (sum_only || !m.wfull);
     // the capture aids synchronise and read scratch: read once, and no front lane while one is armed
     const bool cap_stages = g_stages_capture.load(), cap_window = g_window_capture.load(), cap_masks = g_masks_capture.load();
+    const bool cap_f16 = g_f16_capture.load();
     // The query side on a front lane (FrontStage above; the handle entry points of capi.hip ask for it, the score engine has lanes of its own): pruned
     // evaluations only.  PBN_KDE_PIPELINE=0 (read per evaluation): everything on ctx->stream, as before the lanes.
-    FrontStage front(ctx, front_lanes && prune && m.d <= PBN_W_INLINE_D && !cap_stages && !cap_window && !cap_masks && knob_int("PBN_KDE_PIPELINE", 1) != 0);
+    FrontStage front(ctx, front_lanes && prune && m.d <= PBN_W_INLINE_D && !cap_stages && !cap_window && !cap_masks && !cap_f16 && knob_int("PBN_KDE_PIPELINE", 1) != 0);
     // query fragments in scratch: Bpack | nypack | Bxpack
     const bool b3 = use_f16x2(fdt);
     const size_t bpack_b = b3 ? (size_t)nqtiles * m.KS * 64 * 16 : (size_t)nqtiles * m.KS * 64 * es,
@@ -733,6 +753,22 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
     pa.far_flag = ff_b ? (unsigned char*)(q + ((bpack_b + ny_b + bx_b + xn_b + 255) / 256) * 256) : nullptr;
     { KernelTimer kt(ctx, PBN_K_PACK); launch_pack(pa, fdt, ctx->stream); }
     const int P = m.cond ? 4 : 2;
+    const bool fdbg = b3 && cap_f16;   // pbn_debug_f16_stages
+    F16Stage fev;
+    if (fdbg) {   // the fragments as the pack kernels left them (the copies are awaited behind the sweep)
+        const size_t nq16 = (size_t)nqtiles * 16;
+        fev.W = m.wfull ? m.Wrot : m.W;
+        fev.mu = m.mu;
+        fev.cols.assign(pa.cols, pa.cols + m.d);
+        stage_fetch(fev.apack, m.Apack, (size_t)m.ntiles * m.KS * 64 * 8, ctx->stream);
+        stage_fetch(fev.axpack, m.Axpack, m.cond ? (size_t)m.ntiles * 64 * 8 : 0, ctx->stream);
+        stage_fetch(fev.bpack, pa.pack, (size_t)nqtiles * m.KS * 64 * 8, ctx->stream);
+        stage_fetch(fev.npack, pa.npack, nq16, ctx->stream);
+        stage_fetch(fev.bxpack, pa.xpack, m.cond ? (size_t)nqtiles * 64 * 8 : 0, ctx->stream);
+        stage_fetch(fev.xnorm, pa.xnorm, pa.xnorm ? nq16 : 0, ctx->stream);
+        stage_fetch(fev.far, pa.far_flag, pa.far_flag ? nq16 : 0, ctx->stream);
+        stage_fetch(fev.qperm, qperm, qperm ? (size_t)n : 0, ctx->stream);
+    }
     const bool wmul = !fold && sweep_weights_norm(fdt, m.cond, m.KS, m.dm);
     if (prune) {
         // bounds of the queries' largest exponents: neighbours in Morton order, and (more dimensions than keys) one sweep over
@@ -913,8 +949,26 @@ void kde_eval_enqueue(pbn_ctx* ctx, const KdeModel& m, const pbn_table* test, co
         const long long dims[6] = {(long long)ceil_div(nqtiles, PBN_QG_PRUNE), (long long)nsplit, (long long)ceil_div(tps, 64), (long long)tps, (long long)m.ntiles, (long long)n};
         for (int i = 0; i < 6; ++i) g_masks.dims[i] = dims[i];
     }
+    if (fdbg) {   // the partials as the sweep left them
+        stage_fetch(fev.part_sweep, sa.part, (size_t)nsplit * nqtiles * 16 * P, ctx->stream);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
     // f16x2 fragments: queries beyond the f16 range were clamped by the pack - their partials are recomputed in fp64 (a flag test otherwise)
     if (b3) launch_far_fix(pa, m.Apack, m.Axpack, m.KS, m.N, m.ntiles, sa.part, (int)nsplit, nqtiles, m.cond, ctx->stream);
+    if (fdbg) {   // ... and as kde_finish_kernel is about to merge them
+        stage_fetch(fev.part_fixed, sa.part, (size_t)nsplit * nqtiles * 16 * P, ctx->stream);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        // the kernel launch_sweep_f16 chose: 0 = 16x16, 1 = W32 (unpruned), 2 = 16x16 pruned, 3 = W32P
+        const int kernel = prune ? ((!m.cond && sa.w32 && m.KS == 1) ? 3 : 2) : ((!m.cond && sa.w32 && (m.KS == 1 || m.KS == 2)) ? 1 : 0);
+        const long long head[19] = {(long long)n, (long long)m.N, m.d, m.dm, m.cond ? 1 : 0, m.KS, f16x2_spd(m.dm), (long long)m.ntiles, (long long)nqtiles,
+                                    (long long)nsplit, (long long)tps, P, sa.w32, prune ? 1 : 0, sum_only ? 1 : 0, sweep_qg(fdt, m.cond, m.KS, prune), kernel,
+                                    ctx->num_cus, (prune && m.nsub) ? 1 : 0};
+        for (int i = 0; i < 19; ++i) fev.head[i] = head[i];
+        fev.num[0] = sa.prune_margin; fev.num[1] = m.lognorm; fev.num[2] = m.lognorm_marg;
+        std::lock_guard<std::mutex> lk(g_f16_mu);
+        if (g_f16_stages.size() >= PBN_F16_STAGES_KEEP) g_f16_stages.erase(g_f16_stages.begin());
+        g_f16_stages.push_back(std::move(fev));
+    }
 
     if (sdbg) {   // what kde_finish_kernel is about to merge, and the batch boxes of the walk
         const long long rows = sa.far_mask ? 2 * nsplit : nsplit;
@@ -1062,4 +1116,49 @@ extern "C" int64_t pbn_debug_prune_stages(int side, int back, int what, void* ou
         }
     }
     return -1;
+}
+
+// pbn_debug_f16_stages (test aid, not part of the C ABI header).  capture > 0 arms the aid, 0 disarms it and forgets what was kept, < 0 leaves it as it
+// is (a read).  back = 0 the last captured evaluation, 1 the one before ... (PBN_F16_STAGES_KEEP are kept); what = -1 returns how many are kept;
+// the size of an item comes back with a null buffer.  Copies up to cap items into out (null: none) and returns how many there are, -1 for an
+// unknown code or a record that does not exist.
+//   0 header, 19 int64: n, N, d, dm, cond, NB (KS: 32-slot blocks of the main contraction), slots per dimension (f16x2_spd), ntiles, nqtiles, nsplit, tps
+//     (tiles per split), P (doubles per partial), SweepArgs::w32, prune, sum_only, sweep_qg, kernel (0 = kde_sweep_f16_kernel unpruned, 1 =
+//     kde_sweep_f16_w32_kernel, 2 = kde_sweep_f16_kernel pruned, 3 = kde_sweep_f16_w32p_kernel), the context's num_cus, 1 where a subsample
+//     sweep ran in front (pruned, more dimensions than boxes)
+//   1 prune_margin, lognorm, lognorm_marg as kde_finish_kernel gets them (3 doubles)   2 W [d][d] row-major as the pack kernels were handed it   3 mu [d]   4 the table's columns in W's order (int32)
+//   5 training fragments [ntiles][NB][64][8] (f16 as uint16)   6 the CKDE block of the training side [ntiles][64][8] (empty unless cond)
+//   7 query fragments [nqtiles][NB][64][8] as pack_rows_f16_kernel left them   8 npack [nqtiles 16] (float)   9 query CKDE block [nqtiles][64][8]
+//   10 xnorm [nqtiles 16] (float; empty unless cond)   11 far flags [nqtiles 16] (bytes)   12 qperm (int32; empty unless pruned)
+//   13 partials [nsplit][nqtiles 16][P] behind the sweep   14 the same behind kde_far_fix_kernel, as kde_finish_kernel reads them
+extern "C" int64_t pbn_debug_f16_stages(int back, int what, void* out, int64_t cap, int capture) {
+    if (capture >= 0) pbn::g_f16_capture.store(capture != 0);
+    std::lock_guard<std::mutex> lk(pbn::g_f16_mu);
+    if (capture == 0) pbn::g_f16_stages.clear();
+    auto copy = [&](const void* src, size_t count, size_t size) -> int64_t {
+        if (out && count) std::memcpy(out, src, std::min<size_t>(count, (size_t)std::max<int64_t>(cap, 0)) * size);
+        return (int64_t)count;
+    };
+    const auto& all = pbn::g_f16_stages;
+    if (what == -1) return (int64_t)all.size();
+    if (back < 0 || (size_t)back >= all.size()) return -1;
+    const pbn::F16Stage& e = all[all.size() - 1 - (size_t)back];
+    switch (what) {
+        case 0: return copy(e.head, 19, 8);
+        case 1: return copy(e.num, 3, 8);
+        case 2: return copy(e.W.data(), e.W.size(), 8);
+        case 3: return copy(e.mu.data(), e.mu.size(), 8);
+        case 4: return copy(e.cols.data(), e.cols.size(), 4);
+        case 5: return copy(e.apack.data(), e.apack.size(), 2);
+        case 6: return copy(e.axpack.data(), e.axpack.size(), 2);
+        case 7: return copy(e.bpack.data(), e.bpack.size(), 2);
+        case 8: return copy(e.npack.data(), e.npack.size(), 4);
+        case 9: return copy(e.bxpack.data(), e.bxpack.size(), 2);
+        case 10: return copy(e.xnorm.data(), e.xnorm.size(), 4);
+        case 11: return copy(e.far.data(), e.far.size(), 1);
+        case 12: return copy(e.qperm.data(), e.qperm.size(), 4);
+        case 13: return copy(e.part_sweep.data(), e.part_sweep.size(), 8);
+        case 14: return copy(e.part_fixed.data(), e.part_fixed.size(), 8);
+        default: return -1;
+    }
 }

@@ -7,7 +7,9 @@
 // cycles).  Round 6 measured the f16x2 sweep POWER-bound (profiles/r6/f32_power_bound.txt: 19 % fewer cycles bought a 19 % lower
 // clock; 2.0 PFLOP/s of dense bf16 MFMA work): what a pair value costs in wall time is its matrix work, so the contraction is halved -
 // every whitened coordinate is split into TWO f16 pieces z^ = a1 + a2 (a1 = f16(z), a2 = f16(z - a1): 22 mantissa bits, |z - z^| <=
-// 2^-22 |z|), the three products with weight >= 2^-11 (a1 b1, a1 b2, a2 b1) are exact in the f32 accumulator, the fourth (a2 b2,
+// max(2^-22 |z|, 2^-20) - the floor is h_piece's flush rule: a low piece below 2^-20 is stored as zero, so the error is absolute wherever
+// |z - a1| < 2^-20, which values next to an f16 value meet up to |z| ~ 4), the three products with weight >= 2^-11 (a1 b1, a1 b2, a2 b1)
+// are exact in the f32 accumulator, the fourth (a2 b2,
 // <= 2^-22 |a||b|) is dropped, and the norms are taken from the REPRESENTED z^: what the sweep evaluates is -1/2 |z^_t - z^_q|^2 up to
 // the dropped products - an input perturbation of 2^-22 relative (fp32 inputs carry 2^-24 themselves) plus <= 2^-22 sum |a2 b2|, where
 // bf16x3 paid 2^-24 |z|^2 of cancellation error with its norms from the unsplit z.  K = 3 d + 3 slots instead of 6 d + 3: ONE 32-slot
@@ -15,9 +17,13 @@
 // f16 has 5 exponent bits: pieces are kept out of its subnormal range and inside its finite range by power-of-two slot scales -
 //   coordinate k, slots 3k ... 3k+2:   training (a1, a1 2^-6, a2 2^6)   x   query (b1, b2 2^6, b1 2^-6);
 //   a scalar that rides in slots (the training norm -1/2|z^_t|^2, the CKDE / W32 query offsets) is cut by split3s into three pieces
-//   x = 2^15 p1 + 2^5 p2 + 2^-6 p3 against the constants (2^15, 2^5, 2^-6) on the other side: |x| <= 2^31, residual <= 2^-33 |x|;
-//   a piece that would be subnormal is stored as zero (its value stays in the residual the next piece takes), so the result does not
-//   depend on whether the matrix cores flush f16 subnormals.
+//   x = 2^15 p1 + 2^5 p2 + 2^-6 p3 against the constants (2^15, 2^5, 2^-6) on the other side: |x| <= 2^31, residual <= max(2^-33 |x|, 2^-20);
+//   a piece that would be subnormal is stored as zero (its value stays in the residual the next piece takes - the LAST piece's stays
+//   unrepresented: the absolute floors 2^-20 above), so the result does not depend on whether the matrix cores flush f16 subnormals.
+//   The scaled roles a1 2^-6 and a2 go through the same rule: a1 2^-6 is zero for |a1| < 2^-8 and a2 for |a2| < 2^-14, and the products
+//   they carry (|a1 b2| < 2^-19 |b|, |a2 b2| < 2^-25 max(|a|, |b|)) are then missing from the sweeps' exponents - below 2^-22 |z|^2 from
+//   |z| = 8 on and below 2^-16 per coordinate under it.  (tests/f16_restatement.py proves the bounds, tests/test_f16_restatement_cpu.py
+//   and tests/test_f16_stages_gpu.py assert them.)
 // Query coordinates beyond +-65504 (54 000 bandwidths from the centre of the training set) are clamped and counted (PackArgs::far_count).
 // Slot s of a row: s = 3 k + r (dimension k, role r) for s < 3 dm, then the three norm pieces; slot s lives in MFMA s / 32, lane group
 // (s % 32) / 8, element s % 8.   Fragment arrays: [tile][NB][64 lanes][8 f16].  The query side -1/2|z^_q|^2 - m_q is the MFMA's C operand
