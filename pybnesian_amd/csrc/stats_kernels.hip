@@ -8,10 +8,13 @@
 // mle_LinearGaussianCPD.hpp:11-193, via the normal equations), BGe's cached SSE (learning/scores/
 // bge.hpp:52-72).
 //
-// Layout: the table is column-major (Arrow columns).  For a 16-row chunk a lane (c = lane&15,
-// kq = lane>>4) reads rows 4kq..4kq+3 of column 16*I + c; k-step j of the chunk multiplies, for every
-// column-tile pair I <= J, A[i][k] = x[row 4k+j][col 16I+i] with B[k][jj] = x[row 4k+j][col 16J+jj].
-// Row order inside the contraction is irrelevant, so no transpose through LDS is needed.
+// Layout: the table is column-major (Arrow columns), up to 64 columns per launch in NCT = ceil(n_cols / 16) groups of 16.  A
+// block's four waves each take their own rows of the block's chunks; operand lane (c = lane&15, kq = lane>>4) holds rows of
+// column 16*I + c, and a k-step multiplies, for every column-tile pair I <= J, A[i][k] = x[row r(k)][col 16I+i] with
+// B[k][jj] = x[row r(k)][col 16J+jj] (v_mfma_f64_16x16x4_f64, 4 rows per step).  Which rows share a k-step is irrelevant to the
+// contraction as long as every column group agrees, so each kernel takes the assignment that its loads deliver: no transpose.
+// Contiguous rows stream through per-wave LDS rings filled by the LDS-DMA (gram_glds_kernel for double tables,
+// gram_glds_f32_kernel for float ones), row lists through a ring of registers (gram_gring_kernel); pick_gram() is the table.
 // Numerics: values are shifted by a per-column pilot mean (mean of the first <=1024 rows; the shift array
 // is indexed by TABLE column so that Grams of different row ranges / column subsets are additive) before the
 // products, so  SSE = G_shift - S S^T / N  has no catastrophic cancellation (S = shifted column sums).
@@ -54,159 +57,14 @@ struct NPairs {
 };
 
 // partial layout per block: [NP][256] tile accumulators (lane-major: element lane*4 + reg), then [NCT*16] sums
-// 16 bytes of a column with only element alignment guaranteed (global_load_dwordx4 asks for no more): vector types with
-// their alignment lowered, so that the load stays one instruction
-typedef double d2_elem_aligned __attribute__((ext_vector_type(2), aligned(8)));
-typedef float f4_elem_aligned __attribute__((ext_vector_type(4), aligned(4)));
-template <typename T>
-__device__ __forceinline__ void load_rows4(const T* p, T (&out)[4]);
-template <>
-__device__ __forceinline__ void load_rows4<double>(const double* p, double (&out)[4]) {
-    const d2_elem_aligned lo = *(const d2_elem_aligned*)p, hi = *(const d2_elem_aligned*)(p + 2);
-    out[0] = lo[0]; out[1] = lo[1]; out[2] = hi[0]; out[3] = hi[1];
-}
-template <>
-__device__ __forceinline__ void load_rows4<float>(const float* p, float (&out)[4]) {
-    const f4_elem_aligned v = *(const f4_elem_aligned*)p;
-    out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; out[3] = v[3];
-}
-template <typename T, int NCT, bool GATHER>
-__global__ __launch_bounds__(256, 2) void gram_kernel(GramArgs a) {
-    constexpr int NP = NPairs<NCT>::value;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int c = lane & 15, kq = lane >> 4;
 
-    const int64_t rb0 = (int64_t)blockIdx.x * a.rows_per_block;
-    int64_t rb1 = rb0 + a.rows_per_block;
-    if (rb1 > a.n) rb1 = a.n;
-
-    const T* colp[NCT];
-    double sh[NCT];
-    bool cvalid[NCT];
-#pragma unroll
-    for (int I = 0; I < NCT; ++I) {
-        const int ci = I * 16 + c;
-        cvalid[I] = ci < a.n_cols;
-        const int src = cvalid[I] ? a.gc.cols[ci] : a.gc.cols[0];
-        colp[I] = (const T*)a.base + (int64_t)src * a.ld + (GATHER ? 0 : a.row0);
-        sh[I] = cvalid[I] ? a.shift[src] : 0.0;
-    }
-
-    d4 acc[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) acc[p] = d4{0, 0, 0, 0};
-    double csum[NCT];
-#pragma unroll
-    for (int I = 0; I < NCT; ++I) csum[I] = 0.0;
-
-    // software-pipelined over 16-row chunks: the loads of chunk i+1 are in flight under the MFMAs of chunk i
-    auto load_chunk = [&](int64_t r, T (&raw)[NCT][4], bool (&ok)[4]) {
-        const int64_t rl = r + 4 * kq;
-        int64_t src[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            ok[j] = rl + j < rb1;
-            src[j] = ok[j] ? (GATHER ? (int64_t)a.rows[rl + j] : rl + j) : (GATHER ? (int64_t)a.rows[rb0] : rb0);
-        }
-        if (!GATHER && ok[3]) {
-            // the lane's four rows are consecutive in memory: one 16- / two 16-byte loads per column instead of four
-            // 4- / 8-byte ones (element alignment is all the hardware asks for), half the sectors the L1 has to serve
-#pragma unroll
-            for (int I = 0; I < NCT; ++I) load_rows4<T>(colp[I] + rl, raw[I]);
-            return;
-        }
-#pragma unroll
-        for (int I = 0; I < NCT; ++I)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) raw[I][j] = colp[I][src[j]];
-    };
-    T raw[NCT][4];
-    bool ok[4];
-    int64_t r = rb0 + wave * 16;
-    if (r < rb1) load_chunk(r, raw, ok);
-    for (; r < rb1; r += 64) {
-        double x[NCT][4];
-#pragma unroll
-        for (int I = 0; I < NCT; ++I)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) x[I][j] = (ok[j] && cvalid[I]) ? (double)raw[I][j] - sh[I] : 0.0;
-        if (r + 64 < rb1) load_chunk(r + 64, raw, ok);
-#pragma unroll
-        for (int I = 0; I < NCT; ++I) csum[I] += (x[I][0] + x[I][1]) + (x[I][2] + x[I][3]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            int p = 0;
-#pragma unroll
-            for (int I = 0; I < NCT; ++I)
-#pragma unroll
-                for (int J = I; J < NCT; ++J) {
-                    acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[I][j], x[J][j], acc[p], 0, 0, 0);
-                    ++p;
-                }
-        }
-    }
-
-    // ---- block combine (fixed wave order) -------------------------------------------------------
-    // one LDS image, waves add into it in wave order 0,1,2,3 (deterministic)
-    __shared__ double lds[NP * 256 + NCT * 16];
-    constexpr int WS = NP * 256 + NCT * 16;
-    double cs[NCT];
-#pragma unroll
-    for (int I = 0; I < NCT; ++I) {
-        double s = csum[I];
-        s += __shfl_xor(s, 16);
-        s += __shfl_xor(s, 32);
-        cs[I] = s;
-    }
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int e = p * 256 + i * 64 + lane;
-                    lds[e] = (w == 0) ? acc[p][i] : lds[e] + acc[p][i];
-                }
-            }
-            if (kq == 0) {
-#pragma unroll
-                for (int I = 0; I < NCT; ++I) {
-                    const int e = NP * 256 + I * 16 + c;
-                    lds[e] = (w == 0) ? cs[I] : lds[e] + cs[I];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    double* out = a.partial + (int64_t)blockIdx.x * WS;
-    for (int e = threadIdx.x; e < WS; e += 256) out[e] = lds[e];
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// gram_lds_kernel: the same statistics with the rows staged through LDS and the K-STEPS split over the waves.
-// gram_kernel above gives every wave its own rows: all NCT(NCT+1)/2 accumulator tiles AND four k-steps of operands and
-// their prefetch live in registers (NCT = 4: 196 VGPRs, 2 waves / SIMD, each alternating between its load phase and its
-// MFMA phase: 0.52 of the HBM peak at 64 columns).  Here a 256-thread block loads a chunk of 32 rows x all columns ONCE,
-// coalesced (4 threads per column, 64 contiguous bytes each), subtracts the pilot shift and writes doubles to LDS; wave w
-// then multiplies k-steps 2w and 2w + 1 of the chunk (rows 8w .. 8w + 7) into ALL tile pairs: per k-step NCT operand
-// fragments from LDS feed NCT(NCT+1)/2 MFMAs, every wave has the same work (20 MFMAs per chunk at NCT = 4), and the
-// registers hold the accumulators (80) plus one k-step of operands - ~120 VGPRs, 4 waves / SIMD, 4 blocks per CU.  The
-// global loads of chunk i + 1 are in flight (registers) under the MFMAs of chunk i (double-buffered LDS, one barrier per
-// chunk); the four waves' accumulators are added through LDS in wave order at the end (deterministic).
-// Two earlier splits were measured and dropped: tile PAIRS over the waves (10 pairs = 3 + 3 + 2 + 2: the barrier per chunk
-// waits for the 3-pair waves, and every wave reads two fragments per MFMA from LDS - 216 us for the MFMA side alone against
-// 130 us of MFMA work; with the compiler's ds_read2_b64 fusion the LDS reads alone took as long as the MFMAs), and a
-// prefetch distance of two chunks (158 VGPRs, a block per CU lost: 320 us).
-// LDS image: [k-step s (8)][column group I][half h = k >> 1][column c (16)][k & 1] - the 32 lanes of a half wave
-// (lane = 16 k + c, k in {0, 1} or {2, 3}) read 32 CONSECUTIVE doubles of k-step s, group I: one conflict-free
-// ds_read_b64 (2 LDS cycles, 256 B/clk; MI355X_MICROARCH.md "LDS").  The k-steps are 2064 B apart on purpose: at <= 2040 B
-// or at a multiple of 512 B the compiler fuses reads of neighbouring k-steps into ds_read2[st64]_b64, which run at half the
-// rate (8 cycles per KiB, 32-bank mapping).
-// ------------------------------------------------------------------------------------------------------------------
+// History the ring kernels below refer to: their predecessor, since removed, staged a block-wide image of 32 rows through
+// registers into a double-buffered LDS (shift, convert, ds_write_b128; one barrier per chunk, four blocks per CU) and split the
+// chunk's k-steps over the waves.  "The LDS-image kernel" below is that one; profiles/r2 keeps its records.
+//
 // Wave priority for kernels that run ONE long-lived block per resident slot with the same work in each: a SIMD issues by
 // priority, then AGE, so at equal priority the oldest wave's MFMAs go nearly unimpeded and the youngest gets the leftovers -
-// measured with in-kernel time stamps on gram_lds_kernel (2M x 64, loads off): the four blocks of a CU finished after 88,
+// measured with in-kernel time stamps on the LDS-image kernel (2M x 64, loads off): the four blocks of a CU finished after 88,
 // 121, 155 and 178 us, the last stretch with one or two waves per SIMD, which cannot keep the matrix pipe busy.  A wave's
 // priority therefore rotates with its OWN chunk count offset by its slot: whoever holds the highest runs ahead one chunk and
 // drops to 0; no block leads by more than a few chunks and the blocks of a CU finish together (172-200 us after the change).
@@ -223,138 +81,11 @@ __device__ __forceinline__ void rotate_priority(int k) {
         default: __builtin_amdgcn_s_setprio(3); break;
     }
 }
-constexpr int GL_ROWS = 32;                         // rows per chunk
-constexpr int GL_KSTRIDE = 258;                     // doubles between k-steps in the LDS image: 4 groups x 64, + 16 B
-
-template <typename T, int NCT, bool GATHER>
-__global__ __launch_bounds__(256, 4) void gram_lds_kernel(GramArgs a) {
-    constexpr int NP = NPairs<NCT>::value;
-    constexpr int NC = NCT * 16;
-    constexpr int WS = NP * 256 + NCT * 16;
-    constexpr int IMG = (GL_ROWS / 4) * GL_KSTRIDE;
-    static_assert(2 * IMG >= WS, "the final combine reuses the LDS images");
-    __shared__ double lds[2 * IMG];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: scalar
-    const int c = lane & 15, kq = lane >> 4;
-
-    int64_t rb0 = (int64_t)blockIdx.x * a.rows_per_block;
-    int64_t rb1 = rb0 + a.rows_per_block;
-    if (rb1 > a.n) rb1 = a.n;
-    if (a.blk) {   // a piece of one segment (launch_gram_segments)
-        rb0 = a.blk[4 * blockIdx.x + 1]; rb1 = a.blk[4 * blockIdx.x + 2];
-        if (rb1 <= rb0) return;   // a padding entry of an aligned launch order: no piece, no partial
-    }
-
-    // loader role: thread t -> column t >> 2 (of the first NC columns), rows (t & 3) * 8 .. + 7 of the chunk
-    const int lcol = tid >> 2, lrg = tid & 3;
-    const bool lvalid = lcol < a.n_cols;
-    const bool lactive = lcol < NC;
-    const int lsrc = lvalid ? a.gc.cols[lcol] : a.gc.cols[0];
-    const T* lp = (const T*)a.base + (int64_t)lsrc * a.ld + (GATHER ? 0 : a.row0);
-    const double lsh = lvalid ? a.shift[lsrc] : 0.0;
-    double csum = 0.0;
-
-    d4 acc[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) acc[p] = d4{0, 0, 0, 0};
-    // this lane's operand element of k-step 2 * wave, column group 0 (doubles into an image)
-    const int off0 = (2 * wave) * GL_KSTRIDE + (kq >> 1) * 32 + c * 2 + (kq & 1);
-
-    T raw[8] = {};
-    auto load_chunk = [&](int64_t r) {   // rows r + lrg * 8 .. + 7 of this thread's column into registers
-        if (!lactive || a.debug_skip >= 2) return;
-        const int64_t rl = r + lrg * 8;
-        if (!GATHER && rl + 8 <= rb1) {   // straight into the prefetch registers: a copy would make the compiler wait for the loads here
-            load_rows4<T>(lp + rl, reinterpret_cast<T(&)[4]>(raw[0]));
-            load_rows4<T>(lp + rl + 4, reinterpret_cast<T(&)[4]>(raw[4]));
-            return;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const bool ok = rl + j < rb1;
-            const int64_t src = ok ? (GATHER ? (int64_t)a.rows[rl + j] : rl + j) : (GATHER ? (int64_t)a.rows[rb0] : rb0);
-            raw[j] = lp[src];
-        }
-    };
-    auto store_chunk = [&](int64_t r, int buf) {   // shift, widen, column sums, LDS image
-        if (!lactive || a.debug_skip == 3) return;
-        const int64_t rl = r + lrg * 8;
-        double x[8];
-        double s = 0.0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            x[j] = (lvalid && rl + j < rb1) ? (double)raw[j] - lsh : 0.0;
-            s += x[j];
-        }
-        csum += s;
-        // rows lrg * 8 + j: k-steps 2 lrg (j < 4) and 2 lrg + 1, k = j & 3; (k = 0, 1) and (k = 2, 3) are 16-byte pairs
-        double* dst = &lds[buf * IMG + (2 * lrg) * GL_KSTRIDE + (lcol >> 4) * 64 + (lcol & 15) * 2];
-        typedef double d2v __attribute__((ext_vector_type(2)));
-        *(d2v*)(dst) = d2v{x[0], x[1]};
-        *(d2v*)(dst + 32) = d2v{x[2], x[3]};
-        *(d2v*)(dst + GL_KSTRIDE) = d2v{x[4], x[5]};
-        *(d2v*)(dst + GL_KSTRIDE + 32) = d2v{x[6], x[7]};
-    };
-
-    int64_t r = rb0;
-    int buf = 0;
-    if (r < rb1) { load_chunk(r); store_chunk(r, 0); }
-    __syncthreads();
-    int turn = wave_slot();
-    for (; r < rb1; r += GL_ROWS) {
-        rotate_priority(turn++);
-        const bool more = r + GL_ROWS < rb1;
-        if (more) load_chunk(r + GL_ROWS);             // in flight under the MFMAs below
-        const double* img = lds + buf * IMG + off0;
-        if (a.debug_skip != 1) {
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                double x[NCT];
-#pragma unroll
-                for (int I = 0; I < NCT; ++I) x[I] = img[s2 * GL_KSTRIDE + I * 64];
-                int p = 0;
-#pragma unroll
-                for (int I = 0; I < NCT; ++I)
-#pragma unroll
-                    for (int J = I; J < NCT; ++J) {
-                        acc[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(x[I], x[J], acc[p], 0, 0, 0);
-                        ++p;
-                    }
-            }
-        }
-        if (more) store_chunk(r + GL_ROWS, buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-
-    __builtin_amdgcn_s_setprio(0);
-    // ---- block combine: one LDS image, the waves add into it in wave order 0, 1, 2, 3 (deterministic) -----------------
-    for (int w = 0; w < 4; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int e = p * 256 + i * 64 + lane;
-                    lds[e] = (w == 0) ? acc[p][i] : lds[e] + acc[p][i];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    double* out = a.partial + (int64_t)(a.blk ? a.blk[4 * blockIdx.x + 3] : blockIdx.x) * WS;
-    for (int e = threadIdx.x; e < NP * 256; e += 256) out[e] = lds[e];
-    // column sums: the 4 loader threads of a column are adjacent lanes
-    double s = csum;
-    s += __shfl_xor(s, 1);
-    s += __shfl_xor(s, 2);
-    if (lactive && lrg == 0) out[NP * 256 + lcol] = s;
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // gram_glds_kernel (double tables, contiguous rows): every WAVE streams its own rows through its own ring of LDS stages
 // filled by the LDS-DMA (global_load_lds_dwordx4) - no barrier in the loop, no register spent on the prefetch.
-// What the measurements on gram_lds_kernel said (2M x 64 fp64, profiles/r2/gram_floors.txt): (1) the shift / convert /
+// What the measurements on the LDS-image kernel had said (2M x 64 fp64, profiles/r2/gram_floors.txt): (1) the shift / convert /
 // ds_write_b128 phase costs a quarter of the MFMA side (206 -> 158 us without it; 16-byte LDS stores move their data at
 // ~79 B/clk per CU, MI355X_MICROARCH.md "LDS"); (2) with one chunk in flight per block the loads alone take 185-215 us - the
 // memory side is latency-bound, not bandwidth-bound; (3) the blocks of a CU finish one after the other (rotate_priority
@@ -366,14 +97,14 @@ __global__ __launch_bounds__(256, 4) void gram_lds_kernel(GramArgs a) {
 // 2h + e contracting rows 16w + 8h + 2kq + e - the contraction does not care which rows share a k-step as long as every
 // column group agrees.  LDS is a register file extension: a ring of two stages per wave, filled two chunks ahead (a stage
 // is refilled as soon as its chunk sits in registers, one chunk before it is multiplied), 16 KiB in flight per wave,
-// 128 KiB per CU at two blocks - against 64 KiB with gram_lds_kernel's block-wide double buffer.  Own counted vmcnt is all
+// 128 KiB per CU at two blocks - against the 64 KiB of the LDS-image kernel's block-wide double buffer.  Own counted vmcnt is all
 // the ordering a wave needs for its own DMA (MI355X_MICROARCH.md, "Two waves per SIMD", item 7).  The pilot shift is
 // subtracted and the column sums are taken where the operands are read (4 NCT + 4 NCT DP instructions beside
 // 2 NCT (NCT + 1) MFMAs per chunk); the steady state is one branch-free block with that work and the DMA instructions
 // pinned between groups of NCT + 1 MFMAs.
 // Chunk j of block b is chunk j gridDim.x + b of the range, so at any moment the resident blocks read one contiguous
 // window of every column; only the range's very last chunk can be cut short, and its rows come through registers.
-// Measured (tools/gram_bench.py, 2M x 64): 190-200 us per launch against 224-237 for gram_lds_kernel on the same boxes; MFMAs
+// Measured (tools/gram_bench.py, 2M x 64): 190-200 us per launch against 224-237 for the LDS-image kernel on the same boxes; MFMAs
 // alone (PBN_GRAM_DEBUG=2) 165-172, DMA alone (=1) 172-185 = 5.5-5.9 TB/s.
 // ------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
@@ -848,8 +579,8 @@ __global__ __launch_bounds__(256, GD_BLOCKS_PER_CU) void gram_glds_f32_kernel(Gr
 // a load instruction touch 16 columns x 4 rows: with a dense, increasing list the 4 rows and the chunk's other 3 loads of the
 // column group share a 128-byte line, with a sparse one every element is its own 64-byte sector and the pass is bound by the
 // sectors it drags in.
-// gram_lds_kernel<T, NCT, true> - a block-wide 32-row LDS image, one chunk of 8 single-element loads per thread in flight, the
-// row index read again by each of the 64 column threads - took 637 us for a 4-category grouping of the 2M x 64 table.
+// The LDS-image kernel's row-list form - a block-wide 32-row LDS image, one chunk of 8 single-element loads per thread in flight,
+// the row index read again by each of the 64 column threads - had taken 637 us for a 4-category grouping of the 2M x 64 table.
 // ------------------------------------------------------------------------------------------------------------------
 template <int N> struct IdxVec;
 template <> struct IdxVec<4> { typedef int type __attribute__((ext_vector_type(4), aligned(4))); };
@@ -1063,78 +794,6 @@ __global__ __launch_bounds__(256) void gram_seg_reduce_kernel(const double* __re
     if (q == 0 && e < WS) out[(size_t)g * WS + e] = ((run[0][threadIdx.x] + run[1][threadIdx.x]) + run[2][threadIdx.x]) + run[3][threadIdx.x];
 }
 
-// PBN_GRAM_LDS: 0 = gram_kernel (rows in registers), 1 = gram_lds_kernel, 2 (default) = the LDS-DMA ring kernels where they apply
-// (contiguous rows: gram_glds_kernel for double tables, gram_glds_f32_kernel for float ones) and gram_lds_kernel elsewhere.
-static int gram_variant() {
-    static const int v = PBN_TUNE(GRAM_LDS, 2);
-    return v;
-}
-
-// launches the partial-sum kernel; returns the number of blocks (= partials) it used (<= nblocks)
-template <typename T, bool GATHER>
-static int launch_gram_t(const GramArgs& a, int nct, int nblocks, hipStream_t st) {
-    dim3 grid(nblocks), block(256);
-    if constexpr (!GATHER) {
-        if (gram_variant() >= 2) {
-            if (a.num_cus > 0 && nblocks > GD_BLOCKS_PER_CU * a.num_cus) grid.x = GD_BLOCKS_PER_CU * a.num_cus;   // one block per slot
-            const int dbg = a.debug_skip == 1 ? 1 : a.debug_skip >= 2 ? 2 : 0;
-#ifdef PBN_GRAM_MEASURE   // measurement builds only (tools/gram_variants.sh): the floor variants produce garbage statistics
-#define PBN_GLDS_K(K, N)                                                                                \
-        if (dbg == 0) hipLaunchKernelGGL((K<N, 0>), grid, block, 0, st, a);                            \
-        else if (dbg == 1) hipLaunchKernelGGL((K<N, 1>), grid, block, 0, st, a);                       \
-        else hipLaunchKernelGGL((K<N, 2>), grid, block, 0, st, a);
-#else
-#define PBN_GLDS_K(K, N) (void)dbg; hipLaunchKernelGGL((K<N, 0>), grid, block, 0, st, a);
-#endif
-#define PBN_GLDS(N)                                                                                     \
-    case N:                                                                                             \
-        if constexpr (sizeof(T) == 8) { PBN_GLDS_K(gram_glds_kernel, N) } else { PBN_GLDS_K(gram_glds_f32_kernel, N) }   \
-        break;
-            switch (nct) {
-                PBN_GLDS(1) PBN_GLDS(2) PBN_GLDS(3) PBN_GLDS(4)
-                default: throw invalid_error("gram: at most 64 columns per launch");
-            }
-#undef PBN_GLDS
-#undef PBN_GLDS_K
-            HIP_CHECK(hipGetLastError());
-            return (int)grid.x;
-        }
-    }
-    if constexpr (GATHER) {
-        if (gram_variant() >= 2) {
-            switch (nct) {
-                case 1: hipLaunchKernelGGL((gram_gring_kernel<T, 1, false>), grid, block, 0, st, a); break;
-                case 2: hipLaunchKernelGGL((gram_gring_kernel<T, 2, false>), grid, block, 0, st, a); break;
-                case 3: hipLaunchKernelGGL((gram_gring_kernel<T, 3, false>), grid, block, 0, st, a); break;
-                case 4: hipLaunchKernelGGL((gram_gring_kernel<T, 4, false>), grid, block, 0, st, a); break;
-                default: throw invalid_error("gram: at most 64 columns per launch");
-            }
-            HIP_CHECK(hipGetLastError());
-            return nblocks;
-        }
-    }
-    if (gram_variant() >= 1) {
-        switch (nct) {
-            case 1: hipLaunchKernelGGL((gram_lds_kernel<T, 1, GATHER>), grid, block, 0, st, a); break;
-            case 2: hipLaunchKernelGGL((gram_lds_kernel<T, 2, GATHER>), grid, block, 0, st, a); break;
-            case 3: hipLaunchKernelGGL((gram_lds_kernel<T, 3, GATHER>), grid, block, 0, st, a); break;
-            case 4: hipLaunchKernelGGL((gram_lds_kernel<T, 4, GATHER>), grid, block, 0, st, a); break;
-            default: throw invalid_error("gram: at most 64 columns per launch");
-        }
-        HIP_CHECK(hipGetLastError());
-        return nblocks;
-    }
-    switch (nct) {
-        case 1: hipLaunchKernelGGL((gram_kernel<T, 1, GATHER>), grid, block, 0, st, a); break;
-        case 2: hipLaunchKernelGGL((gram_kernel<T, 2, GATHER>), grid, block, 0, st, a); break;
-        case 3: hipLaunchKernelGGL((gram_kernel<T, 3, GATHER>), grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL((gram_kernel<T, 4, GATHER>), grid, block, 0, st, a); break;
-        default: throw invalid_error("gram: at most 64 columns per launch");
-    }
-    HIP_CHECK(hipGetLastError());
-    return nblocks;
-}
-
 // 64 rows per block through an LDS tile: column reads and row writes both run along their contiguous direction; a thread's 4 NCT
 // column reads are issued together
 template <typename T, int NCT>
@@ -1191,6 +850,42 @@ void launch_pilot(const void* base, int64_t ld, const GramCols& gc, int n_cols, 
     HIP_CHECK(hipGetLastError());
 }
 
+// The one place a partial-sum kernel is chosen, for the plain and the segmented launcher alike: contiguous rows (a.rows == null)
+// stream through the LDS-DMA rings, row lists through the register ring, which reads the row-major mirror where the launch has one.
+typedef void (*GramKernel)(GramArgs);
+enum GramForm {
+    GRAM_CONTIGUOUS,
+    GRAM_LIST,
+    GRAM_LIST_MIRROR,
+#ifdef PBN_GRAM_MEASURE   // measurement builds only (tools/gram_variants.sh): the floor variants produce garbage statistics
+    GRAM_CONTIGUOUS_NO_MFMA,   // PBN_GRAM_DEBUG=1
+    GRAM_CONTIGUOUS_NO_DMA,    // PBN_GRAM_DEBUG=2
+#endif
+};
+template <int NCT>
+static GramKernel pick_gram_nct(bool f64, GramForm form) {
+    switch (form) {
+        case GRAM_CONTIGUOUS: return f64 ? gram_glds_kernel<NCT, 0> : gram_glds_f32_kernel<NCT, 0>;
+        case GRAM_LIST: return f64 ? gram_gring_kernel<double, NCT, false> : gram_gring_kernel<float, NCT, false>;
+        case GRAM_LIST_MIRROR: return f64 ? gram_gring_kernel<double, NCT, true> : gram_gring_kernel<float, NCT, true>;
+#ifdef PBN_GRAM_MEASURE
+        case GRAM_CONTIGUOUS_NO_MFMA: return f64 ? gram_glds_kernel<NCT, 1> : gram_glds_f32_kernel<NCT, 1>;
+        case GRAM_CONTIGUOUS_NO_DMA: return f64 ? gram_glds_kernel<NCT, 2> : gram_glds_f32_kernel<NCT, 2>;
+#endif
+    }
+    return nullptr;
+}
+static GramKernel pick_gram(int dtype, GramForm form, int nct) {
+    const bool f64 = dtype == PBN_F64;
+    switch (nct) {
+        case 1: return pick_gram_nct<1>(f64, form);
+        case 2: return pick_gram_nct<2>(f64, form);
+        case 3: return pick_gram_nct<3>(f64, form);
+        case 4: return pick_gram_nct<4>(f64, form);
+        default: throw invalid_error("gram: at most 64 columns per launch");
+    }
+}
+
 int launch_gram(const GramArgs& a_in, int dtype, int nblocks, double* out, hipStream_t st) {
     GramArgs a = a_in;
     // PBN_GRAM_DEBUG (1 = no MFMAs, 2 = no loads: floors of the two halves, garbage statistics) exists in measurement builds only
@@ -1210,10 +905,14 @@ int launch_gram(const GramArgs& a_in, int dtype, int nblocks, double* out, hipSt
     const int nct = (a.n_cols + 15) / 16;
     const int WS = gram_ws(nct);
     const bool gather = a.rows != nullptr;
-    if (dtype == PBN_F64)
-        nblocks = gather ? launch_gram_t<double, true>(a, nct, nblocks, st) : launch_gram_t<double, false>(a, nct, nblocks, st);
-    else
-        nblocks = gather ? launch_gram_t<float, true>(a, nct, nblocks, st) : launch_gram_t<float, false>(a, nct, nblocks, st);
+    GramForm form = gather ? GRAM_LIST : GRAM_CONTIGUOUS;   // a row list never takes the mirror here
+#ifdef PBN_GRAM_MEASURE
+    if (!gather) form = dbg == 1 ? GRAM_CONTIGUOUS_NO_MFMA : dbg >= 2 ? GRAM_CONTIGUOUS_NO_DMA : GRAM_CONTIGUOUS;
+#endif
+    // the rings run one block per resident slot; from here on nblocks is the launched grid (= the partials written)
+    if (!gather && a.num_cus > 0 && nblocks > GD_BLOCKS_PER_CU * a.num_cus) nblocks = GD_BLOCKS_PER_CU * a.num_cus;
+    hipLaunchKernelGGL(pick_gram(dtype, form, nct), dim3(nblocks), dim3(256), 0, st, a);
+    HIP_CHECK(hipGetLastError());
     // tree of arity 16 over the blocks, fixed order
     int stride = 1;
     while ((nblocks + stride - 1) / stride > 16) {
@@ -1223,7 +922,7 @@ int launch_gram(const GramArgs& a_in, int dtype, int nblocks, double* out, hipSt
     }
     hipLaunchKernelGGL(gram_reduce_kernel, dim3((WS + 255) / 256, 1), dim3(256), 0, st, a.partial, nblocks, WS, stride, out);
     HIP_CHECK(hipGetLastError());
-    if (a.stamps && dtype == PBN_F64 && !gather && gram_variant() >= 2) {
+    if (a.stamps && dtype == PBN_F64 && !gather) {
         std::vector<long long> h((size_t)nblocks * 3);
         HIP_CHECK(hipStreamSynchronize(st));
         HIP_CHECK(hipMemcpy(h.data(), stamps_dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
@@ -1243,50 +942,9 @@ void launch_gram_segments(const GramArgs& a_in, int dtype, int nblocks, const in
     const int nct = (a.n_cols + 15) / 16;
     const int WS = gram_ws(nct);
     if (nblocks > 0) {
-        const bool gather = a.rows != nullptr;
-        const dim3 grid(nblocks), block(256);
-        // the kernels of the plain form, block b on the piece blk[4b + 1 .. 2] -> partial slot blk[4b + 3]: the LDS-DMA rings for
-        // contiguous rows, the register ring for row lists (PBN_GRAM_LDS < 2: gram_lds_kernel for both)
-        const bool ring = gram_variant() >= 2;
-#define PBN_SEG_N(K_RING, K_LDS)                                                                \
-    switch (nct) {                                                                              \
-        case 1: if (ring) hipLaunchKernelGGL((K_RING(1)), grid, block, 0, st, a); else hipLaunchKernelGGL((K_LDS(1)), grid, block, 0, st, a); break; \
-        case 2: if (ring) hipLaunchKernelGGL((K_RING(2)), grid, block, 0, st, a); else hipLaunchKernelGGL((K_LDS(2)), grid, block, 0, st, a); break; \
-        case 3: if (ring) hipLaunchKernelGGL((K_RING(3)), grid, block, 0, st, a); else hipLaunchKernelGGL((K_LDS(3)), grid, block, 0, st, a); break; \
-        case 4: if (ring) hipLaunchKernelGGL((K_RING(4)), grid, block, 0, st, a); else hipLaunchKernelGGL((K_LDS(4)), grid, block, 0, st, a); break; \
-        default: throw invalid_error("gram: at most 64 columns per launch");                    \
-    }
-#define PBN_K_GLDS64(N) gram_glds_kernel<N, 0>
-#define PBN_K_GLDS32(N) gram_glds_f32_kernel<N, 0>
-#define PBN_K_GRING64(N) gram_gring_kernel<double, N, false>
-#define PBN_K_GRING32(N) gram_gring_kernel<float, N, false>
-#define PBN_K_GROWS64(N) gram_gring_kernel<double, N, true>
-#define PBN_K_GROWS32(N) gram_gring_kernel<float, N, true>
-#define PBN_K_LDS64(N) gram_lds_kernel<double, N, false>
-#define PBN_K_LDS32(N) gram_lds_kernel<float, N, false>
-#define PBN_K_LDS64G(N) gram_lds_kernel<double, N, true>
-#define PBN_K_LDS32G(N) gram_lds_kernel<float, N, true>
-        const bool mirror = gather && ring && a.rowmajor != nullptr;
-        if (dtype == PBN_F64) {
-            if (mirror) { PBN_SEG_N(PBN_K_GROWS64, PBN_K_LDS64G) }
-            else if (gather) { PBN_SEG_N(PBN_K_GRING64, PBN_K_LDS64G) }
-            else { PBN_SEG_N(PBN_K_GLDS64, PBN_K_LDS64) }
-        } else {
-            if (mirror) { PBN_SEG_N(PBN_K_GROWS32, PBN_K_LDS32G) }
-            else if (gather) { PBN_SEG_N(PBN_K_GRING32, PBN_K_LDS32G) }
-            else { PBN_SEG_N(PBN_K_GLDS32, PBN_K_LDS32) }
-        }
-#undef PBN_SEG_N
-#undef PBN_K_GLDS64
-#undef PBN_K_GLDS32
-#undef PBN_K_GRING64
-#undef PBN_K_GRING32
-#undef PBN_K_GROWS64
-#undef PBN_K_GROWS32
-#undef PBN_K_LDS64
-#undef PBN_K_LDS32
-#undef PBN_K_LDS64G
-#undef PBN_K_LDS32G
+        // the kernels of the plain form, block b on the piece blk[4b + 1 .. 2] -> partial slot blk[4b + 3]
+        const GramForm form = !a.rows ? GRAM_CONTIGUOUS : a.rowmajor ? GRAM_LIST_MIRROR : GRAM_LIST;
+        hipLaunchKernelGGL(pick_gram(dtype, form, nct), dim3(nblocks), dim3(256), 0, st, a);
     }
     if (n_seg > 0) hipLaunchKernelGGL(gram_seg_reduce_kernel, dim3((WS + 63) / 64, n_seg), dim3(64, 4), 0, st, a.partial, blk_off, WS, out);
     HIP_CHECK(hipGetLastError());

@@ -29,7 +29,9 @@ struct GramArgs {
     double* partial;      // device, [nblocks][gram_ws(nct)]
     int num_cus;          // of the device (0 = unknown): gram_glds_kernel runs one block per resident slot
     long long* stamps;    // measurement aid (PBN_GRAM_STAMPS): per-block start / end / hardware slot, or null
-    int debug_skip;       // measurement aid (PBN_GRAM_DEBUG): 1 = no MFMAs (loads + LDS traffic only), 2 = no global loads
+    int debug_skip;       // measurement aid (PBN_GRAM_DEBUG): 1 = no MFMAs (loads + LDS traffic only), 2 = no global loads.  No kernel
+                          // reads it: launch_gram of a -DPBN_GRAM_MEASURE build records the value it picked the contiguous kernel's
+                          // DBG variant by, 0 everywhere else.  It stays so that the kernels' argument block keeps its layout.
 };
 
 struct LgArgs {

@@ -50,7 +50,7 @@ def plain_blocks(n, num_cus):
 
 
 def plain_grid(nblocks, num_cus):
-    """stats_kernels.hip launch_gram_t: if (a.num_cus > 0 && nblocks > GD_BLOCKS_PER_CU * a.num_cus) grid.x = GD_BLOCKS_PER_CU * a.num_cus;"""
+    """stats_kernels.hip launch_gram: if (!gather && a.num_cus > 0 && nblocks > GD_BLOCKS_PER_CU * a.num_cus) nblocks = GD_BLOCKS_PER_CU * a.num_cus;"""
     cap = GD_BLOCKS_PER_CU * num_cus
     return cap if nblocks > cap else nblocks
 

@@ -34,9 +34,6 @@ the installed moments equal a recomputation of the same ranges through the aid, 
 
 What was reached is asserted at the end (test_every_ring_state_was_seen) from the aids' records held against the restatement.
 
-NOT reached from here: gram_kernel and gram_lds_kernel.  A production build compiles PBN_TUNE(GRAM_LDS, 2) to its default, so neither
-launch_gram nor launch_gram_segments can select them.
-
 Measured on an MI355X (256 CUs; this file alone, one pytest process; profiles/gram_shapes/tests.txt): 7.5 s for the 87 tests, the slowest
 (test_segments_rounding[70-8400-float32]) 0.64 s, most of it the longdouble references; the slowest exact test 0.29 s
 (test_plain_exact_capped[4-float32], which also builds its table).  2 198 pbn_debug_table_gram, 28 pbn_debug_scoredata_segments and 144

@@ -6,7 +6,7 @@ def run(env_extra):
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")][-1]
     return json.loads(line[len("RESULT "):])
 a = run({}); 
-for name, env in (("lds1", {"PBN_GRAM_LDS": "1"}), ("nomirror", {"PBN_MI_MIRROR_MB": "0"}), ("nofull", {"PBN_MI_FULLGRAM": "0"})):
+for name, env in (("nomirror", {"PBN_MI_MIRROR_MB": "0"}), ("nofull", {"PBN_MI_FULLGRAM": "0"})):
     b = run(env)
     for key in ("mi_plain", "mi_nulls"):
         x, y = np.array(a[key]), np.array(b[key])

@@ -1,7 +1,7 @@
 """The C4 Gram pass on its own: 2M x 64 fp64 table resident in HBM, pbn_table_sse (pilot + gram + reduce) a few times.
 Run under rocprofv3 --kernel-trace --stats for the gram kernel's duration (tools/gram_timing.sh).  PBN_GRAM_DEBUG=1 / 2 give
-the kernel without its MFMAs / without its global loads (floors; the statistics are then garbage); GRAM_DTYPE=f32 times the
-float table (gram_lds_kernel), PBN_GRAM_LDS=0/1 the older kernels.
+the kernel without its MFMAs / without its global loads (floors; the statistics are then garbage; measurement builds only,
+tools/gram_variants.sh); GRAM_DTYPE=f32 times the float table (gram_glds_f32_kernel).
 GRAM_MODE=segments times the product's score-data constructor (pbn_scoredata_create: the segmented Gram of BGe / BIC, C4's constructor);
 GRAM_MODE=gather the gathered, segmented Gram of a MutualInformation grouping (all continuous columns per configuration of GRAM_CARD
 categories through the grouping's row list, mi.hip ensure_full) - GRAM_GROUPS discrete columns, one grouping each."""
